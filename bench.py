@@ -10,6 +10,11 @@ Launch: `python bench.py` (N=1), `python bench.py --gpus N` (bench.py starts the
 processes itself, as ddp/main.py:46-49's mp.spawn does) or `python -m torch.distributed.run
 --nproc-per-node N ... bench.py --gpus N`. The world size must equal --gpus. Rank 0 prints one
 JSON line.
+
+A plain run sets up, warms up, times --steps steps and prints the line. `--full` adds what takes runs
+of its own after the timed region: the serialized event-timed roofline region, the communication
+timing, config 3 and the all-reduce probe (N > 1), the HBM probe and the CPU baseline. `--dump-outputs
+DIR` writes what the last timed step computed as DIR/<name>.npy (dump_outputs).
 """
 from __future__ import annotations
 
@@ -266,27 +271,32 @@ def bench_dp(args):
     pool = [dtc.data.synthetic_batch(i, B, S, S, 100, dev, templates) for i in range(4)]
     losses = []
 
-    def step(i):
+    def step(i, keep=False):
         img, label = pool[i % len(pool)]
         opt.zero_grad()
         with dtc.autocast():
-            loss = crit(model(img), label)
+            logit = model(img)
+            loss = crit(logit, label)
         scaler.scale(loss).backward()
         scaler.step(opt)
         scaler.update()
         losses.append(loss.item())
+        if keep:  # --dump-outputs: what this step handed its caller
+            last[:] = [logit, loss]
 
+    last = []
     for i in range(args.warmup):
         step(i)
     for d in set(dev_ids):
         torch.cuda.synchronize(d)
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(args.warmup + i)
+        step(args.warmup + i, bool(args.dump_outputs) and i == args.steps - 1)
     for d in set(dev_ids):
         torch.cuda.synchronize(d)
     elapsed = time.perf_counter() - t0
     shared = len(set(dev_ids)) < len(dev_ids)
+    dumped = dump_outputs(args.dump_outputs, last[0], last[1], model.module.flat) if args.dump_outputs else None
     print(json.dumps({
         "metric": f"images/sec ResNet-18 CIFAR-100 DataParallel (global batch {B}, one process)",
         "value": round(B * args.steps / elapsed, 2), "unit": "images/sec", "n_gpus": len(set(dev_ids)),
@@ -300,7 +310,8 @@ def bench_dp(args):
                    else "grouped RCCL broadcast / reduce over distinct devices (dtc_dp_*, ncclCommInitAll)"},
         "note": (f"device_ids {dev_ids}: {len(dev_ids)} replicas on ONE GPU -- the single-GPU form of the "
                  "DataParallel path, NOT BASELINE config 4 (8 GPUs)") if shared else None,
-        "final_loss": round(losses[-1], 4)}), flush=True)
+        "final_loss": round(losses[-1], 4),
+        "dumped_outputs": {"dir": args.dump_outputs, "arrays": dumped} if dumped else None}), flush=True)
 
 
 HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md); measured copy ~6.3 TB/s
@@ -356,6 +367,37 @@ def hbm_probe(dtc, dev, B, S, nparam, reps=20):
     return out
 
 
+DUMP_BUDGET_BYTES = 64 * 10**6  # --dump-outputs: at most this much in all
+
+
+def sample_f32(t, max_numel: int, seed: int = 1234):
+    """float32 host copy of tensor `t`, flattened past `max_numel` elements to a fixed sample: the elements
+    at `max_numel` sorted indices drawn without replacement by numpy's default_rng(seed), so two builds'
+    dumps hold the same elements."""
+    a = t.detach().float().cpu().numpy()
+    if a.size <= max_numel:
+        return np.ascontiguousarray(a)
+    idx = np.sort(np.random.default_rng(seed).choice(a.size, size=max_numel, replace=False))
+    return np.ascontiguousarray(a.reshape(-1)[idx])
+
+
+def dump_outputs(path: str, logits, loss, flat, budget: int = DUMP_BUDGET_BYTES) -> dict:
+    """--dump-outputs: what the caller of the last timed step holds after it, as float32 `path`/<name>.npy:
+    `logits` [B, classes] and `loss` (the forward's results), `params` (the flat fp32 parameter buffer after
+    the optimizer step), `bn_buffers` (the running statistics) and `grads` (a seeded 2M-element sample of the
+    flat gradient buffer as the step left it). Returns {name: shape}; refuses to write more than `budget` bytes."""
+    arrays = {"logits": sample_f32(logits, 1 << 20), "loss": np.array([loss.item()], np.float32),
+              "params": sample_f32(flat.params, 11 << 20), "bn_buffers": sample_f32(flat.bufs, 1 << 20),
+              "grads": sample_f32(flat.grads, 2 << 20)}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > budget:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (> {budget})")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -390,7 +432,7 @@ def main():
     ap.add_argument("--no-allreduce-probe", action="store_true", help="skip the N>1 all-reduce busBW probe")
     ap.add_argument("--no-comm-timing", action="store_true",
                     help="skip the per-bucket / exposed-communication timing region (N>1 or --sim-world)")
-    ap.add_argument("--allreduce-probe", action="store_true", help="run the busBW probe at N=1 too (plumbing check)")
+    ap.add_argument("--allreduce-probe", action="store_true", help="with --full: run the busBW probe at N=1 too (plumbing check)")
     ap.add_argument("--no-hbm-probe", action="store_true", help="skip the BN / SGD HBM-roofline probe")
     ap.add_argument("--sync-bn", action="store_true",
                     help="SyncBatchNorm (off in the reference); at N=1 a one-rank communicator forces the sync path")
@@ -399,7 +441,17 @@ def main():
                     help="PMC conv-traffic summary for roofline.traffic (default: the newest profiles/*conv_traffic.json)")
     ap.add_argument("--stream-prio", type=int, default=0,
                     help="run the step on a torch stream of this priority (-1 = high; 0 = torch's default stream)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the regions that take runs of their own: live roofline, "
+                         "communication timing, config 3 and all-reduce probe (N>1), HBM probe, CPU baseline (each "
+                         "still has its --no-* switch); a plain run skips them all")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (logits, loss, updated parameters, BN buffers, "
+                         "a gradient sample) as float32 DIR/<name>.npy")
     args = ap.parse_args()
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        args.no_live_roofline = args.no_comm_timing = args.no_config3 = True
+        args.no_allreduce_probe = args.no_hbm_probe = args.no_cpu_baseline = True
     if args.mode == "dp":
         return bench_dp(args)
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -451,7 +503,7 @@ def main():
         torch.cuda.synchronize()
         torch.cuda.set_stream(torch.cuda.Stream(dev, priority=args.stream_prio))
 
-    def step(i, b=B, host_sync=True):
+    def step(i, b=B, host_sync=True, keep=False):
         img, label = pools[b][i % len(pools[b])]
         opt.zero_grad()
         with dtc.autocast():
@@ -467,13 +519,17 @@ def main():
         scaler.update()
         if host_sync and not args.no_item:
             losses.append(loss.item())
+        if keep:  # --dump-outputs: what this step handed its caller
+            last[:] = [logit, loss]
 
-    def timed(k, first, b=B, host_sync=True):
+    last = []
+
+    def timed(k, first, b=B, host_sync=True, keep_last=False):
         dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for i in range(k):
-            step(first + i, b, host_sync)
+            step(first + i, b, host_sync, keep_last and i == k - 1)
         torch.cuda.synchronize()
         dist.barrier()
         el = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev)
@@ -483,7 +539,10 @@ def main():
     for i in range(args.warmup):
         step(i)
     # Region 1 (the reported value): K plain steps.
-    elapsed = timed(args.steps, args.warmup)
+    elapsed = timed(args.steps, args.warmup, keep_last=bool(args.dump_outputs))
+    dumped = None
+    if args.dump_outputs and rank == 0:  # before any later region steps the model again
+        dumped = dump_outputs(args.dump_outputs, last[0], last[1], model.module.flat)
     # Region 2 (roofline): the same K steps, serialized and eager (options bwd_streams=0, graphs=0: every
     # kernel has the chip to itself and is launched on the compute stream), with every timed launcher call
     # bracketed by two HIP timing events on that stream (dtc_rn18_profile_events: its launch duration as
@@ -573,7 +632,7 @@ def main():
     if rank == 0:
         conv_ms = sum(ms)
         conv_flops = sum(fl)
-        traffic, traffic_src = committed_traffic(B, S, args.traffic_file)
+        traffic, traffic_src = committed_traffic(B, S, args.traffic_file) if args.full else (None, None)
         n_launch = sum(cnt)
         # refuse a fraction whose time total misses launches (event pool used up) -- it would be overstated
         achieved = conv_flops / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 and ev_dropped.value == 0 else None
@@ -599,6 +658,7 @@ def main():
             "warmup": args.warmup,
             "ms_per_step": round(elapsed / args.steps * 1e3, 4),
             "higher_is_better": True,
+            "full": bool(args.full),
             "scaling": "strong" if args.global_batch else "weak",
             "vs_baseline": None,
             "dtype": "bf16",
@@ -662,6 +722,8 @@ def main():
                                                 / BF16_PEAK_TFLOPS, 4),
             "final_loss": round(losses[-1], 4) if losses else None,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if comm_exposed is not None:
             out["comm_exposed_us"] = comm_exposed
             out["buckets_us"] = buckets_us

@@ -124,6 +124,44 @@ def test_prof_summary_flops_follow_the_bench_batch(tmp_path):
     assert ps.bench_gflop(str(f))[0] is None
 
 
+def test_dump_outputs_float32_seeded_sample_within_budget(bench, tmp_path):
+    """--dump-outputs: float32 <name>.npy files of what the last step left; a buffer past its cap is cut to a
+    fixed seeded sample (the same elements on every run), and the whole dump stays under the byte budget."""
+    import types
+
+    import numpy as np
+    import torch
+
+    g = torch.Generator().manual_seed(0)
+    flat = types.SimpleNamespace(params=torch.randn(1000, generator=g), bufs=torch.randn(64, generator=g),
+                                 grads=torch.randn((2 << 20) + 77, generator=g))
+    logits = torch.randn(4, 100, generator=g).bfloat16()
+    loss = torch.tensor(4.625)
+    shapes = bench.dump_outputs(str(tmp_path / "a"), logits, loss, flat)
+    bench.dump_outputs(str(tmp_path / "b"), logits, loss, flat)
+    assert set(shapes) == {"logits", "loss", "params", "bn_buffers", "grads"}
+    total = 0
+    for name, shape in shapes.items():
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and list(a.shape) == shape and np.array_equal(a, b)
+        total += a.nbytes
+    assert total <= bench.DUMP_BUDGET_BYTES
+    assert np.array_equal(np.load(tmp_path / "a" / "logits.npy"), logits.float().numpy())
+    assert np.load(tmp_path / "a" / "loss.npy").tolist() == [4.625]
+    assert np.array_equal(np.load(tmp_path / "a" / "params.npy"), flat.params.numpy())
+    gs = np.load(tmp_path / "a" / "grads.npy")
+    assert gs.shape == (2 << 20,) and np.isin(gs[:100], flat.grads.numpy()).all()
+    with pytest.raises(SystemExit, match="--dump-outputs would write"):
+        bench.dump_outputs(str(tmp_path / "c"), logits, loss, flat, budget=1 << 20)
+    assert not (tmp_path / "c").exists()
+
+
+def test_plain_run_has_full_and_dump_switches():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs DIR" in r.stdout
+
+
 def test_comm_timing_fields(bench):
     """the N>1 line carries comm_exposed_us (tail + weight-gradient join wait) and buckets_us
     (per bucket start / end / duration) from dtc_rn18_comm_timing_result's arrays."""

@@ -19,7 +19,7 @@
 set -u
 TAG=$1; shift
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
-BA=${BENCH_ARGS:-}
+BA="--full ${BENCH_ARGS:-}"  # every bench.py run below keeps its extra regions (cut back by $QUIET)
 QUIET="--no-cpu-baseline --no-live-roofline --no-hbm-probe"
 specs=()
 for st in "$@"; do

@@ -8,7 +8,7 @@ mkdir -p gpurun_out
 for r in $(seq 1 $R); do
   for spec in "$@"; do
     tag="${spec%%=*}"; lib="${spec#*=}"
-    DTC_LIB=$lib timeout -k 10 200 python bench.py --no-cpu-baseline --no-hbm-probe --steps 40 --warmup 10 ${BENCH_ARGS:-} \
+    DTC_LIB=$lib timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-hbm-probe --steps 40 --warmup 10 ${BENCH_ARGS:-} \
       > gpurun_out/lab_run.json 2> gpurun_out/lab_run.err || { echo "run $tag failed"; tail -5 gpurun_out/lab_run.err; exit 1; }
     python - "$tag" <<'PY' | tee -a gpurun_out/lab_ab.txt
 import json, sys

@@ -7,7 +7,7 @@ mkdir -p gpurun_out
 for r in $(seq 1 $R); do
   for spec in "$@"; do
     tag="${spec%%|*}"; opts="${spec#*|}"
-    timeout -k 10 200 python bench.py --no-cpu-baseline --no-hbm-probe --steps 40 --warmup 10 $opts \
+    timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-hbm-probe --steps 40 --warmup 10 $opts \
       > gpurun_out/ol_run.json 2> gpurun_out/ol_run.err || { echo "run $tag failed"; tail -5 gpurun_out/ol_run.err; exit 1; }
     python - "$tag" <<'PY' | tee -a gpurun_out/ol_ab.txt
 import json, sys

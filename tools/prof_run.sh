@@ -15,7 +15,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out
 mkdir -p "$OUT"
 ( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats $EXTRA -d "$OUT/prof_$TAG" -o prof -- \
-    python3 "$ROOT/bench.py" --steps 20 --warmup 5 --no-cpu-baseline $LIVE --no-hbm-probe "$@" \
+    python3 "$ROOT/bench.py" --full --steps 20 --warmup 5 --no-cpu-baseline $LIVE --no-hbm-probe "$@" \
     > "$OUT/${TAG}_prof_bench.json" ) || exit $?
 python3 "$ROOT/tools/prof_summary.py" "$OUT/prof_$TAG" "$OUT/${TAG}_kernel_trace.md" --bench "$OUT/${TAG}_prof_bench.json" > /dev/null
 python3 "$ROOT/tools/step_timeline.py" "$OUT/prof_$TAG" > "$OUT/${TAG}_timeline.txt" 2>&1 || true
