@@ -47,6 +47,13 @@ class ConvDesc(C.Structure):
 
 PConv = C.POINTER(ConvDesc)
 
+
+class EvalRecord(C.Structure):
+    """dtc_eval_record: one evaluation batch's metrics (16 bytes, device memory)."""
+
+    _fields_ = [("loss", C.c_float), ("n", C.c_int32), ("top1", C.c_int32), ("topk", C.c_int32)]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "dtc_abi_version": (i32, []),
@@ -85,6 +92,7 @@ _SIGS = {
     "dtc_xent_fwd": (i32, [vp, vp, i32, i32, vp, vp, vp]),
     "dtc_xent_fwd_ex": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]),
     "dtc_xent_bwd": (i32, [vp, vp, vp, vp, i32, i32, vp, vp]),
+    "dtc_eval_metrics": (i32, [vp, vp, i32, i32, i32, vp, vp]),
     "dtc_sgd_nesterov_flat": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, vp, vp, vp]),
     "dtc_cast_f32_bf16": (i32, [vp, vp, i64, vp]),
     "dtc_amp_scale": (i32, [vp, vp, vp, i64, vp]),
@@ -142,6 +150,7 @@ _SIGS = {
     "dtc_rn18_forward": (i32, [vp, vp, vp, i32, vp]),
     "dtc_rn18_backward": (i32, [vp, vp, f32, vp, vp]),
     "dtc_rn18_xent_backward": (i32, [vp, vp, vp, vp, vp, f32, vp, vp]),
+    "dtc_rn18_eval_batch": (i32, [vp, vp, vp, i32, i32, vp, vp, vp]),
     "dtc_rn18_set_sync_bn": (i32, [vp, vp]),
     "dtc_rn18_dlogits_buffer": (i32, [vp, C.POINTER(sz)]),
 }

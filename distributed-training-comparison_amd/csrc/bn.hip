@@ -91,12 +91,36 @@ __global__ void bn_eval_coef_kernel(int C, const float* __restrict__ gamma, cons
                                     float* __restrict__ shift) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  const float is = 1.f / sqrtf(rv[c] + eps);
-  mean[c] = rm[c];
-  invstd[c] = is;
-  const float a = gamma[c] * is;
-  scale[c] = a;
-  shift[c] = beta[c] - rm[c] * a;
+  bn_eval_coef_channel(c, gamma, beta, rm, rv, eps, mean, invstd, scale, shift);
+}
+
+// Every BatchNorm of the network in one launch: workgroup b serves the 256 channels from (b - blk0) * 256 of the
+// table entry whose workgroup range holds b (a uniform scan of at most DTC_EVAL_BN_MAX entries of the kernel
+// argument segment)
+__global__ void __launch_bounds__(256) bn_eval_coef_all_kernel(const BnEvalTable tab, float eps) {
+  const int b = blockIdx.x;
+  int i = 0;
+  while (i + 1 < tab.n && tab.e[i + 1].blk0 <= b) ++i;
+  const BnEvalEntry& e = tab.e[i];
+  const int c = (b - e.blk0) * 256 + threadIdx.x;
+  if (c >= e.C) return;
+  bn_eval_coef_channel(c, e.gamma, e.beta, e.rmean, e.rvar, eps, e.mean, e.invstd, e.scale, e.shift);
+}
+
+int bn_eval_coef_all(BnEvalTable& tab, float eps, hipStream_t st) {
+  DTC_CHECK_ARG(tab.n > 0 && tab.n <= DTC_EVAL_BN_MAX, "bn_eval_coef_all: %d BatchNorms (1..%d)", tab.n,
+                DTC_EVAL_BN_MAX);
+  int blocks = 0;
+  for (int i = 0; i < tab.n; ++i) {
+    BnEvalEntry& e = tab.e[i];
+    DTC_CHECK_ARG(e.gamma && e.beta && e.rmean && e.rvar && e.mean && e.invstd && e.scale && e.shift && e.C > 0,
+                  "bn_eval_coef_all: bad entry %d", i);
+    e.blk0 = blocks;
+    blocks += ceil_div_i(e.C, 256);
+  }
+  DTC_KLAUNCH(bn_eval_coef_all_kernel, dim3(blocks), dim3(256), 0, st, tab, eps);
+  DTC_LAUNCH_CHECK();
+  return 0;
 }
 
 int bn_eval_coef(int C, const float* gamma, const float* beta, const float* running_mean, const float* running_var,

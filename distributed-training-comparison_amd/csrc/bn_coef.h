@@ -136,6 +136,22 @@ __device__ __forceinline__ void fa_fwd_coef_from(const BnFwdArgs& A, const SlotF
   lds_barrier();
 }
 
+// eval mode: channel c's scale / shift from the running statistics (mean / invstd also written, for reference).
+// ONE definition for bn_eval_coef_kernel and bn_eval_coef_all_kernel (bn.hip), so the two cannot differ in FMA
+// contraction: an evaluation batch and an eval-mode forward apply bit-identical coefficients.
+__device__ __forceinline__ void bn_eval_coef_channel(int c, const float* __restrict__ gamma,
+                                                     const float* __restrict__ beta, const float* __restrict__ rm,
+                                                     const float* __restrict__ rv, float eps, float* __restrict__ mean,
+                                                     float* __restrict__ invstd, float* __restrict__ scale,
+                                                     float* __restrict__ shift) {
+  const float is = 1.f / sqrtf(rv[c] + eps);
+  mean[c] = rm[c];
+  invstd[c] = is;
+  const float a = gamma[c] * is;
+  scale[c] = a;
+  shift[c] = beta[c] - rm[c] * a;
+}
+
 __device__ __forceinline__ void fa_fwd_coef(const BnFwdArgs& A, int C, int cg, int64_t* part, float* sc, float* sh) {
   SlotFold f;
   fold_issue_fwd(A, C, cg, f);

@@ -396,6 +396,10 @@ int dtc_xent_fwd_ex(const float* logits, const int64_t* labels, int n, int ncls,
                     const float* scale, float* scaled, float* host_loss, void* stream) {
   GUARD(return xent_fwd_fused(logits, labels, n, ncls, loss, lse, scale, scaled, host_loss, S(stream));)
 }
+int dtc_eval_metrics(const float* logits, const int64_t* labels, int n, int ncls, int topk, dtc_eval_record* rec,
+                     void* stream) {
+  GUARD(return eval_metrics(logits, labels, n, ncls, topk, rec, S(stream));)
+}
 int dtc_xent_bwd(const float* logits, const int64_t* labels, const float* lse, const float* gscale, int n, int ncls,
                  float* dlogits, void* stream) {
   return xent_bwd(logits, labels, lse, gscale, n, ncls, dlogits, S(stream));

@@ -187,11 +187,36 @@ __device__ __forceinline__ float row16_max(float v) {
   v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xF, 0xF, false)));
   return v;
 }
+// the same tree over int32 counts (exact in any order; the fixed tree keeps one code shape with the float folds)
+__device__ __forceinline__ int row16_sum_i(int v) {
+  v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, false);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, false);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x124, 0xF, 0xF, false);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x128, 0xF, 0xF, false);
+  return v;
+}
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+
+// Per-row log-sum-exp: sixteen lanes per row (one DPP row), lane l holding z[l], z[l + 16], ...: a per-lane
+// max / sum over its values, then the 16-lane DPP tree (four VALU steps, no LDS permutes). The same function
+// (same per-lane order, same tree) serves xent_lse_kernel, the one-launch xent_fwd_fused_kernel (head.hip) and eval_metrics_kernel (metrics.hip), so
+// all three produce bit-identical lse and loss.
+__device__ __forceinline__ float row_lse16(const float* __restrict__ z, int ncls, int li) {
+  float m = -INFINITY;
+#pragma unroll 8
+  for (int j = li; j < ncls; j += 16) m = fmaxf(m, z[j]);
+  m = row16_max(m);
+  float s = 0.f;
+#pragma unroll 8
+  for (int j = li; j < ncls; j += 16) s += expf(z[j] - m);
+  s = row16_sum(s);
+  return m + logf(s);
+}
+
 
 // ---------------------------------------------------------------- BN statistic accumulators
 // A BN's batch sums (sum x, sum x^2 in the forward; sum dz, sum dz * xhat in the backward) are built from

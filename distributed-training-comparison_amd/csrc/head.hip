@@ -222,22 +222,7 @@ int head_fwd(const float* act, int N, int HW, int C, const float* wfc, const flo
   return head_fwd_t<float>(act, N, HW, C, wfc, bfc, ncls, feat, logits, st);
 }
 
-// Per-row log-sum-exp: sixteen lanes per row (one DPP row), lane l holding z[l], z[l + 16], ...: a per-lane
-// max / sum over its values, then the 16-lane DPP tree (four VALU steps, no LDS permutes). The same function
-// (same per-lane order, same tree) serves xent_lse_kernel and the one-launch xent_fwd_fused_kernel, so both
-// produce bit-identical lse and loss.
-__device__ __forceinline__ float row_lse16(const float* __restrict__ z, int ncls, int li) {
-  float m = -INFINITY;
-#pragma unroll 8
-  for (int j = li; j < ncls; j += 16) m = fmaxf(m, z[j]);
-  m = row16_max(m);
-  float s = 0.f;
-#pragma unroll 8
-  for (int j = li; j < ncls; j += 16) s += expf(z[j] - m);
-  s = row16_sum(s);
-  return m + logf(s);
-}
-
+// (row_lse16, the per-row log-sum-exp shared with metrics.hip, is in common.h)
 __global__ void __launch_bounds__(256) xent_lse_kernel(const float* __restrict__ logits, int N, int ncls,
                                                       float* __restrict__ lse) {
   const int li = threadIdx.x & 15;

@@ -7,6 +7,8 @@
 #include "common.h"
 #include "bnb_epi.h"
 
+struct dtc_eval_record;  // include/dtc.h
+
 namespace dtc {
 
 // ------------------------------------------------------------------ tuning options (atomic ints)
@@ -188,6 +190,26 @@ int bn_fwd_finalize(int64_t* stats, int C, int64_t count, const float* gamma, co
 // eval mode: scale/shift from running statistics (mean/invstd also written for reference)
 int bn_eval_coef(int C, const float* gamma, const float* beta, const float* running_mean, const float* running_var,
                  float eps, float* mean, float* invstd, float* scale, float* shift, hipStream_t st);
+// the same for every BatchNorm of a network in ONE launch, driven by a by-value descriptor table (the kernel
+// argument segment holds it: nothing is allocated). Per channel the arithmetic is bn_eval_coef's own device
+// function (bn_coef.h). blk0 is filled by the launcher.
+constexpr int DTC_EVAL_BN_MAX = 20;  // ResNet-18: 20 BatchNorms, 72 B each = 1.4 KB of kernel arguments
+struct BnEvalEntry {
+  int C = 0, blk0 = 0;  // channels; first workgroup of this BN (256 channels per workgroup)
+  const float* gamma = nullptr;
+  const float* beta = nullptr;
+  const float* rmean = nullptr;
+  const float* rvar = nullptr;
+  float* mean = nullptr;
+  float* invstd = nullptr;
+  float* scale = nullptr;
+  float* shift = nullptr;
+};
+struct BnEvalTable {
+  BnEvalEntry e[DTC_EVAL_BN_MAX];
+  int n = 0;
+};
+int bn_eval_coef_all(BnEvalTable& tab, float eps, hipStream_t st);
 // y = relu(x*scale + shift)
 int bn_apply_relu(const u16* x, const float* scale, const float* shift, u16* y, int64_t M, int C, hipStream_t st);
 // y = relu(x*scale + shift + res)            (identity shortcut)
@@ -307,6 +329,10 @@ int xent_fwd_fused(const float* logits, const int64_t* labels, int N, int ncls, 
                    const float* scale, float* scaled, float* host, hipStream_t st);
 int xent_fwd(const float* logits, const int64_t* labels, int N, int ncls, float* loss, float* lse,
              hipStream_t st);
+// evaluation metrics of one batch (metrics.hip): mean cross-entropy (bit-identical to xent_fwd's), the row count
+// and the top-1 / top-k hit counts into one 16-byte device record, one launch (N <= 4096)
+int eval_metrics(const float* logits, const int64_t* labels, int N, int ncls, int topk, ::dtc_eval_record* rec,
+                 hipStream_t st);
 // dlogits = (softmax - onehot) * (*gscale) / N
 int xent_bwd(const float* logits, const int64_t* labels, const float* lse, const float* gscale, int N, int ncls,
              float* dlogits, hipStream_t st);

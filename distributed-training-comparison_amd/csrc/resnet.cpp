@@ -100,6 +100,9 @@ struct Net {
   // them already used (a second backward over one forward) zeroes them first instead of adding onto
   // the previous backward's sums
   bool sums_fresh = false;
+  // set by eval_batch around its forward body: one bn_eval_coef_all launch already wrote every BN's scale /
+  // shift (and mean / invstd), so the eval branch of bn_act / bn_act_f32 skips the per-BN coefficient launches
+  bool coef_ready = false;
   // buckets: [offset, numel) in flat elements, and the block index after whose backward it fires
   std::vector<int64_t> bucket_off, bucket_len;
   std::vector<int> bucket_after_block;  // -1 = after the stem (last)
@@ -658,8 +661,10 @@ static int bn_act(Net& n, int mode, BNL& b, const u16* x, BNL* b2, const u16* x2
     prof_ev_close(n, ev);
     return rc;
   }
-  DTC_TRY(bn_finalize_fwd(n, b, cnt, train, st));
-  if (b2) DTC_TRY(bn_finalize_fwd(n, *b2, cnt, train, st));
+  if (!n.coef_ready) {
+    DTC_TRY(bn_finalize_fwd(n, b, cnt, train, st));
+    if (b2) DTC_TRY(bn_finalize_fwd(n, *b2, cnt, train, st));
+  }
   const float* s1 = n.at<float>(b.scale);
   const float* h1 = n.at<float>(b.shift);
   if (mode == 1) return bn_apply_relu(x, s1, h1, y, M, b.C, st);
@@ -749,8 +754,10 @@ static int bn_act_f32(Net& n, int mode, BNL& b, const float* x, BNL* b2, const f
     const BnFwdArgs a2 = b2 ? fwd_args(n, *b2, cnt) : BnFwdArgs{};
     return bn_fin_apply(mode, x, a1, x2, b2 ? &a2 : nullptr, y, M, b.C, st);
   }
-  DTC_TRY(bn_finalize_fwd(n, b, cnt, false, st));
-  if (b2) DTC_TRY(bn_finalize_fwd(n, *b2, cnt, false, st));
+  if (!n.coef_ready) {
+    DTC_TRY(bn_finalize_fwd(n, b, cnt, false, st));
+    if (b2) DTC_TRY(bn_finalize_fwd(n, *b2, cnt, false, st));
+  }
   const float* s1 = n.at<float>(b.scale);
   const float* h1 = n.at<float>(b.shift);
   if (mode == 1) return bn_apply_relu(x, s1, h1, y, M, b.C, st);
@@ -935,6 +942,58 @@ static int forward_impl(Net& n, const float* x, float* logits, bool train, hipSt
   if (!n.f32) return forward_head(n, logits, st);
   DTC_HIP(hipMemcpyAsync(logits, n.at<float>(n.LOGITS), (size_t)n.B * n.ncls * 4, hipMemcpyDeviceToDevice, st));
   return 0;
+}
+
+// One evaluation batch (reference trainer.py validate / test): the eval-mode forward of the first nv images of
+// x and the batch's metrics, enqueued with no host synchronisation. The input is staged as forward_impl stages
+// it, for nv images, and the remaining B - nv image slots of the executor's own input are zeroed: eval-mode rows
+// are independent (running statistics), so the valid rows' logits do not depend on the padding, and a short
+// last batch needs no second executor. Every BN's coefficients come from ONE launch (bn_eval_coef_all) instead
+// of one per BN; the body then runs as forward(train = 0) does, always eagerly (no graph is captured, replayed
+// or dropped) and without profiling slots.
+static int eval_batch(Net& n, const float* x, const int64_t* labels, int nv, int topk, float* logits,
+                      ::dtc_eval_record* rec, hipStream_t st) {
+  n.prof_st = st;
+  const size_t img = (size_t)n.H * n.W;  // pixels per image
+  const int pad = n.B - nv;
+  if (n.f32) {  // fp32 im2col rows [B*H*W][32]
+    DTC_TRY(f32_stem_im2col(x, n.at<float>(n.X0), nv, n.H, n.W, st));
+    if (pad) DTC_TRY(zero_bytes(n.ws + n.X0 + (size_t)nv * img * 32 * 4, (size_t)pad * img * 32 * 4, st));
+  } else if (n.stem_direct) {  // the executor's copy of the fp32 NCHW input
+    const size_t xb = (size_t)nv * 3 * img * 4, zb = (size_t)pad * 3 * img * 4;
+    char* xin = n.ws + n.XIN;
+    if (xb % 16 == 0 && zb % 8 == 0 && ((uintptr_t)x & 15) == 0 && option_get(OPT_STEM_PROLOGUE) != 0) {
+      DTC_TRY(copy_and_zero(x, xin, xb, xin + xb, zb, st));  // one launch: copy the images, zero the padding
+    } else {
+      DTC_HIP(hipMemcpyAsync(xin, x, xb, hipMemcpyDeviceToDevice, st));
+      if (zb) DTC_HIP(hipMemsetAsync(xin + xb, 0, zb, st));
+    }
+  } else {  // bf16 im2col rows [B*H*W][64]
+    DTC_TRY(stem_im2col(x, n.at<u16>(n.X0), nv, n.H, n.W, st));
+    if (pad) DTC_TRY(zero_bytes(n.ws + n.X0 + (size_t)nv * img * 64 * 2, (size_t)pad * img * 64 * 2, st));
+  }
+  BnEvalTable tab;
+  DTC_CHECK_ARG(n.bns.size() <= (size_t)DTC_EVAL_BN_MAX, "eval_batch: %zu BatchNorms", n.bns.size());
+  for (BNL* b : n.bns) {
+    BnEvalEntry& e = tab.e[tab.n++];
+    e.C = b->C;
+    e.gamma = n.pf(b->gidx);
+    e.beta = n.pf(b->bidx);
+    e.rmean = n.bufs + b->rm_off;
+    e.rvar = n.bufs + b->rv_off;
+    e.mean = n.at<float>(b->mean);
+    e.invstd = n.at<float>(b->invstd);
+    e.scale = n.at<float>(b->scale);
+    e.shift = n.at<float>(b->shift);
+  }
+  DTC_TRY(bn_eval_coef_all(tab, 1e-5f, st));
+  float* lg = logits ? logits : n.at<float>(n.LOGITS);
+  n.coef_ready = true;
+  const int rc = forward_body(n, lg, false, st);  // (sets prof_next = PROF_SLOTS: eval passes are not timed)
+  n.coef_ready = false;
+  n.sums_fresh = false;  // the saved mean / invstd slots now hold the running statistics
+  DTC_TRY(rc);
+  return eval_metrics(lg, labels, nv, n.ncls, topk, rec, st);
 }
 
 // Bucket point after block `after_block` (-1: after the stem). Eager: all-reduce the buckets that
@@ -1950,6 +2009,17 @@ int dtc_rn18_set_sync_bn(dtc_net* net, dtc_comm* comm) {
 int dtc_rn18_forward(dtc_net* net, const float* x, float* logits, int train, void* stream) {
   DTC_CHECK_ARG(net && net->n.ws && x && logits, "dtc_rn18_forward: unbound net or null pointer");
   return forward(net->n, x, logits, train != 0, (hipStream_t)stream);
+}
+
+int dtc_rn18_eval_batch(dtc_net* net, const float* x, const int64_t* labels, int n_valid, int topk, float* logits,
+                        dtc_eval_record* rec, void* stream) {
+  DTC_CHECK_ARG(net != nullptr, "dtc_rn18_eval_batch: null net");
+  DTC_CHECK_ARG(n_valid >= 1 && n_valid <= net->n.B && n_valid <= 4096,
+                "dtc_rn18_eval_batch: n_valid = %d outside [1, min(batch = %d, 4096)]", n_valid, net->n.B);
+  DTC_CHECK_ARG(topk >= 1 && topk <= net->n.ncls, "dtc_rn18_eval_batch: topk = %d outside [1, num_classes = %d]", topk,
+                net->n.ncls);
+  DTC_CHECK_ARG(net->n.ws && x && labels && rec, "dtc_rn18_eval_batch: unbound net or null pointer");
+  return eval_batch(net->n, x, labels, n_valid, topk, logits, rec, (hipStream_t)stream);
 }
 
 int dtc_rn18_backward(dtc_net* net, const float* dlogits, float grad_scale, dtc_comm* comm, void* stream) {

@@ -148,6 +148,19 @@ class Executor:
         self.generation += 1
         return self.generation
 
+    def eval_batch(self, x: torch.Tensor, labels: torch.Tensor, n_valid: int, topk: int, rec: torch.Tensor,
+                   logits: Optional[torch.Tensor] = None) -> int:
+        """One evaluation batch (dtc_rn18_eval_batch): the eval-mode forward of the first `n_valid` images of
+        x (fp32 NCHW, contiguous) and their loss / top-1 / top-k counts against `labels` (int64) into `rec`
+        (a contiguous int32 [4] device tensor, see ops.eval_metrics), enqueued with no host synchronisation.
+        `logits` (fp32 [batch, num_classes]) receives the logits when given. The call overwrites the
+        BatchNorm statistics a training forward saved, so it starts a new generation: a backward still
+        pending on an earlier training forward is refused by consume()."""
+        call("dtc_rn18_eval_batch", self.handle, ptr(x), ptr(labels), int(n_valid), int(topk), ptr(logits), ptr(rec),
+             stream_ptr())
+        self.generation += 1
+        return self.generation
+
     def consume(self, gen: int) -> None:
         """Claim the forward of generation `gen` for one backward. The kernels WRITE gradients, which
         equals the reference's zero_grad() + backward(); a second backward over the same forward
@@ -468,6 +481,59 @@ class CrossEntropyLoss(nn.Module):
         return _XentFn.apply(logits, labels)
 
 
+# ----------------------------------------------------------------------------- evaluation result
+class EvalResult:
+    """Per-batch metrics of ``ResNet.evaluate``: arrays ``loss`` (fp32 mean cross-entropy of each batch), ``n``
+    (rows), ``top1`` and ``topk`` (rows whose label ranks < 1 / < k, int32), in batch order; ``k`` is the
+    top-k that was asked for."""
+
+    def __init__(self, loss, n, top1, topk, k: int):
+        import numpy as np
+
+        self.loss = np.asarray(loss, dtype=np.float32)
+        self.n = np.asarray(n, dtype=np.int32)
+        self.top1 = np.asarray(top1, dtype=np.int32)
+        self.topk = np.asarray(topk, dtype=np.int32)
+        self.k = int(k)
+
+    @classmethod
+    def from_records(cls, records: torch.Tensor, k: int) -> "EvalResult":
+        """records: an int32 [batches, 4] host tensor of dtc_eval_record words."""
+        r = records.contiguous().numpy().reshape(-1, 4)
+        return cls(r[:, 0].copy().view("float32"), r[:, 1], r[:, 2], r[:, 3], k)
+
+    def __len__(self) -> int:
+        return int(self.n.shape[0])
+
+    def reference_meters(self) -> Dict[str, float]:
+        """What the reference's validate / test report (trainer.py:170-215): an ``AverageMeter`` fed each
+        batch's mean loss and each batch's ``accuracy`` value -- the fp32 product count * (100 / n), as
+        utils.py:18-31 forms it -- with weight 1 per batch, so a short last batch counts as much as a full
+        one. Keys: loss, top1, topk (0.0 for an empty evaluation, the meter's initial value)."""
+        import numpy as np
+
+        def avg(vals):
+            s, cnt = 0.0, 0
+            for v in vals:  # AverageMeter.update(v): sum += v * 1; avg = sum / count
+                s += float(v) * 1
+                cnt += 1
+            return s / cnt if cnt else 0.0
+
+        scale = (100.0 / self.n.astype(np.float64)).astype(np.float32)  # mul_(100.0 / batch_size) on an fp32 tensor
+        return {"loss": avg(self.loss), "top1": avg(self.top1.astype(np.float32) * scale),
+                "topk": avg(self.topk.astype(np.float32) * scale)}
+
+    def totals(self) -> Dict[str, float]:
+        """Sample-weighted totals over all rows: mean loss, top-1 / top-k accuracy in percent, row count."""
+        import numpy as np
+
+        rows = int(self.n.sum())
+        if rows == 0:
+            return {"loss": 0.0, "top1": 0.0, "topk": 0.0, "n": 0}
+        return {"loss": float(np.dot(self.loss.astype(np.float64), self.n) / rows),
+                "top1": 100.0 * int(self.top1.sum()) / rows, "topk": 100.0 * int(self.topk.sum()) / rows, "n": rows}
+
+
 # ----------------------------------------------------------------------------- modules
 class BasicBlock(nn.Module):
     """Parameter container with reference net.py:13-38's construction order and names."""
@@ -655,6 +721,49 @@ class ResNet(nn.Module):
             x = x.float().contiguous()
         exe = self.executor(x.shape[0], x.shape[2], x.shape[3])
         return _NetFn.apply(x, self._anchor, self, exe)
+
+    # ------------------------------------------------------------------ evaluation
+    def evaluate(self, batches, topk: int = 5) -> EvalResult:
+        """The reference's validate / test loop (trainer.py:170-215) on the device: for every (images, labels)
+        batch one native call enqueues the eval-mode forward and the batch's loss / top-1 / top-k counts into
+        the next slot of one device record buffer -- no host synchronisation per batch -- and ONE
+        device-to-host copy at the end brings all records back. Runs under no_grad semantics (nothing is
+        recorded for autograd, running statistics are used and left untouched, whatever ``self.training``
+        says) in the current ``compute_precision()``. The executor is the one for the first batch's size; a
+        smaller batch (the short last one) runs on it through ``n_valid``, a larger one takes the executor
+        of its own size. `batches` needs a length (a list or a loader), else it is materialised first."""
+        flat = self.flat
+        if not hasattr(batches, "__len__"):
+            batches = list(batches)
+        precision = self.compute_precision()
+        dev = flat.device
+        cap = len(batches)
+        recs = torch.empty(max(cap, 1), 4, dtype=torch.int32, device=dev)
+        first = None
+        i = 0
+        with torch.no_grad():
+            for x, y in batches:
+                if i >= cap:
+                    raise NativeError(f"evaluate: the loader yielded more than its len() = {cap} batches")
+                x = x.to(dev, non_blocking=True)
+                y = y.to(dev, non_blocking=True)
+                if x.dim() != 4 or x.shape[1] != 3:
+                    raise ValueError(f"expected [N,3,H,W] input, got {tuple(x.shape)}")
+                if x.dtype != torch.float32 or not x.is_contiguous():
+                    x = x.float().contiguous()
+                if y.dtype != torch.int64 or not y.is_contiguous():
+                    y = y.long().contiguous()
+                n, h, w = x.shape[0], x.shape[2], x.shape[3]
+                if y.dim() != 1 or y.shape[0] != n:
+                    raise ValueError(f"expected {n} labels, got {tuple(y.shape)}")
+                if first is None:
+                    first = self.executor(n, h, w, precision)
+                exe = first
+                if n > exe.batch or (h, w) != (exe.height, exe.width):
+                    exe = self.executor(n, h, w, precision)
+                exe.eval_batch(x, y, n, topk, recs[i])
+                i += 1
+        return EvalResult.from_records(recs[:i].cpu(), topk)  # the one device-to-host copy (and wait)
 
 
 class SyncBatchNorm:

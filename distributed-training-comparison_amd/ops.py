@@ -323,6 +323,21 @@ def xent_fwd(logits, labels):
     return loss, lse
 
 
+def eval_metrics(logits, labels, topk=5, out=None):
+    """One evaluation batch's metrics in one launch, no host sync (dtc_eval_metrics): logits fp32 [n, ncls],
+    labels int64 [n] -> an int32 [4] device tensor viewing one 16-byte record (loss, n, top1, topk): word 0
+    holds the fp32 mean cross-entropy's bits (``rec[:1].view(torch.float32)``), bit-identical to
+    ``xent_fwd``'s; top1 / topk count the rows whose label ranks < 1 / < topk (ties to the lower index).
+    `out`: a contiguous int32 [4] device tensor to write (e.g. one slot of a record buffer)."""
+    require_cuda(logits, labels, out)
+    n, ncls = logits.shape
+    rec = torch.empty(4, dtype=torch.int32, device=logits.device) if out is None else out
+    if rec.dtype != torch.int32 or rec.numel() != 4 or not rec.is_contiguous():
+        raise NativeError("eval_metrics: out must be a contiguous int32 [4] tensor")
+    call("dtc_eval_metrics", ptr(logits), ptr(labels), n, ncls, int(topk), ptr(rec), stream_ptr())
+    return rec
+
+
 def xent_bwd(logits, labels, lse, gscale=None, out=None):
     n, ncls = logits.shape
     dl = torch.empty_like(logits) if out is None else out

@@ -56,6 +56,9 @@ def load_config(argv=None, mode: str = "ddp"):
     p.add_argument("--max-steps", type=int, default=0, help="stop each epoch after N steps (0 = full epoch)")
     p.add_argument("--device-data", action="store_true", default=False,
                    help="HBM-resident uint8 dataset + on-GPU crop/flip/normalize (data.DeviceLoader)")
+    p.add_argument("--fused-eval", action="store_true", default=False,
+                   help="validate()/test() on the device: one native call per batch (eval forward + loss + top-k "
+                        "counts), one device-to-host copy per evaluation (ResNet.evaluate); same numbers")
     if mode == "dp":  # not in the reference (nn.DataParallel takes every visible GPU): replica placement
         p.add_argument("--device-ids", type=lambda v: [int(d) for d in v.split(",")], default=None,
                        help="comma-separated GPU ids of the replicas (may repeat); default: all visible")
@@ -230,7 +233,27 @@ class Trainer:
         # (dp/trainer.py:121-129 calls self.model, the DataParallel wrapper)
         return self.model.module if self.distributed else self.model
 
+    def _module_for_eval(self):
+        """--fused-eval: the native ResNet that ``evaluate`` runs on. DDP: rank 0's unwrapped module, as
+        the default path. DP: the wrapped module on device_ids[0] -- evaluation batches are NOT scattered
+        over the replicas and gathered back (the default path's ``self.model(img)`` does that); a
+        scattered device-side evaluation is not implemented."""
+        return self.model.module if (self.distributed or self.data_parallel) else self.model
+
+    def _fused_meters(self, loader, topk: int):
+        """The meters of validate() / test() from one on-device evaluation (ResNet.evaluate)."""
+        m = self._module_for_eval().evaluate(loader, topk=topk).reference_meters()
+        out = []
+        for key in ("loss", "top1", "topk"):
+            meter = AverageMeter()
+            meter.avg = m[key]
+            out.append(meter)
+        return out
+
     def validate(self, epoch: int) -> Tuple[float, float]:
+        if getattr(self.hparams, "fused_eval", False):
+            val_loss, top1, _ = self._fused_meters(self.val_loader, 1)
+            return val_loss.avg, top1.avg
         val_loss, top1 = AverageMeter(), AverageMeter()
         net = self._module()  # rank 0 evaluates the unwrapped module (SURVEY A.3)
         net.eval()
@@ -246,16 +269,19 @@ class Trainer:
     def test(self, state_dict) -> dict:
         test_loss, top1, top5 = AverageMeter(), AverageMeter(), AverageMeter()
         self.model.load_state_dict(state_dict)
-        net = self._module()
-        net.eval()
-        with torch.no_grad():
-            for img, label in self.test_loader:
-                img, label = img.to(self.device), label.to(self.device)
-                pred = net(img)
-                test_loss.update(self.criterion(pred, label).item())
-                p1, p5 = accuracy(pred, label, topk=(1, 5))
-                top1.update(p1.item())
-                top5.update(p5.item())
+        if getattr(self.hparams, "fused_eval", False):
+            test_loss, top1, top5 = self._fused_meters(self.test_loader, 5)
+        else:
+            net = self._module()
+            net.eval()
+            with torch.no_grad():
+                for img, label in self.test_loader:
+                    img, label = img.to(self.device), label.to(self.device)
+                    pred = net(img)
+                    test_loss.update(self.criterion(pred, label).item())
+                    p1, p5 = accuracy(pred, label, topk=(1, 5))
+                    top1.update(p1.item())
+                    top5.update(p5.item())
         logging.info(f"** Test Loss: {test_loss.avg:.4f}")
         logging.info(f"** Top-1 Accuracy: {top1.avg:.4f}%")
         logging.info(f"** Top-5 Accuracy: {top5.avg:.4f}%")

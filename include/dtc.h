@@ -176,6 +176,23 @@ int dtc_xent_fwd_ex(const float* logits, const int64_t* labels, int n, int ncls,
                     const float* scale, float* scaled, float* host_loss, void* stream);
 int dtc_xent_bwd(const float* logits, const int64_t* labels, const float* lse, const float* gscale, int n, int ncls,
                  float* dlogits, void* stream);
+/* Evaluation metrics of one batch (reference trainer.py validate / test: `criterion(pred, label).item()` and
+ * utils.py:18-31 `accuracy(pred, label, topk)`), one launch of one workgroup, no host synchronisation: writes
+ * *rec (device memory, 16 bytes) and nothing else. 1 <= n <= 4096, ncls >= 1, 1 <= topk <= ncls.
+ *   loss        mean cross-entropy over the n rows, bit-identical to what dtc_xent_fwd stores in *loss (an
+ *               out-of-range label makes it NaN, as there);
+ *   n           the row count;
+ *   top1, topk  rows whose label has rank < 1 / rank < topk, where for a label y in range
+ *                 rank = #{ j != y : !(z[j] <= z[y]) } + #{ j < y : z[j] == z[y] }
+ *               (strictly greater logits first, ties to the lower index, a NaN logit above everything; a NaN
+ *               label logit gives rank ncls - 1). A row whose label is out of range counts for neither.
+ *               torch.topk leaves the order of ties unspecified; on tie-free rows the two agree. */
+typedef struct dtc_eval_record {
+  float loss;
+  int32_t n, top1, topk;
+} dtc_eval_record; /* 16 bytes */
+int dtc_eval_metrics(const float* logits, const int64_t* labels, int n, int ncls, int topk, dtc_eval_record* rec,
+                     void* stream);
 
 /* ------------------------------------------------------------------ optimizer / AMP
  * sgd: optim.SGD(lr, weight_decay, momentum, nesterov=True).step() (trainer.py:92-98, 158) over a
@@ -336,6 +353,19 @@ int dtc_rn18_set_sync_bn(dtc_net* net, dtc_comm* comm);
  * log-sum-exp dtc_xent_fwd wrote, gscale: device fp32 scalar or NULL (1). */
 int dtc_rn18_xent_backward(dtc_net* net, const float* logits, const int64_t* labels, const float* lse,
                            const float* gscale, float grad_scale, dtc_comm* comm, void* stream);
+/* One evaluation batch (reference trainer.py validate / test: `net(img)` in eval mode, the loss and
+ * `accuracy`) as one call with no host synchronisation: the eval-mode forward (running statistics) of the
+ * first n_valid images of x, then dtc_eval_metrics over their logits and labels into *rec (device memory).
+ * 1 <= n_valid <= batch (and <= 4096); exactly n_valid images of x and n_valid labels are read. The remaining
+ * batch - n_valid image slots of the executor's own input are zeroed; eval-mode rows are independent, so the
+ * valid rows' logits do not depend on that padding -- a short last batch runs on the full-batch executor.
+ * logits: fp32 [batch][num_classes] (rows >= n_valid are the padding's), or NULL = a workspace region.
+ * The BatchNorm coefficients of all layers are computed by one launch; the other launches are those of
+ * dtc_rn18_forward(train = 0). Always runs eagerly (option "graphs" does not apply), takes no profiling slots,
+ * both precisions. Leaves parameters, running statistics and num_batches_tracked untouched; overwrites the
+ * saved mean / invstd of every BatchNorm, so a backward of an earlier training forward must not follow. */
+int dtc_rn18_eval_batch(dtc_net* net, const float* x, const int64_t* labels, int n_valid, int topk, float* logits,
+                        dtc_eval_record* rec, void* stream);
 /* Byte offset into the workspace of the executor's own fp32 [batch][num_classes] dlogits buffer.
  * A caller that writes the loss gradient there (e.g. the fused cross-entropy backward) and passes
  * that pointer to dtc_rn18_backward saves the graph path's copy-in. */
