@@ -15,7 +15,8 @@ from ._native import NativeError  # noqa: F401
 from . import data, ops  # noqa: F401
 from .amp import GradScaler, autocast  # noqa: F401
 from .nn import BasicBlock, CrossEntropyLoss, EvalResult, ResNet, ResNet18, SyncBatchNorm  # noqa: F401
-from .optim import SGD  # noqa: F401
+from . import optim  # noqa: F401
+from .optim import SGD, Adam, AdamW, clip_grad_norm_  # noqa: F401
 from .parallel import DDP, Comm, DataParallel, DistributedDataParallel, barrier  # noqa: F401
 from . import parallel  # noqa: F401
 from . import trainer  # noqa: F401

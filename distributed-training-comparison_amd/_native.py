@@ -35,6 +35,7 @@ vp = C.c_void_p
 i32 = C.c_int
 i64 = C.c_int64
 f32 = C.c_float
+f64 = C.c_double
 sz = C.c_size_t
 P64 = C.POINTER(C.c_int64)
 Pi32 = C.POINTER(C.c_int)
@@ -94,6 +95,10 @@ _SIGS = {
     "dtc_xent_bwd": (i32, [vp, vp, vp, vp, i32, i32, vp, vp]),
     "dtc_eval_metrics": (i32, [vp, vp, i32, i32, i32, vp, vp]),
     "dtc_sgd_nesterov_flat": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, vp, vp, vp]),
+    "dtc_adam_state_words": (i32, []),
+    "dtc_adam_flat": (i32, [vp, vp, vp, vp, vp, i64, vp, f64, f64, f64, f64, f64, i32, vp, vp, vp]),
+    "dtc_grad_norm_workspace_bytes": (sz, [i64]),
+    "dtc_grad_norm_clip": (i32, [vp, i64, vp, f64, vp, vp, vp, vp]),
     "dtc_cast_f32_bf16": (i32, [vp, vp, i64, vp]),
     "dtc_amp_scale": (i32, [vp, vp, vp, i64, vp]),
     "dtc_amp_check_finite": (i32, [vp, i64, vp, vp]),

@@ -409,6 +409,17 @@ int dtc_sgd_nesterov_flat(float* p, const float* g, float* mom, uint16_t* pb, in
                           const float* inv_scale, const int* found_inf, void* stream) {
   return sgd_nesterov(p, g, mom, pb, n, lr, wd, mu, inv_scale, found_inf, S(stream));
 }
+int dtc_adam_state_words(void) { return DTC_ADAM_STATE_WORDS; }
+int dtc_adam_flat(float* p, const float* g, float* m, float* v, uint16_t* pb, int64_t n, void* state, double lr,
+                  double beta1, double beta2, double eps, double wd, int decoupled, const float* inv_scale,
+                  const int* found_inf, void* stream) {
+  return adam_flat(p, g, m, v, pb, n, state, lr, beta1, beta2, eps, wd, decoupled, inv_scale, found_inf, S(stream));
+}
+size_t dtc_grad_norm_workspace_bytes(int64_t n) { return grad_norm_workspace_bytes(n); }
+int dtc_grad_norm_clip(const float* g, int64_t n, const float* inv_scale, double max_norm, void* workspace,
+                       float* total_norm, float* grad_mult, void* stream) {
+  return grad_norm_clip(g, n, inv_scale, max_norm, workspace, total_norm, grad_mult, S(stream));
+}
 int dtc_cast_f32_bf16(const float* src, uint16_t* dst, int64_t n, void* stream) {
   return cast_f32_bf16(src, dst, n, S(stream));
 }

@@ -359,6 +359,19 @@ int head_bwd(const float* dlogits, const float* feat, const u16* wfc, int N, int
 // Nesterov SGD over a flat buffer (torch.optim.SGD semantics, dampening 0).
 int sgd_nesterov(float* p, const float* g, float* mom, u16* p_bf16, int64_t n, float lr, float wd, float mu,
                  const float* inv_scale, const int* found_inf, hipStream_t st);
+// Adam / AdamW over a flat buffer (torch.optim.Adam / AdamW semantics, amsgrad off): a one-thread tick that
+// advances the device-side step count in `state` (DTC_ADAM_STATE_WORDS zeroed 32-bit words, 16-byte aligned)
+// unless *found_inf, then the update. The scalars are doubles: 1-beta, 1-lr*wd and the bias corrections are
+// formed in double, as torch forms them from Python floats.
+#define DTC_ADAM_STATE_WORDS 4
+int adam_flat(float* p, const float* g, float* m, float* v, u16* p_bf16, int64_t n, void* state, double lr,
+              double beta1, double beta2, double eps, double wd, int decoupled, const float* inv_scale,
+              const int* found_inf, hipStream_t st);
+// total_norm = inv_scale * ||g||_2 and grad_mult = inv_scale * min(1, max_norm / (total_norm + 1e-6)), on the
+// device; double accumulation in a fixed order (bit-reproducible). workspace: grad_norm_workspace_bytes(n).
+size_t grad_norm_workspace_bytes(int64_t n);
+int grad_norm_clip(const float* g, int64_t n, const float* inv_scale, double max_norm, void* workspace,
+                   float* total_norm, float* grad_mult, hipStream_t st);
 int cast_f32_bf16(const float* src, u16* dst, int64_t n, hipStream_t st);
 // zero an 8-byte aligned range (a kernel node, unlike hipMemsetAsync's fill dispatch)
 int zero_bytes(void* p, size_t bytes, hipStream_t st);

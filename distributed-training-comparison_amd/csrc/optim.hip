@@ -48,6 +48,192 @@ int sgd_nesterov(float* p, const float* g, float* mom, u16* p_bf16, int64_t n, f
   return 0;
 }
 
+// ---------------------------------------------------------------- Adam / AdamW
+// torch.optim.Adam / AdamW (amsgrad=False, maximize=False), per element and in torch's own operation order
+// (_single_tensor_adam):
+//     g' = g * gmul ;  Adam: g' += wd*p ;  AdamW: p *= 1 - lr*wd
+//     m += (g' - m)*(1-b1) ;  v = b2*v + (1-b2)*g'*g'
+//     p -= (lr/bc1) * (m / (sqrt(v)/sqrt(bc2) + eps)),   bc1 = 1 - b1^t, bc2 = 1 - b2^t
+// The step count t lives in a small device record (AdamState): a GradScaler-skipped step must not advance it,
+// and the host cannot know about a skip without a synchronisation. A one-thread "tick" launch ahead of the
+// update advances t (unless *found_inf) and writes the two factors that depend on it, computed in double
+// as torch's Python scalars are; the update launch only reads the record, so no block can see it half
+// written (stream order separates the two launches). Two launches per step, no host synchronisation.
+struct AdamState {
+  int step;         // completed (non-skipped) steps
+  float step_size;  // lr / bc1
+  float bc2_sqrt;   // sqrt(bc2)
+  int reserved;
+};
+static_assert(sizeof(AdamState) == 4 * DTC_ADAM_STATE_WORDS, "AdamState is DTC_ADAM_STATE_WORDS 32-bit words");
+
+// b^t by squaring, in double: at most 62 multiplications (1 - b^t within 2e-14 of pow()'s, invisible once
+// the factors are rounded to float), a fraction of the time of two library pow() calls in a one-thread kernel
+__device__ __forceinline__ double pow_int(double b, int t) {
+  double r = 1.0;
+  for (; t > 0; t >>= 1, b *= b)
+    if (t & 1) r *= b;
+  return r;
+}
+
+__global__ void adam_tick_kernel(AdamState* __restrict__ s, double lr, double b1, double b2,
+                                 const int* __restrict__ found_inf) {
+  if (found_inf && *found_inf) return;
+  const int t = s->step + 1;
+  s->step = t;
+  s->step_size = (float)(lr / (1.0 - pow_int(b1, t)));
+  s->bc2_sqrt = (float)sqrt(1.0 - pow_int(b2, t));
+}
+
+// omb1 = 1-b1, omb2 = 1-b2, decay = 1 - lr*wd are formed in double by the launcher: 1.f - 0.999f is
+// 0.00100004673, 4.7e-5 off, an order of magnitude more than the whole update's fp32 error.
+template <bool DECOUPLED>
+__global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                   float* __restrict__ m, float* __restrict__ v,
+                                                   u16* __restrict__ pb, int64_t n4,
+                                                   const AdamState* __restrict__ state, float omb1, float b2,
+                                                   float omb2, float eps, float wd, float decay,
+                                                   const float* __restrict__ inv_scale,
+                                                   const int* __restrict__ found_inf) {
+  if (found_inf && *found_inf) return;  // GradScaler: skip the whole step (the tick skipped it too)
+  const float is = inv_scale ? *inv_scale : 1.f;
+  const float step_size = state->step_size, bc2_sqrt = state->bc2_sqrt;
+  for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+    f32x4 pv = *(const f32x4*)(p + i * 4);
+    f32x4 gv = *(const f32x4*)(g + i * 4) * is;
+    f32x4 mv = *(const f32x4*)(m + i * 4);
+    f32x4 vv = *(const f32x4*)(v + i * 4);
+    if (DECOUPLED) pv = pv * decay;
+    else gv = gv + pv * wd;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      // the roundings of torch's CPU kernels: lerp_ is one fused multiply-add, addcmul_ another on mul_'s result
+      mv[k] = fmaf(gv[k] - mv[k], omb1, mv[k]);
+      vv[k] = fmaf(omb2 * gv[k], gv[k], vv[k] * b2);
+      pv[k] -= step_size * (mv[k] / (sqrtf(vv[k]) / bc2_sqrt + eps));
+    }
+    *(f32x4*)(p + i * 4) = pv;
+    *(f32x4*)(m + i * 4) = mv;
+    *(f32x4*)(v + i * 4) = vv;
+    uint2 w;
+    w.x = pack_bf2(pv[0], pv[1]);
+    w.y = pack_bf2(pv[2], pv[3]);
+    *(uint2*)(pb + i * 4) = w;
+  }
+}
+
+static bool aligned16(const void* a) { return ((uintptr_t)a & 15) == 0; }
+
+int adam_flat(float* p, const float* g, float* m, float* v, u16* p_bf16, int64_t n, void* state, double lr,
+              double beta1, double beta2, double eps, double wd, int decoupled, const float* inv_scale,
+              const int* found_inf, hipStream_t st) {
+  DTC_CHECK_ARG(p && g && m && v && p_bf16 && state, "adam_flat: null pointer");
+  DTC_CHECK_ARG(n > 0 && (n % 4) == 0, "adam_flat: n = %lld must be a positive multiple of 4", (long long)n);
+  DTC_CHECK_ARG(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && ((uintptr_t)p_bf16 & 7) == 0 &&
+                    ((uintptr_t)state & 15) == 0,
+                "adam_flat: p, g, m, v and state must be 16-byte aligned, p_bf16 8-byte aligned");
+  DTC_CHECK_ARG(eps > 0.0, "adam_flat: eps = %g must be positive", eps);
+  DTC_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0,
+                "adam_flat: betas (%g, %g) must lie in [0, 1)", beta1, beta2);
+  DTC_CHECK_ARG(lr >= 0.0 && wd >= 0.0, "adam_flat: lr = %g and weight_decay = %g must not be negative", lr, wd);
+  const int64_t n4 = n / 4;
+  const int blocks = (int)std::min<int64_t>(2048, (n4 + 255) / 256);
+  DTC_KLAUNCH(adam_tick_kernel, dim3(1), dim3(1), 0, st, (AdamState*)state, lr, beta1, beta2, found_inf);
+  const float omb1 = (float)(1.0 - beta1), b2 = (float)beta2, omb2 = (float)(1.0 - beta2);
+  const float decay = (float)(1.0 - lr * wd);
+  if (decoupled)
+    DTC_KLAUNCH(adam_kernel<true>, dim3(blocks), dim3(256), 0, st, p, g, m, v, p_bf16, n4, (const AdamState*)state,
+                omb1, b2, omb2, (float)eps, (float)wd, decay, inv_scale, found_inf);
+  else
+    DTC_KLAUNCH(adam_kernel<false>, dim3(blocks), dim3(256), 0, st, p, g, m, v, p_bf16, n4, (const AdamState*)state,
+                omb1, b2, omb2, (float)eps, (float)wd, decay, inv_scale, found_inf);
+  DTC_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---------------------------------------------------------------- global gradient norm + clip coefficient
+// torch.nn.utils.clip_grad_norm_(norm_type=2) over the flat gradient buffer, with the GradScaler factor
+// folded in: total_norm = inv_scale * sqrt(sum g^2), grad_mult = inv_scale * min(1, max_norm / (total_norm
+// + 1e-6)). The optimizer kernels take grad_mult where they would take inv_scale, so the clip costs one
+// read pass and no write pass. Squares are accumulated in double (loss-scaled gradients overflow and
+// underflow fp32 squares) and in a fixed order -- per thread in index order, a butterfly over the wave, the
+// block's waves in index order, one workspace slot per block, the slots in index order -- with no
+// floating-point atomics: the result is bit-identical from run to run.
+constexpr int GN_THREADS = 1024;  // one workgroup per CU fills it (16 waves), and keeps the slot count small
+constexpr int GN_MAX_BLOCKS = 256;
+static int grad_norm_blocks(int64_t n) {
+  return (int)std::max<int64_t>(1, std::min<int64_t>(GN_MAX_BLOCKS, (n / 4 + GN_THREADS - 1) / GN_THREADS));
+}
+size_t grad_norm_workspace_bytes(int64_t n) { return n > 0 ? (size_t)grad_norm_blocks(n) * sizeof(double) : 0; }
+
+__device__ __forceinline__ double sumsq4(double acc, const f32x4& a) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const double d = (double)a[k];
+    acc += d * d;
+  }
+  return acc;
+}
+
+__global__ void __launch_bounds__(GN_THREADS) grad_sumsq_kernel(const float* __restrict__ g, int64_t n4,
+                                                                double* __restrict__ slots) {
+  const int64_t stride = (int64_t)gridDim.x * GN_THREADS;
+  const f32x4* __restrict__ g4 = (const f32x4*)g;
+  double acc = 0.0;
+  int64_t i = blockIdx.x * (int64_t)GN_THREADS + threadIdx.x;
+  for (; i + 3 * stride < n4; i += 4 * stride) {  // four loads in flight per thread per trip
+    const f32x4 a = g4[i], b = g4[i + stride], c = g4[i + 2 * stride], d = g4[i + 3 * stride];
+    acc = sumsq4(sumsq4(sumsq4(sumsq4(acc, a), b), c), d);
+  }
+  for (; i < n4; i += stride) acc = sumsq4(acc, g4[i]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);  // a + b == b + a: every lane gets the same bits
+  __shared__ double wsum[GN_THREADS / 64];
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = wsum[0];
+#pragma unroll
+    for (int w = 1; w < GN_THREADS / 64; ++w) s += wsum[w];
+    slots[blockIdx.x] = s;
+  }
+}
+
+__global__ void __launch_bounds__(64) grad_norm_finalize_kernel(const double* __restrict__ slots, int nslots,
+                                                                const float* __restrict__ inv_scale,
+                                                                double max_norm, float* __restrict__ total_norm,
+                                                                float* __restrict__ grad_mult) {
+  __shared__ double sh[GN_MAX_BLOCKS];
+#pragma unroll
+  for (int k = threadIdx.x; k < GN_MAX_BLOCKS; k += 64) sh[k] = k < nslots ? slots[k] : 0.0;  // one memory latency
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double s = 0.0;  // index order; the unused slots add + 0.0, which changes no bit of a sum of squares
+#pragma unroll 16
+  for (int k = 0; k < GN_MAX_BLOCKS; ++k) s += sh[k];
+  const double is = inv_scale ? (double)*inv_scale : 1.0;
+  const double tn = is * sqrt(s);
+  const double c = max_norm / (tn + 1e-6);
+  const double coef = c > 1.0 ? 1.0 : c;  // clamp(max=1) that keeps a NaN a NaN, as torch's does
+  *total_norm = (float)tn;
+  *grad_mult = (float)(is * coef);
+}
+
+int grad_norm_clip(const float* g, int64_t n, const float* inv_scale, double max_norm, void* workspace,
+                   float* total_norm, float* grad_mult, hipStream_t st) {
+  DTC_CHECK_ARG(g && workspace && total_norm && grad_mult, "grad_norm_clip: null pointer");
+  DTC_CHECK_ARG(n > 0 && (n % 4) == 0, "grad_norm_clip: n = %lld must be a positive multiple of 4", (long long)n);
+  DTC_CHECK_ARG(aligned16(g) && ((uintptr_t)workspace & 7) == 0,
+                "grad_norm_clip: g must be 16-byte aligned, the workspace 8-byte aligned");
+  DTC_CHECK_ARG(max_norm > 0.0, "grad_norm_clip: max_norm = %g must be positive", max_norm);
+  const int blocks = grad_norm_blocks(n);
+  DTC_KLAUNCH(grad_sumsq_kernel, dim3(blocks), dim3(GN_THREADS), 0, st, g, n / 4, (double*)workspace);
+  DTC_KLAUNCH(grad_norm_finalize_kernel, dim3(1), dim3(64), 0, st, (const double*)workspace, blocks, inv_scale,
+              max_norm, total_norm, grad_mult);
+  DTC_LAUNCH_CHECK();
+  return 0;
+}
+
 __global__ void cast_f32_bf16_kernel(const float* __restrict__ s, u16* __restrict__ d, int64_t n) {
   for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) d[i] = f2bf(s[i]);
 }

@@ -111,6 +111,10 @@ class FlatState:
         self.params_bf16 = torch.zeros(layout.flat_numel, dtype=torch.bfloat16, device=device)
         self.bufs = torch.zeros(layout.bufs_numel, dtype=torch.float32, device=device)
         self.nbt = torch.zeros(len(layout.bns), dtype=torch.int64, device=device)
+        # optim.clip_grad_norm_: the device-side gradient multiplier the next optimizer step applies
+        self.grad_mult = None
+        self.norm_ws = None
+        self.clip_pending = False
 
     def refresh_bf16(self):
         ops.cast_f32_bf16(self.params, self.params_bf16)

@@ -350,6 +350,38 @@ def sgd_nesterov_flat(p, g, mom, pb, lr, weight_decay, momentum, inv_scale=None,
          float(momentum), ptr(inv_scale), ptr(found_inf), stream_ptr())
 
 
+def adam_state(device):
+    """The zeroed device state record of one adam_flat optimizer (word 0: the int32 step count)."""
+    return torch.zeros(lib.dtc_adam_state_words(), dtype=torch.int32, device=device)
+
+
+def adam_flat(p, g, m, v, pb, state, lr, beta1, beta2, eps, weight_decay, decoupled, inv_scale=None, found_inf=None):
+    """One torch.optim.Adam (decoupled=False) / AdamW (decoupled=True) step over flat fp32 buffers, the bf16
+    shadow `pb` refreshed in the same pass; `state` from adam_state() carries the device-side step count."""
+    call("dtc_adam_flat", ptr(p), ptr(g), ptr(m), ptr(v), ptr(pb), p.numel(), ptr(state), float(lr), float(beta1),
+         float(beta2), float(eps), float(weight_decay), int(bool(decoupled)), ptr(inv_scale), ptr(found_inf),
+         stream_ptr())
+
+
+def grad_norm_workspace(n, device):
+    return torch.empty(max(1, lib.dtc_grad_norm_workspace_bytes(int(n)) // 8), dtype=torch.float64, device=device)
+
+
+def grad_norm_clip(g, max_norm, inv_scale=None, workspace=None, total_norm=None, grad_mult=None):
+    """(total_norm, grad_mult), two fp32 [1] device tensors: the L2 norm of g * inv_scale and inv_scale *
+    min(1, max_norm / (total_norm + 1e-6)) (torch.nn.utils.clip_grad_norm_'s coefficient with the GradScaler
+    factor folded in). No host synchronisation; bit-identical from run to run."""
+    if workspace is None:
+        workspace = grad_norm_workspace(g.numel(), g.device)
+    if total_norm is None:
+        total_norm = torch.empty(1, dtype=torch.float32, device=g.device)
+    if grad_mult is None:
+        grad_mult = torch.empty(1, dtype=torch.float32, device=g.device)
+    call("dtc_grad_norm_clip", ptr(g), g.numel(), ptr(inv_scale), float(max_norm), ptr(workspace), ptr(total_norm),
+         ptr(grad_mult), stream_ptr())
+    return total_norm, grad_mult
+
+
 def cast_f32_bf16(src, dst):
     call("dtc_cast_f32_bf16", ptr(src), ptr(dst), src.numel(), stream_ptr())
 

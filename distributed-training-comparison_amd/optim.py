@@ -1,10 +1,16 @@
-"""optim.SGD mirror running the fused flat-buffer Nesterov kernel.
+"""optim.SGD / Adam / AdamW mirrors running fused flat-buffer kernels, and clip_grad_norm_.
 
 Reference: ``optim.SGD(self.model.parameters(), lr, weight_decay, momentum=0.9, nesterov=True)``
-(src/ddp/trainer.py:92-98) stepped through ``GradScaler.step`` (trainer.py:158). The class
-subclasses ``torch.optim.Optimizer`` so ``optim.lr_scheduler.StepLR`` (trainer.py:101-105)
-drives ``param_groups[0]['lr']`` unchanged; ``step()`` enqueues ONE kernel over the model's
-flat parameter / gradient / momentum buffers that also refreshes the bf16 weight shadow.
+(src/ddp/trainer.py:92-98) stepped through ``GradScaler.step`` (trainer.py:158); the reference's README
+invites users to swap the optimizer in ``configure_optimizers`` ("e.g. using ADAM optimizer"). The classes
+subclass ``torch.optim.Optimizer`` so ``optim.lr_scheduler.StepLR`` (trainer.py:101-105) drives
+``param_groups[0]['lr']`` unchanged; ``step()`` enqueues ONE update kernel over the model's flat
+parameter / gradient / state buffers that also refreshes the bf16 weight shadow (Adam: plus a one-thread
+tick that advances the device-side step count).
+
+``clip_grad_norm_`` computes the global gradient norm and the clip coefficient on the device and DEFERS
+the clip: the multiplier is handed to the next ``optimizer.step()``, which applies it to the gradients as it
+reads them. ``p.grad`` keeps showing the unclipped gradients.
 """
 from __future__ import annotations
 
@@ -15,35 +21,49 @@ from . import ops
 from ._native import NativeError
 
 
-class SGD(Optimizer):
-    def __init__(self, params, lr, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False):
+def _model_of(params, who: str):
+    """The native ResNet whose flat buffers hold `params` (every parameter view carries a weak reference)."""
+    ref = getattr(params[0], "_dtc_model", None) if params else None
+    model = ref() if ref is not None else None
+    if model is None:
+        raise NativeError(f"{who} parameters do not belong to a native ResNet moved to the GPU "
+                          f"(create the optimizer after model.to('cuda'))")
+    return model
+
+
+def _check_owns_all(params, flat, who: str):
+    ids = {p.data_ptr() for p in params}
+    if len(ids) != len(flat.layout.params):
+        raise NativeError(f"{who} must own every parameter of the model (flat-buffer update)")
+
+
+class _FlatOptimizer(Optimizer):
+    """What the fused optimizers share: one parameter group that owns every parameter of one native model,
+    lazy binding to its FlatState, the no-op zero_grad, and a step() that hands the kernel the device-side
+    gradient multiplier (GradScaler's inv_scale, or a pending clip_grad_norm_ multiplier) and found_inf."""
+
+    def __init__(self, params, defaults):
         params = list(params)
-        if isinstance(params[0], dict):
+        if params and isinstance(params[0], dict):
             raise NotImplementedError("per-parameter groups are not used by the reference (trainer.py:92-98)")
-        defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov)
         super().__init__(params, defaults)
-        if not nesterov or dampening != 0.0 or momentum <= 0.0:
-            raise NotImplementedError("the fused kernel implements SGD(momentum>0, dampening=0, nesterov=True) "
-                                      "as used by the reference (trainer.py:92-98)")
         self._flat = None
-        self._mom = None
 
     def attach(self, model):
         """Bind to the model's flat buffers (done lazily on the first step)."""
         flat = model.flat
-        ids = {p.data_ptr() for p in self.param_groups[0]["params"]}
-        if len(ids) != len(flat.layout.params):
-            raise NativeError("SGD must own every parameter of the model (flat-buffer update)")
+        _check_owns_all(self.param_groups[0]["params"], flat, type(self).__name__)
         self._flat = flat
-        self._mom = torch.zeros_like(flat.params)
+        self._init_state(flat)
 
     def _find_flat(self):
-        ref = getattr(self.param_groups[0]["params"][0], "_dtc_model", None)
-        model = ref() if ref is not None else None
-        if model is None:
-            raise NativeError("SGD parameters do not belong to a native ResNet moved to the GPU "
-                              "(create the optimizer after model.to('cuda'))")
-        return model
+        return _model_of(self.param_groups[0]["params"], type(self).__name__)
+
+    def _init_state(self, flat):
+        raise NotImplementedError
+
+    def _update(self, flat, group, grad_mult, found_inf):
+        raise NotImplementedError
 
     def zero_grad(self, set_to_none: bool = True):
         # The native backward WRITES every gradient (it never accumulates), which is exactly
@@ -56,7 +76,104 @@ class SGD(Optimizer):
             raise NotImplementedError("closures are not used by the reference")
         if self._flat is None:
             self.attach(self._find_flat())
-        g = self.param_groups[0]
-        ops.sgd_nesterov_flat(self._flat.params, self._flat.grads, self._mom, self._flat.params_bf16, g["lr"],
-                              g["weight_decay"], g["momentum"], inv_scale, found_inf)
+        flat = self._flat
+        if flat.clip_pending:  # clip_grad_norm_ ran since the last step: its multiplier includes inv_scale
+            inv_scale = flat.grad_mult
+            flat.clip_pending = False
+        self._update(flat, self.param_groups[0], inv_scale, found_inf)
         return None
+
+
+class SGD(_FlatOptimizer):
+    def __init__(self, params, lr, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False):
+        defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov)
+        super().__init__(params, defaults)
+        if not nesterov or dampening != 0.0 or momentum <= 0.0:
+            raise NotImplementedError("the fused kernel implements SGD(momentum>0, dampening=0, nesterov=True) "
+                                      "as used by the reference (trainer.py:92-98)")
+        self._mom = None
+
+    def _init_state(self, flat):
+        self._mom = torch.zeros_like(flat.params)
+
+    def _update(self, flat, g, grad_mult, found_inf):
+        ops.sgd_nesterov_flat(flat.params, flat.grads, self._mom, flat.params_bf16, g["lr"], g["weight_decay"],
+                              g["momentum"], grad_mult, found_inf)
+
+
+class Adam(_FlatOptimizer):
+    """torch.optim.Adam (amsgrad=False, maximize=False) on the fused flat-buffer kernel. The step count lives
+    on the device and does not advance on a step GradScaler skips, as torch's ``state['step']``."""
+
+    _decoupled = False
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False,
+                 maximize=False):
+        if amsgrad or maximize:
+            raise NotImplementedError("the fused kernel implements amsgrad=False, maximize=False")
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 < eps:
+            raise ValueError(f"Invalid epsilon value: {eps} (the fused kernel needs eps > 0)")
+        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError(f"Invalid beta parameters: {betas}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize)
+        super().__init__(params, defaults)
+        self._exp_avg = self._exp_avg_sq = self._step_state = None
+
+    def _init_state(self, flat):
+        self._exp_avg = torch.zeros_like(flat.params)
+        self._exp_avg_sq = torch.zeros_like(flat.params)
+        self._step_state = ops.adam_state(flat.params.device)
+
+    def _update(self, flat, g, grad_mult, found_inf):
+        ops.adam_flat(flat.params, flat.grads, self._exp_avg, self._exp_avg_sq, flat.params_bf16, self._step_state,
+                      g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], self._decoupled,
+                      grad_mult, found_inf)
+
+
+class AdamW(Adam):
+    """torch.optim.AdamW: Adam with decoupled weight decay (p *= 1 - lr * weight_decay)."""
+
+    _decoupled = True
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False,
+                 maximize=False):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad,
+                         maximize=maximize)
+
+
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, scaler=None) -> torch.Tensor:
+    """torch.nn.utils.clip_grad_norm_ for a native model: one read pass over the flat gradient buffer and a
+    tiny finalize, nothing leaves the GPU.
+
+    ``parameters`` must be all parameters of one native ResNet. With ``scaler`` (a GradScaler, after its
+    ``unscale_`` -- which here only checks for inf/NaN and leaves the gradients loss-scaled) the scaler's
+    device-side 1/scale is folded in. Returns the total norm of the unscaled gradients as a 0-dim device
+    tensor, without a host synchronisation.
+
+    Deviation from torch: the gradients are NOT rewritten. The multiplier is stored on the model's
+    FlatState and the next ``step()`` of SGD / Adam / AdamW applies it where it would apply ``inv_scale``
+    (no extra read-modify-write pass over the gradients); ``p.grad`` keeps showing the unclipped values.
+    """
+    if float(norm_type) != 2.0:
+        raise NotImplementedError("only the L2 norm (norm_type=2) is implemented")
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    params = list(parameters)
+    flat = _model_of(params, "clip_grad_norm_").flat
+    _check_owns_all(params, flat, "clip_grad_norm_")
+    if flat.grad_mult is None:
+        flat.grad_mult = torch.empty(1, dtype=torch.float32, device=flat.device)
+        flat.norm_ws = ops.grad_norm_workspace(flat.grads.numel(), flat.device)
+    inv_scale = None
+    if scaler is not None and scaler.is_enabled():
+        scaler._lazy_init(flat.device)
+        inv_scale = scaler._inv_scale
+    # a fresh word per call (an allocation, not a launch): norms the caller kept stay valid
+    total_norm = torch.empty(1, dtype=torch.float32, device=flat.device)
+    ops.grad_norm_clip(flat.grads, max_norm, inv_scale, flat.norm_ws, total_norm, flat.grad_mult)
+    flat.clip_pending = True
+    return total_norm.reshape(())

@@ -22,7 +22,7 @@ import torch.distributed as dist
 from . import data as D
 from .amp import GradScaler, autocast
 from .nn import CrossEntropyLoss, ResNet18, SyncBatchNorm
-from .optim import SGD
+from .optim import SGD, Adam, AdamW, clip_grad_norm_
 from .parallel import DDP, DataParallel, barrier
 
 
@@ -50,6 +50,11 @@ def load_config(argv=None, mode: str = "ddp"):
     p.add_argument("--weight-decay", type=float, default=0.0001)
     p.add_argument("--lr-decay-step-size", type=int, default=60)
     p.add_argument("--lr-decay-gamma", type=float, default=0.1)
+    # not in the reference, whose README suggests the experiment ("e.g. using ADAM optimizer")
+    p.add_argument("--optimizer", type=str, default="sgd", choices=("sgd", "adam", "adamw"),
+                   help="fused flat-buffer optimizer; --lr and --weight-decay pass through")
+    p.add_argument("--clip-grad-norm", type=float, default=0.0,
+                   help="clip the global gradient L2 norm to this value before each step (0 = off)")
     # synthetic-data size knobs (not in the reference: CIFAR-100 cannot be downloaded here)
     p.add_argument("--synthetic-train", type=int, default=50000)
     p.add_argument("--synthetic-test", type=int, default=10000)
@@ -162,8 +167,13 @@ class Trainer:
             self._scalars.flush()
 
     def configure_optimizers(self):
-        optimizer = SGD(self.model.parameters(), lr=self.hparams.lr, weight_decay=self.hparams.weight_decay,
-                        momentum=0.9, nesterov=True)                                      # trainer.py:92-98
+        h = self.hparams
+        if h.optimizer == "sgd":
+            optimizer = SGD(self.model.parameters(), lr=h.lr, weight_decay=h.weight_decay,
+                            momentum=0.9, nesterov=True)                                  # trainer.py:92-98
+        else:
+            cls = {"adam": Adam, "adamw": AdamW}[h.optimizer]
+            optimizer = cls(self.model.parameters(), lr=h.lr, weight_decay=h.weight_decay)
         scheduler = torch.optim.lr_scheduler.StepLR(optimizer, step_size=self.hparams.lr_decay_step_size,
                                                     gamma=self.hparams.lr_decay_gamma)    # trainer.py:101-105
         return optimizer, scheduler
@@ -203,6 +213,9 @@ class Trainer:
                 if self.distributed:
                     barrier()  # dist.barrier() on the native communicator            # trainer.py:156
                 self.scaler.scale(loss).backward()
+                if self.hparams.clip_grad_norm > 0:  # torch's documented order: unscale_, clip, step
+                    self.scaler.unscale_(self.optimizer)
+                    clip_grad_norm_(self.model.parameters(), self.hparams.clip_grad_norm, scaler=self.scaler)
                 self.scaler.step(self.optimizer)
                 self.scaler.update()
             else:
@@ -211,6 +224,8 @@ class Trainer:
                 if self.distributed:
                     barrier()                                                             # trainer.py:163
                 loss.backward()
+                if self.hparams.clip_grad_norm > 0:
+                    clip_grad_norm_(self.model.parameters(), self.hparams.clip_grad_norm)
                 self.optimizer.step()
             train_loss.update(loss.item())
             self.global_step += 1

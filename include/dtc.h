@@ -202,6 +202,33 @@ int dtc_eval_metrics(const float* logits, const int64_t* labels, int n, int ncls
 int dtc_sgd_nesterov_flat(float* p, const float* g, float* momentum_buf, uint16_t* p_bf16, int64_t n, float lr,
                           float weight_decay, float momentum, const float* inv_scale, const int* found_inf,
                           void* stream);
+/* adam: torch.optim.Adam (decoupled = 0: g += weight_decay * p) / torch.optim.AdamW (decoupled = 1:
+ * p *= 1 - lr * weight_decay) with amsgrad = False, maximize = False -- the optimizer the reference's README
+ * suggests trying in configure_optimizers (trainer.py:91-107) -- over flat fp32 buffers p, g, exp_avg m,
+ * exp_avg_sq v (all 16-byte aligned, n % 4 == 0); p_bf16 (8-byte aligned) receives the bf16 shadow. As for sgd,
+ * grads are multiplied by *inv_scale (NULL: 1) and the whole step is skipped when *found_inf != 0 (NULL: never).
+ * `state` is dtc_adam_state_words() (= 4) 32-bit words of device memory, 16-byte aligned, zeroed by the caller
+ * before the first step and owned by the library's kernels afterwards: word 0 is the int32 count of steps
+ * taken. It advances on the device, and only on a step that is not skipped (torch's GradScaler does not
+ * advance state['step'] on a skipped step either), so the bias corrections 1 - beta^t need no host
+ * synchronisation. Two launches: a one-thread tick that advances the count and derives lr / (1 - beta1^t) and
+ * sqrt(1 - beta2^t) in double, then the update. The scalars are doubles because torch's are Python floats:
+ * 1 - beta2 formed from a float 0.999 is off by 4.7e-5. Requires eps > 0, betas in [0, 1), lr, weight_decay >= 0. */
+int dtc_adam_state_words(void);
+int dtc_adam_flat(float* p, const float* g, float* exp_avg, float* exp_avg_sq, uint16_t* p_bf16, int64_t n, void* state,
+                  double lr, double beta1, double beta2, double eps, double weight_decay, int decoupled,
+                  const float* inv_scale, const int* found_inf, void* stream);
+/* torch.nn.utils.clip_grad_norm_(norm_type = 2) over a flat gradient buffer (16-byte aligned, n % 4 == 0) that
+ * may still be loss-scaled: *total_norm = s * sqrt(sum g^2) and *grad_mult = s * min(1, max_norm / (*total_norm
+ * + 1e-6)) with s = *inv_scale (NULL: 1), both fp32 words in device memory. Passing grad_mult as the inv_scale
+ * of dtc_sgd_nesterov_flat / dtc_adam_flat applies unscale and clip inside the update: the gradients are not
+ * rewritten. Squares are summed in double in a fixed order (no floating-point atomics): bit-identical results run
+ * to run. Non-finite gradients give a non-finite norm (error_if_nonfinite = False); found_inf is not touched.
+ * workspace: dtc_grad_norm_workspace_bytes(n) bytes, 8-byte aligned, overwritten. Two launches (the read pass
+ * and a one-workgroup finalize), no host synchronisation. Requires max_norm > 0. */
+size_t dtc_grad_norm_workspace_bytes(int64_t n);
+int dtc_grad_norm_clip(const float* g, int64_t n, const float* inv_scale, double max_norm, void* workspace,
+                       float* total_norm, float* grad_mult, void* stream);
 int dtc_cast_f32_bf16(const float* src, uint16_t* dst, int64_t n, void* stream);
 int dtc_amp_check_finite(const float* g, int64_t n, int* found_inf, void* stream);
 /* GradScaler.scale(loss): out = x * (*scale) with the scale device-resident (no host sync) */
