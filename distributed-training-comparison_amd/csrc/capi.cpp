@@ -363,6 +363,65 @@ int dtc_bn_bwd_apply(const uint16_t* dz, const uint16_t* x1, const float* coef1,
   return bn_bwd_apply(dz, x1, coef1, dx1, x2, coef2, dx2, m, c, S(stream));
 }
 
+int dtc_bn_fin_apply(int mode, const uint16_t* x, const int64_t* stats, int64_t count, const float* gamma,
+                     const float* beta, float* running_mean, float* running_var, int64_t* nbt, float momentum,
+                     float eps, float* mean, float* invstd, const uint16_t* x2, const int64_t* stats2,
+                     const float* gamma2, const float* beta2, float* running_mean2, float* running_var2,
+                     int64_t* nbt2, float* mean2, float* invstd2, uint16_t* y, uint8_t* mask_bits, int64_t m, int c,
+                     void* stream) {
+  DTC_CHECK_ARG(mode >= 1 && mode <= 3, "dtc_bn_fin_apply: mode %d (1 relu, 2 add + relu, 3 dual + relu)", mode);
+  DTC_CHECK_ARG(x && stats && gamma && beta && mean && invstd && y, "dtc_bn_fin_apply: null argument");
+  DTC_CHECK_ARG(m > 0 && count > 0 && c > 0 && c % 64 == 0, "dtc_bn_fin_apply: bad shape (m=%lld count=%lld c=%d)",
+                (long long)m, (long long)count, c);
+  DTC_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr),
+                "dtc_bn_fin_apply: running_mean and running_var go together");
+  DTC_CHECK_ARG(mode == 1 || x2, "dtc_bn_fin_apply: mode %d needs x2", mode);
+  BnFwdArgs a1, a2;
+  a1.stats = stats; a1.count = count; a1.gamma = gamma; a1.beta = beta; a1.rmean = running_mean;
+  a1.rvar = running_var; a1.nbt = nbt; a1.momentum = momentum; a1.eps = eps; a1.mean = mean; a1.invstd = invstd;
+  if (mode == 3) {
+    DTC_CHECK_ARG(stats2 && gamma2 && beta2 && mean2 && invstd2, "dtc_bn_fin_apply: second BN arguments");
+    DTC_CHECK_ARG((running_mean2 == nullptr) == (running_var2 == nullptr),
+                  "dtc_bn_fin_apply: running_mean2 and running_var2 go together");
+    a2 = a1;
+    a2.stats = stats2; a2.gamma = gamma2; a2.beta = beta2; a2.rmean = running_mean2; a2.rvar = running_var2;
+    a2.nbt = nbt2; a2.mean = mean2; a2.invstd = invstd2;
+  }
+  GUARD(return bn_fin_apply(mode, x, a1, mode == 1 ? nullptr : x2, mode == 3 ? &a2 : nullptr, y, m, c, S(stream),
+                            mask_bits);)
+}
+
+int dtc_bn_bwd_mask(const uint16_t* dy, const uint8_t* mask_bits, uint16_t* dz_out, const uint16_t* x1,
+                    const float* gamma1, const float* mean1, const float* invstd1, float* dgamma1, float* dbeta1,
+                    uint16_t* dx1, const uint16_t* x2, const float* gamma2, const float* mean2, const float* invstd2,
+                    float* dgamma2, float* dbeta2, uint16_t* dx2, int64_t count, float gscale, int one_launch,
+                    int64_t* acc, size_t acc_words, int64_t m, int c, void* stream) {
+  DTC_CHECK_ARG(dy && mask_bits && x1 && gamma1 && mean1 && invstd1 && dx1, "dtc_bn_bwd_mask: null argument");
+  DTC_CHECK_ARG(m > 0 && count > 0 && c > 0 && c % 64 == 0 && c <= 2048,
+                "dtc_bn_bwd_mask: bad shape (m=%lld count=%lld c=%d)", (long long)m, (long long)count, c);
+  const bool dual = x2 != nullptr;
+  DTC_CHECK_ARG(!dual || (gamma2 && mean2 && invstd2 && dx2), "dtc_bn_bwd_mask: second BN arguments");
+  BnBwdArgs a1, a2;
+  a1.count = count; a1.gamma = gamma1; a1.mean = mean1; a1.invstd = invstd1; a1.gscale = gscale;
+  a1.dgamma = dgamma1; a1.dbeta = dbeta1;
+  a2 = a1;
+  a2.gamma = gamma2; a2.mean = mean2; a2.invstd = invstd2; a2.dgamma = dgamma2; a2.dbeta = dbeta2;
+  if (one_launch) {
+    DTC_CHECK_ARG(bn_bwd_cg_ok(m, c, dual), "dtc_bn_bwd_mask: m=%lld is past the one-launch limit (%s)", (long long)m,
+                  dual ? "2048 dual" : "4096");
+    GUARD(return bn_bwd_cg(dy, mask_bits, dz_out, x1, a1, dx1, x2, dual ? &a2 : nullptr, dx2, m, c, S(stream));)
+  }
+  const size_t words = DTC_STAT_WORDS(c);
+  DTC_CHECK_ARG(acc && acc_words >= (dual ? 2 : 1) * words,
+                "dtc_bn_bwd_mask: the two-pass form needs %zu zeroed accumulator words", (dual ? 2 : 1) * words);
+  a1.acc = acc;
+  a2.acc = acc + words;
+  GUARD(DTC_TRY(bn_bwd_reduce_mask(dy, mask_bits, x1, mean1, invstd1, acc, x2, mean2, invstd2,
+                                   dual ? acc + words : nullptr, m, c, S(stream)));
+        return bn_bwd_fin_apply_mask(dy, mask_bits, dz_out, x1, a1, dx1, x2, dual ? &a2 : nullptr, dx2, m, c,
+                                     S(stream));)
+}
+
 int dtc_stem_im2col(const float* x, uint16_t* cols, int n, int h, int w, void* stream) {
   return stem_im2col(x, cols, n, h, w, S(stream));
 }

@@ -250,6 +250,53 @@ def bn_bwd_apply(dz, x1, coef1, x2=None, coef2=None):
     return dx1, dx2
 
 
+def bn_fin_apply(mode, x, stats, count, gamma, beta, running_mean=None, running_var=None, nbt=None, x2=None, bn2=None,
+                 momentum=0.1, eps=1e-5, want_mask=True):
+    """The fused forward BN (dtc_bn_fin_apply): mode 1 relu(bn(x)), 2 relu(bn(x) + x2), 3 relu(bn(x) + bn2(x2)) with
+    bn2 = dict(stats=, gamma=, beta=, running_mean=, running_var=, nbt=) of the second BatchNorm. The running
+    statistics and nbt are updated in place. Returns (y, mask bits or None, (mean, invstd), (mean2, invstd2) or
+    None)."""
+    require_cuda(x, stats, gamma, beta, x2)
+    c = x.shape[-1]
+    m = x.numel() // c
+    dev = x.device
+    y = torch.empty_like(x)
+    mask = torch.empty(m * c // 8, dtype=torch.uint8, device=dev) if want_mask else None
+    mean, invstd = (torch.empty(c, dtype=torch.float32, device=dev) for _ in range(2))
+    b2 = bn2 or {}
+    mean2, invstd2 = (torch.empty(c, dtype=torch.float32, device=dev) if bn2 else None for _ in range(2))
+    call("dtc_bn_fin_apply", int(mode), ptr(x), ptr(stats), int(count), ptr(gamma), ptr(beta), ptr(running_mean),
+         ptr(running_var), ptr(nbt), float(momentum), float(eps), ptr(mean), ptr(invstd), ptr(x2), ptr(b2.get("stats")),
+         ptr(b2.get("gamma")), ptr(b2.get("beta")), ptr(b2.get("running_mean")), ptr(b2.get("running_var")),
+         ptr(b2.get("nbt")), ptr(mean2), ptr(invstd2), ptr(y), ptr(mask), m, c, stream_ptr())
+    return y, mask, (mean, invstd), ((mean2, invstd2) if bn2 else None)
+
+
+def bn_bwd_mask(dy, mask_bits, x1, gamma1, mean1, invstd1, x2=None, gamma2=None, mean2=None, invstd2=None, count=None,
+                gscale=1.0, one_launch=False, dz_out=None, acc=None):
+    """The mask-bit BN backward (dtc_bn_bwd_mask), two launches through the accumulator `acc` (a zeroed one is
+    made when None) or one (`one_launch`). dz_out: None, or a tensor to receive dz = dy * bit (may be dy itself).
+    Returns dict(dx1, dgamma1, dbeta1, acc [, dx2, dgamma2, dbeta2])."""
+    require_cuda(dy, mask_bits, x1, gamma1, mean1, invstd1, x2, dz_out)
+    c = x1.shape[-1]
+    m = x1.numel() // c
+    dev = x1.device
+    dual = x2 is not None
+    out = {"dx1": torch.empty_like(x1)}
+    for k in ("dgamma1", "dbeta1") + (("dgamma2", "dbeta2") if dual else ()):
+        out[k] = torch.empty(c, dtype=torch.float32, device=dev)
+    if dual:
+        out["dx2"] = torch.empty_like(x2)
+    if acc is None and not one_launch:
+        acc = torch.zeros((2 if dual else 1) * int(lib.dtc_bn_stat_words(c)), dtype=torch.int64, device=dev)
+    out["acc"] = acc
+    call("dtc_bn_bwd_mask", ptr(dy), ptr(mask_bits), ptr(dz_out), ptr(x1), ptr(gamma1), ptr(mean1), ptr(invstd1),
+         ptr(out["dgamma1"]), ptr(out["dbeta1"]), ptr(out["dx1"]), ptr(x2), ptr(gamma2), ptr(mean2), ptr(invstd2),
+         ptr(out.get("dgamma2")), ptr(out.get("dbeta2")), ptr(out.get("dx2")), int(m if count is None else count),
+         float(gscale), int(bool(one_launch)), ptr(acc), 0 if acc is None else acc.numel(), m, c, stream_ptr())
+    return out
+
+
 def bn_mask_bits(y):
     """ReLU mask bits of a post-ReLU NHWC tensor as the forward BN apply writes them: one byte per 8
     channels, bit k = channel 8j+k > 0."""

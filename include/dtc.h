@@ -145,6 +145,31 @@ int dtc_bn_bwd_finalize(int64_t* acc, int c, int64_t count, const float* gamma, 
                         const float* invstd, float gscale, float* dgamma, float* dbeta, float* coef, void* stream);
 int dtc_bn_bwd_apply(const uint16_t* dz, const uint16_t* x1, const float* coef1, uint16_t* dx1, const uint16_t* x2,
                      const float* coef2, uint16_t* dx2, int64_t m, int c, void* stream);
+/* The executor's default forward BN (finalize folded into the apply, one launch): every workgroup folds the
+ * statistic slots of its 64 channels (stats: sum x, sum x^2 over `count` elements per channel; read, not
+ * re-zeroed) into scale / shift and writes y = relu(bn(x)) (mode 1), relu(bf16(bn(x)) + x2) (mode 2) or
+ * relu(bf16(bn(x)) + bf16(bn2(x2))) (mode 3: the projection shortcut's BN, the *2 arguments; NULL otherwise).
+ * Side outputs, written once per channel: mean / invstd (saved for the backward), the running statistics
+ * (optional; momentum, unbiased variance) and *nbt += 1 (optional). mask_bits (optional, m * c / 8 bytes):
+ * the ReLU mask of y, bit k of byte o / 8 = [y[o + k] > 0] for element offset o. c % 64 == 0. */
+int dtc_bn_fin_apply(int mode, const uint16_t* x, const int64_t* stats, int64_t count, const float* gamma,
+                     const float* beta, float* running_mean, float* running_var, int64_t* nbt, float momentum,
+                     float eps, float* mean, float* invstd, const uint16_t* x2, const int64_t* stats2,
+                     const float* gamma2, const float* beta2, float* running_mean2, float* running_var2,
+                     int64_t* nbt2, float* mean2, float* invstd2, uint16_t* y, uint8_t* mask_bits, int64_t m, int c,
+                     void* stream);
+/* The executor's default BN backward, driven by the forward's mask bits: dz = dy * bit (stored to dz_out if
+ * non-NULL; dz_out may alias dy), dgamma = gscale * sum dz*xhat, dbeta = gscale * sum dz (both optional) and
+ * dx = gamma*invstd * (dz - sum dz / count - xhat * sum dz*xhat / count), for one BN (x2 == NULL) or for
+ * the two BNs that share dz in a projection block (x2 ... dx2). one_launch == 0: a reduction into `acc`
+ * ((1 or 2) * dtc_bn_stat_words(c) int64 words, zeroed by the caller; they hold the sums afterwards) and an
+ * apply that folds them; one_launch != 0: one launch, one workgroup per 8 channels, acc unused -- only for
+ * m <= 4096 (2048 with a second BN), DTC_EINVAL beyond. c % 64 == 0, c <= 2048. */
+int dtc_bn_bwd_mask(const uint16_t* dy, const uint8_t* mask_bits, uint16_t* dz_out, const uint16_t* x1,
+                    const float* gamma1, const float* mean1, const float* invstd1, float* dgamma1, float* dbeta1,
+                    uint16_t* dx1, const uint16_t* x2, const float* gamma2, const float* mean2, const float* invstd2,
+                    float* dgamma2, float* dbeta2, uint16_t* dx2, int64_t count, float gscale, int one_launch,
+                    int64_t* acc, size_t acc_words, int64_t m, int c, void* stream);
 
 /* ------------------------------------------------------------------ stem, head, loss
  * stem: self.conv1 = nn.Conv2d(3, 64, 3, 1, 1) (net.py:91) as im2col [n*h*w][64] + GEMM.

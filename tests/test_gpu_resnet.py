@@ -79,7 +79,33 @@ def _bn_bwd(dz, x, g, rnd=O.bf16):
     return rnd(dx.reshape(x.shape)), dg, db
 
 
-def _teacher_forced(dtc, cuda, batch, hw=32, stages=(0, 1, 2, 3, 4), imgs=None, seed=0, precision="bf16"):
+def _bn_prefixes(sd):
+    return [k[:-len(".running_mean")] for k in sd if k.endswith(".running_mean")]
+
+
+def _bn_state_draw(sd, seed):
+    """A copy of the state dict `sd` (numpy) with every BatchNorm moved off its initial state by a seeded draw:
+    gamma uniform in [0.5, 1.5] with one channel negated and another set to exactly 0, beta uniform in
+    [-0.5, 0.5], running_mean normal x 0.1, running_var uniform in [0.5, 2.0], num_batches_tracked = 1 + the
+    BN's index (small, positive, different in every BN)."""
+    g = np.random.default_rng(seed)
+    out = dict(sd)
+    for i, pre in enumerate(_bn_prefixes(sd)):
+        C = sd[pre + ".weight"].shape[0]
+        gamma = g.uniform(0.5, 1.5, C).astype(np.float32)
+        neg, zero = g.choice(C, 2, replace=False)
+        gamma[neg] = -gamma[neg]
+        gamma[zero] = 0.0
+        out[pre + ".weight"] = gamma
+        out[pre + ".bias"] = g.uniform(-0.5, 0.5, C).astype(np.float32)
+        out[pre + ".running_mean"] = (g.standard_normal(C) * 0.1).astype(np.float32)
+        out[pre + ".running_var"] = g.uniform(0.5, 2.0, C).astype(np.float32)
+        out[pre + ".num_batches_tracked"] = np.asarray(1 + i, np.int64)
+    return out
+
+
+def _teacher_forced(dtc, cuda, batch, hw=32, stages=(0, 1, 2, 3, 4), imgs=None, seed=0, precision="bf16",
+                    bn_state_seed=None, sync_comm=None, eval_after=False):
     """Run one capture-enabled training forward/backward of the executor at (batch, hw x hw) and
     check every layer of the listed stages (0 = stem + head, 1..4 = layer1..4) against the oracle
     evaluated on THAT layer's executor inputs. `imgs` (index array) restricts the per-image ops
@@ -88,9 +114,27 @@ def _teacher_forced(dtc, cuda, batch, hw=32, stages=(0, 1, 2, 3, 4), imgs=None, 
     kernel plan (split-K factors, wgrad splits, persistent-tile walks) is the one under test.
     precision "bf16": the AMP executor at the north_star's 1e-2 (bf16 outputs; fp32 weight gradients
     from identical bf16 operands 1e-4); "fp32": the non-AMP executor at the north_star's 1e-5
-    everywhere, against the fp32 (unrounded) oracle."""
+    everywhere, against the fp32 (unrounded) oracle.
+    `bn_state_seed` (default None: the freshly initialised network, exactly as before): every BatchNorm's
+    gamma, beta, running statistics and num_batches_tracked are first drawn by _bn_state_draw and loaded through
+    load_state_dict, the oracle takes its parameters and buffers from the model's state after that, and on top
+    of the usual checks: every BN's bias gradient (1e-3), every BN's running_mean / running_var after the one
+    training forward against O.bn_train_fwd on that BN's own executor input started from the drawn values
+    (per channel, test_bn_forward's tolerances: rtol 1e-5, atol 1e-6 for the mean), every num_batches_tracked
+    = drawn + 1, and no vacuous comparison (every reference has a non-zero norm; no relu1 / out activation is
+    all zero). `sync_comm`: run as SyncBatchNorm over that communicator. `eval_after`: then an eval-mode
+    forward of the same model against the oracle's eval forward on the post-training buffers (3e-2), which
+    must leave the buffers bit-unchanged."""
     model, sd, x, y = _setup(dtc, cuda, batch, seed=seed, capture=True, hw=hw)
     model.precision = precision
+    perturbed = bn_state_seed is not None
+    if perturbed:
+        drawn = _bn_state_draw(sd, bn_state_seed)
+        model.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in drawn.items()})
+        sd = {k: v.detach().cpu().numpy().copy() for k, v in model.state_dict().items()}
+    if sync_comm is not None:
+        model = dtc.SyncBatchNorm.convert_sync_batchnorm(model)
+        model.set_sync_bn(sync_comm)
     bf = precision == "bf16"
     rnd = O.bf16 if bf else _f32
     crit = dtc.CrossEntropyLoss()
@@ -105,12 +149,24 @@ def _teacher_forced(dtc, cuda, batch, hw=32, stages=(0, 1, 2, 3, 4), imgs=None, 
     P = {k: v for k, v in _split_state(sd)[0].items()}
     W = {k: rnd(O.kcrs_to_krsc(v)) for k, v in P.items() if v.ndim == 4}
     grads = {k: _np(p.grad) for k, p in model.named_parameters()}
+    if perturbed or eval_after:
+        sd_after = {k: v.detach().cpu().numpy().copy() for k, v in model.state_dict().items()}
+    if eval_after:
+        model.eval()
+        with torch.no_grad():
+            logits_eval = _np(model(xd))
+        torch.cuda.synchronize()
+        sd_eval = {k: v.detach().cpu().numpy().copy() for k, v in model.state_dict().items()}
+    if sync_comm is not None:
+        model.set_sync_bn(None)
     del model, exe
     torch.cuda.empty_cache()
     sel = slice(None) if imgs is None else np.asarray(imgs)
     errs = {}
 
     def chk(name, got, ref, tol=BF):
+        if perturbed:
+            assert np.linalg.norm(np.asarray(ref, np.float64).ravel()) > 0, f"vacuous check: {name} has a zero reference"
         errs[name] = (rel_err(got, ref), tol if bf else 1e-5)  # fp32 mode: 1e-5 for everything
 
     def conv_f(inp, w, st, pad):
@@ -177,6 +233,8 @@ def _teacher_forced(dtc, cuda, batch, hw=32, stages=(0, 1, 2, 3, 4), imgs=None, 
         dc1, dg1, db1 = _bn_bwd(G[gp + ".dz1"], A[pre + ".conv1"], P[pre + ".bn1.weight"], rnd)
         chk(gp + ".dc1", G[gp + ".dc1"], dc1)
         chk(pre + ".bn1.weight.grad", grads[pre + ".bn1.weight"], dg1, 1e-3)
+        if perturbed:
+            chk(pre + ".bn1.bias.grad", grads[pre + ".bn1.bias"], db1, 1e-3)
         chk(pre + ".conv1.weight.grad", O.kcrs_to_krsc(grads[pre + ".conv1.weight"]),
             O.conv2d_wgrad(inp, G[gp + ".dc1"], 3, 3, st, 1), F32)
         dx = conv_d(G[gp + ".dc1"], W[pre + ".conv1.weight"], inp.shape[1:3], st, 1)
@@ -184,6 +242,8 @@ def _teacher_forced(dtc, cuda, batch, hw=32, stages=(0, 1, 2, 3, 4), imgs=None, 
             ds, dgs, dbs = _bn_bwd(G[gp + ".dz"], A[pre + ".shortcut"], P[pre + ".shortcut.1.weight"], rnd)
             chk(gp + ".ds", G[gp + ".ds"], ds)
             chk(pre + ".shortcut.1.weight.grad", grads[pre + ".shortcut.1.weight"], dgs, 1e-3)
+            if perturbed:
+                chk(pre + ".shortcut.1.bias.grad", grads[pre + ".shortcut.1.bias"], dbs, 1e-3)
             chk(pre + ".shortcut.0.weight.grad", O.kcrs_to_krsc(grads[pre + ".shortcut.0.weight"]),
                 O.conv2d_wgrad(inp, G[gp + ".ds"], 1, 1, st, 0), F32)
             chk(gp + ".dxs", G[gp + ".dxs"][sel], conv_d(G[gp + ".ds"], W[pre + ".shortcut.0.weight"],
@@ -196,6 +256,8 @@ def _teacher_forced(dtc, cuda, batch, hw=32, stages=(0, 1, 2, 3, 4), imgs=None, 
         dc0, dg0, db0 = _bn_bwd(G["grad.stem.dz"], A["stem.conv"], P["bn1.weight"], rnd)
         chk("grad.stem.dc", G["grad.stem.dc"], dc0)
         chk("bn1.weight.grad", grads["bn1.weight"], dg0, 1e-3)
+        if perturbed:
+            chk("bn1.bias.grad", grads["bn1.bias"], db0, 1e-3)
         chk("conv1.weight.grad", O.kcrs_to_krsc(grads["conv1.weight"]),
             O.conv2d_wgrad(xb, G["grad.stem.dc"], 3, 3, 1, 1), F32)
     bad = {k: v for k, v in errs.items() if v[0] > v[1]}
@@ -203,7 +265,54 @@ def _teacher_forced(dtc, cuda, batch, hw=32, stages=(0, 1, 2, 3, 4), imgs=None, 
     print(f"teacher-forced {precision} B={batch} {hw}x{hw} stages={stages}: {len(errs)} checks, worst {worst[0]} "
           f"{worst[1][0]:.2e} (tol {worst[1][1]:.0e})")
     assert not bad, f"per-layer parity failures: {bad}"
+    if perturbed:
+        _check_bn_state_after(sd, sd_after, A, stages)
+    if eval_after:
+        params, bufs = _split_state(sd_after)
+        ref = R.forward_backward(params, bufs, x, y, bf16_mode=bf, train=False)
+        e = rel_err(logits_eval, ref["logits"])
+        print(f"eval after the training forward: logits rel err {e:.2e}")
+        assert np.linalg.norm(ref["logits"]) > 0 and e < 3e-2, e
+        for k, v in sd_after.items():
+            if k in bufs or k.endswith("num_batches_tracked"):  # eval touches no buffer
+                np.testing.assert_array_equal(sd_eval[k], v, err_msg=k)
     return errs
+
+
+def _check_bn_state_after(sd, sd_after, A, stages):
+    """Buffers of every BatchNorm of the listed stages after ONE training forward from the state `sd`, per
+    channel: running statistics = O.bn_train_fwd on the BN's own executor input (A: the executor's
+    activations) started from sd's values, momentum 0.1, at test_bn_forward's tolerances (the sums are exact
+    fixed point and the finalize is one fp32 rounding); num_batches_tracked = sd's + 1; and no relu1 / out
+    activation all zero (a dead draw would make the mask and gradient checks vacuous). Measured on MI355X
+    over tests/test_gpu_bn_affine.py's cases (bf16 and fp32, M from 5 to 8192): running_var within 9.4e-8
+    relative, running_mean within 3.1e-9 absolute beyond rtol * |ref| -- no BN needs more than the tolerances."""
+    worst = {"running_mean": -1.0, "running_var": 0.0}
+    got = []
+    for pre in _bn_prefixes(sd):
+        stage = int(pre[5]) if pre.startswith("layer") else 0
+        if stage not in stages:
+            continue
+        conv = "stem.conv" if pre == "bn1" else pre[:-len(".shortcut.1")] + ".shortcut" if pre.endswith(".shortcut.1") \
+            else pre[:-len(".bnN")] + ".conv" + pre[-1]
+        xin = A[conv]
+        C = xin.shape[-1]
+        _, _, _, rm, rv = O.bn_train_fwd(xin.reshape(-1, C), sd[pre + ".weight"], sd[pre + ".bias"],
+                                         sd[pre + ".running_mean"].astype(np.float64),
+                                         sd[pre + ".running_var"].astype(np.float64), momentum=0.1)
+        got.append((pre, sd_after[pre + ".running_mean"], rm, sd_after[pre + ".running_var"], rv))
+        worst["running_mean"] = max(worst["running_mean"], float(np.max(np.abs(got[-1][1] - rm) - 1e-5 * np.abs(rm))))
+        worst["running_var"] = max(worst["running_var"], float(np.max(np.abs(got[-1][3] / rv - 1))))
+    print(f"BN state after one forward: worst running_mean |err| - rtol*|ref| {worst['running_mean']:.2e} (atol 1e-6), "
+          f"worst running_var rel err {worst['running_var']:.2e} (rtol 1e-5)")
+    assert got
+    for pre, got_m, rm, got_v, rv in got:
+        np.testing.assert_allclose(got_m, rm, rtol=1e-5, atol=1e-6, err_msg=pre + ".running_mean")
+        np.testing.assert_allclose(got_v, rv, rtol=1e-5, err_msg=pre + ".running_var")
+        assert int(sd_after[pre + ".num_batches_tracked"]) == int(sd[pre + ".num_batches_tracked"]) + 1, pre
+    for k, v in A.items():
+        if k.endswith(".relu1") or k.endswith(".out"):
+            assert np.any(v > 0), f"dead draw: activation {k} is all zero"
 
 
 @pytest.mark.parametrize("batch", [2, 8])

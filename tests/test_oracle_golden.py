@@ -269,3 +269,46 @@ def test_device_loader_rows_follow_subset_and_sampler(dtc):
     assert len(ld) == 23 // 8
     ld2 = dtc.data.DeviceLoader(imgs, tg, 8, subset_idx=sub, train=False, drop_last=False, device="cpu")
     assert len(ld2) == 12 and np.array_equal(ld2._rows(), sub)
+
+
+@pytest.mark.parametrize("M", [2, 300])
+def test_oracle_bn_matches_torch_float64_with_affine_and_running_stats(M):
+    """oracle.ops.bn_train_fwd / bn_train_bwd against torch.nn.functional.batch_norm in float64 with autograd,
+    away from the initial state the goldens were taken at: random gamma with one negative and one zero
+    channel, random beta, running statistics that start at non-trivial values (momentum 0.1, unbiased
+    variance M / (M - 1)). Both sides are float64: 1e-10."""
+    import torch.nn.functional as F
+
+    C = 16
+    g = np.random.default_rng(40 + M)
+    x = g.standard_normal((M, C)) * 1.7 + 0.3
+    gamma = g.uniform(0.5, 1.5, C)
+    gamma[3], gamma[7] = -gamma[3], 0.0
+    beta = g.uniform(-0.5, 0.5, C)
+    rm0 = g.standard_normal(C) * 0.1
+    rv0 = g.uniform(0.5, 2.0, C)
+    dy = g.standard_normal((M, C))
+
+    y, mean, invstd, rm, rv = O.bn_train_fwd(x, gamma, beta, rm0, rv0, eps=1e-5, momentum=0.1)
+    dx, dgamma, dbeta = O.bn_train_bwd(dy, x, gamma, mean, invstd)
+
+    xt = torch.tensor(x, dtype=torch.float64, requires_grad=True)
+    gt = torch.tensor(gamma, dtype=torch.float64, requires_grad=True)
+    bt = torch.tensor(beta, dtype=torch.float64, requires_grad=True)
+    rmt, rvt = torch.tensor(rm0, dtype=torch.float64), torch.tensor(rv0, dtype=torch.float64)
+    yt = F.batch_norm(xt, rmt, rvt, gt, bt, training=True, momentum=0.1, eps=1e-5)
+    yt.backward(torch.tensor(dy, dtype=torch.float64))
+    mt = xt.detach().mean(0)
+    ist = 1.0 / torch.sqrt(xt.detach().var(0, unbiased=False) + 1e-5)
+
+    tol = dict(rtol=1e-10, atol=1e-10)
+    np.testing.assert_allclose(y, yt.detach().numpy(), **tol)
+    np.testing.assert_allclose(mean, mt.numpy(), **tol)
+    np.testing.assert_allclose(invstd, ist.numpy(), **tol)
+    np.testing.assert_allclose(rm, rmt.numpy(), **tol)  # F.batch_norm updated the buffers in place
+    np.testing.assert_allclose(rv, rvt.numpy(), **tol)
+    assert np.abs(rm - rm0).max() > 1e-3 and np.abs(rv - rv0).max() > 1e-3
+    np.testing.assert_allclose(dx, xt.grad.numpy(), **tol)
+    np.testing.assert_allclose(dgamma, gt.grad.numpy(), **tol)
+    np.testing.assert_allclose(dbeta, bt.grad.numpy(), **tol)
+    assert np.all(dx[:, 7] == 0.0) and np.abs(dgamma[7]) > 0  # gamma = 0: no input gradient, dgamma alive
