@@ -14,7 +14,8 @@ from . import _native  # noqa: F401  (loads libdtc_amd.so; raises if it is missi
 from ._native import NativeError  # noqa: F401
 from . import data, ops  # noqa: F401
 from .amp import GradScaler, autocast  # noqa: F401
-from .nn import BasicBlock, CrossEntropyLoss, EvalResult, ResNet, ResNet18, SyncBatchNorm  # noqa: F401
+from .nn import (BasicBlock, CrossEntropyLoss, EvalResult, MixedTarget, ResNet, ResNet18,  # noqa: F401
+                 SyncBatchNorm)
 from . import optim  # noqa: F401
 from .optim import SGD, Adam, AdamW, clip_grad_norm_  # noqa: F401
 from .parallel import DDP, Comm, DataParallel, DistributedDataParallel, barrier  # noqa: F401

@@ -97,6 +97,9 @@ _SIGS = {
     "dtc_xent_fwd": (i32, [vp, vp, i32, i32, vp, vp, vp]),
     "dtc_xent_fwd_ex": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]),
     "dtc_xent_bwd": (i32, [vp, vp, vp, vp, i32, i32, vp, vp]),
+    "dtc_xent_soft_fwd_ex": (i32, [vp, vp, vp, vp, f32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    "dtc_xent_soft_fwd": (i32, [vp, vp, vp, vp, f32, i32, i32, vp, vp, vp]),
+    "dtc_xent_soft_bwd": (i32, [vp, vp, vp, vp, f32, vp, vp, i32, i32, vp, vp]),
     "dtc_eval_metrics": (i32, [vp, vp, i32, i32, i32, vp, vp]),
     "dtc_sgd_nesterov_flat": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, vp, vp, vp]),
     "dtc_adam_state_words": (i32, []),
@@ -109,6 +112,8 @@ _SIGS = {
     "dtc_amp_update_scale": (i32, [vp, vp, vp, vp, f32, f32, i32, vp]),
     "dtc_cifar_augment": (i32, [vp, vp, i64, vp, vp, vp, i32, i32, i32, i32, C.POINTER(f32), C.POINTER(f32), vp, vp,
                                 vp, vp]),
+    "dtc_cifar_augment_mix": (i32, [vp, vp, i64, vp, vp, vp, i32, i32, i32, i32, C.POINTER(f32), C.POINTER(f32), vp,
+                                    i32, vp, vp, vp, vp, vp, vp, vp]),
     "dtc_comm_unique_id_bytes": (sz, []),
     "dtc_comm_get_unique_id": (i32, [vp]),
     "dtc_comm_init": (i32, [C.POINTER(vp), i32, i32, vp, i32]),
@@ -159,6 +164,7 @@ _SIGS = {
     "dtc_rn18_forward": (i32, [vp, vp, vp, i32, vp]),
     "dtc_rn18_backward": (i32, [vp, vp, f32, vp, vp]),
     "dtc_rn18_xent_backward": (i32, [vp, vp, vp, vp, vp, f32, vp, vp]),
+    "dtc_rn18_xent_soft_backward": (i32, [vp, vp, vp, vp, vp, f32, vp, vp, f32, vp, vp]),
     "dtc_rn18_eval_batch": (i32, [vp, vp, vp, i32, i32, vp, vp, vp]),
     "dtc_rn18_set_sync_bn": (i32, [vp, vp]),
     "dtc_rn18_dlogits_buffer": (i32, [vp, C.POINTER(sz)]),

@@ -455,6 +455,21 @@ int dtc_xent_fwd_ex(const float* logits, const int64_t* labels, int n, int ncls,
                     const float* scale, float* scaled, float* host_loss, void* stream) {
   GUARD(return xent_fwd_fused(logits, labels, n, ncls, loss, lse, scale, scaled, host_loss, S(stream));)
 }
+int dtc_xent_soft_fwd_ex(const float* logits, const int64_t* labels_a, const int64_t* labels_b, const float* lam,
+                         float smoothing, int n, int ncls, float* loss, float* lse, const float* scale, float* scaled,
+                         float* host_loss, void* stream) {
+  GUARD(return xent_soft_fwd_fused(logits, labels_a, labels_b, lam, smoothing, n, ncls, loss, lse, scale, scaled,
+                                   host_loss, S(stream));)
+}
+int dtc_xent_soft_fwd(const float* logits, const int64_t* labels_a, const int64_t* labels_b, const float* lam,
+                      float smoothing, int n, int ncls, float* loss, float* lse, void* stream) {
+  GUARD(return xent_soft_fwd(logits, labels_a, labels_b, lam, smoothing, n, ncls, loss, lse, S(stream));)
+}
+int dtc_xent_soft_bwd(const float* logits, const int64_t* labels_a, const int64_t* labels_b, const float* lam,
+                      float smoothing, const float* lse, const float* gscale, int n, int ncls, float* dlogits,
+                      void* stream) {
+  GUARD(return xent_soft_bwd(logits, labels_a, labels_b, lam, smoothing, lse, gscale, n, ncls, dlogits, S(stream));)
+}
 int dtc_eval_metrics(const float* logits, const int64_t* labels, int n, int ncls, int topk, dtc_eval_record* rec,
                      void* stream) {
   GUARD(return eval_metrics(logits, labels, n, ncls, topk, rec, S(stream));)
@@ -498,6 +513,14 @@ int dtc_cifar_augment(const uint8_t* images, const int64_t* targets, int64_t n_i
                       const float* stdv, float* out, int64_t* labels, int* status, void* stream) {
   return cifar_augment(images, targets, n_images, index, crop, flip, n, h, w, pad, mean, stdv, out, labels, status,
                        S(stream));
+}
+
+int dtc_cifar_augment_mix(const uint8_t* images, const int64_t* targets, int64_t n_images, const int64_t* index,
+                          const uint8_t* crop, const uint8_t* flip, int n, int h, int w, int pad, const float* mean,
+                          const float* stdv, const int32_t* partner, int mode, const float* lam, const uint8_t* box,
+                          float* out, int64_t* labels, int64_t* labels_b, int* status, void* stream) {
+  GUARD(return cifar_augment_mix(images, targets, n_images, index, crop, flip, n, h, w, pad, mean, stdv, partner, mode,
+                                 lam, box, out, labels, labels_b, status, S(stream));)
 }
 
 size_t dtc_comm_unique_id_bytes(void) { return comm_unique_id_bytes(); }

@@ -7,6 +7,7 @@
 //       The pool is global over the last feature map (identical to avg_pool2d(4) at 32x32
 //       inputs; at 224x224 this is the documented global-pool deviation, SURVEY §7 viii).
 //   xent_fwd / xent_bwd : `nn.CrossEntropyLoss()` mean reduction (reference trainer.py:40,155).
+//   xent_soft_* : the same loss against a soft target (label smoothing, Mixup, CutMix; not in the reference).
 #include <type_traits>
 
 #include "common.h"
@@ -352,6 +353,131 @@ int xent_fwd_fused(const float* logits, const int64_t* labels, int N, int ncls, 
   return 0;
 }
 
+// Soft targets (label smoothing, Mixup, CutMix): the target of row b is the distribution
+//   q = (1 - eps) * (lam * onehot(ya) + (1 - lam) * onehot(yb)) + eps / ncls
+// and its loss term lse - sum_j q[j] z[j] = lse - t with
+//   t = (1 - eps) * (lam * z[ya] + (1 - lam) * z[yb]) + (eps / ncls) * sum_j z[j].
+// With eps = 0, lam = 1, yb = ya and finite logits t is z[ya] exactly -- 1 * za + 0 * za = za and
+// 1 * za + 0 = za whether or not the compiler contracts the products into FMAs (an FMA with an exact
+// product rounds once, to the same value) -- so the term is xent_fwd_fused_kernel's l - z[ya] bit for bit.
+// The uniform part is not formed at all at eps = 0: a row sum that overflowed would turn 0 * inf into NaN.
+// ok: both labels in range; a lam outside [0, 1] (or NaN) makes the term NaN like a bad label does.
+__device__ __forceinline__ float xent_soft_term(float l, float za, float zb, float lam, float eps, float sumz,
+                                                int ncls, bool ok) {
+  const float mix = lam * za + (1.f - lam) * zb;
+  const float t = (1.f - eps) * mix + (eps > 0.f ? (eps / (float)ncls) * sumz : 0.f);
+  return (ok && lam >= 0.f && lam <= 1.f) ? l - t : NAN;
+}
+
+// xent_fwd_fused_kernel for soft targets: the same launch shape, the same lse (same folds, same tree: bit-
+// identical), the same mean order, scaled loss and host word; per row one more fold -- the sum of z through
+// the per-lane order and row16_sum tree of the LSE's sum, on values already loaded -- and a second label
+// gather. lb == la and lam == nullptr: label smoothing only.
+__global__ void __launch_bounds__(1024) xent_soft_fwd_fused_kernel(
+    const float* __restrict__ logits, const int64_t* __restrict__ la, const int64_t* __restrict__ lb,
+    const float* __restrict__ lam, float eps, int N, int ncls, float* __restrict__ loss, float* __restrict__ lse,
+    const float* __restrict__ scale, float* __restrict__ scaled, float* host) {
+  __shared__ float sterm[XF_MAX_ROWS];
+  __shared__ float part[4];
+  const int t = threadIdx.x, li = t & 15, lane = t & 63;
+  if (ncls <= 128) {
+    constexpr int RR = 4, KV = 8;
+    for (int b0 = t >> 4; b0 < N; b0 += 64 * RR) {
+      float v[RR][KV], lm[RR];
+      int64_t ya[RR], yb[RR];
+#pragma unroll
+      for (int r = 0; r < RR; ++r) {
+        const int b = b0 + 64 * r, bb = b < N ? b : 0;
+        const float* z = logits + (int64_t)bb * ncls;
+#pragma unroll
+        for (int k = 0; k < KV; ++k) v[r][k] = li + 16 * k < ncls ? z[li + 16 * k] : 0.f;
+        ya[r] = la[bb];
+        yb[r] = lb[bb];
+        lm[r] = lam ? lam[bb] : 1.f;
+      }
+#pragma unroll
+      for (int r = 0; r < RR; ++r) {
+        const int b = b0 + 64 * r;
+        float m = -INFINITY;
+#pragma unroll
+        for (int k = 0; k < KV; ++k)
+          if (li + 16 * k < ncls) m = fmaxf(m, v[r][k]);
+        m = row16_max(m);
+        float sum = 0.f, sz = 0.f;
+#pragma unroll
+        for (int k = 0; k < KV; ++k)
+          if (li + 16 * k < ncls) sum += expf(v[r][k] - m);
+        sum = row16_sum(sum);
+#pragma unroll
+        for (int k = 0; k < KV; ++k)
+          if (li + 16 * k < ncls) sz += v[r][k];
+        sz = row16_sum(sz);
+        const float l = m + logf(sum);
+        const bool ok = ya[r] >= 0 && ya[r] < ncls && yb[r] >= 0 && yb[r] < ncls;
+        const int al = ok ? (int)ya[r] : 0, bl = ok ? (int)yb[r] : 0;
+        float ca = 0.f, cb = 0.f;
+#pragma unroll
+        for (int k = 0; k < KV; ++k) {
+          ca = (al >> 4) == k ? v[r][k] : ca;
+          cb = (bl >> 4) == k ? v[r][k] : cb;
+        }
+        const float za = __shfl(ca, (lane & ~15) | (al & 15));
+        const float zb = __shfl(cb, (lane & ~15) | (bl & 15));
+        if (li == 0 && b < N) {
+          lse[b] = l;
+          sterm[b] = xent_soft_term(l, za, zb, lm[r], eps, sz, ncls, ok);
+        }
+      }
+    }
+  } else {
+    for (int b = t >> 4; b < N; b += 64) {
+      const float* z = logits + (int64_t)b * ncls;
+      const float v = row_lse16(z, ncls, li);
+      float sz = 0.f;
+#pragma unroll 8
+      for (int j = li; j < ncls; j += 16) sz += z[j];
+      sz = row16_sum(sz);
+      if (li == 0) {
+        lse[b] = v;
+        const int64_t ya = la[b], yb = lb[b];
+        const bool ok = ya >= 0 && ya < ncls && yb >= 0 && yb < ncls;
+        sterm[b] = xent_soft_term(v, ok ? z[ya] : 0.f, ok ? z[yb] : 0.f, lam ? lam[b] : 1.f, eps, sz, ncls, ok);
+      }
+    }
+  }
+  __syncthreads();
+  if (t < 256) {  // the mean exactly as xent_mean_kernel sums it
+    float acc = 0.f;
+    for (int b = t; b < N; b += 256) acc += sterm[b];
+    acc = wave_sum(acc);
+    if ((t & 63) == 0) part[t >> 6] = acc;
+  }
+  __syncthreads();
+  if (t == 0) {
+    const float l = (part[0] + part[1] + part[2] + part[3]) / (float)N;
+    *loss = l;
+    if (scaled) *scaled = l * *scale;
+    if (host) *host = l;
+  }
+}
+
+static bool soft_args_ok(const int64_t* labels_b, const float* lam, float smoothing) {
+  return (labels_b != nullptr) == (lam != nullptr) && smoothing >= 0.f && smoothing <= 1.f;  // (NaN fails)
+}
+
+int xent_soft_fwd_fused(const float* logits, const int64_t* labels_a, const int64_t* labels_b, const float* lam,
+                        float smoothing, int N, int ncls, float* loss, float* lse, const float* scale, float* scaled,
+                        float* host, hipStream_t st) {
+  DTC_CHECK_ARG(logits && labels_a && loss && lse && N > 0 && N <= XF_MAX_ROWS && ncls > 0 && (!scaled || scale),
+                "xent_soft_fwd_fused: bad args (N=%d)", N);
+  DTC_CHECK_ARG(soft_args_ok(labels_b, lam, smoothing),
+                "xent_soft_fwd_fused: labels_b and lam go together, smoothing = %g must be in [0, 1]", (double)smoothing);
+  DTC_KLAUNCH(xent_soft_fwd_fused_kernel, dim3(1), dim3(1024), 0, st, logits, labels_a,
+                     labels_b ? labels_b : labels_a, lam, smoothing, N, ncls, loss, lse, scale, scaled, host);
+  DTC_LAUNCH_CHECK();
+  return 0;
+}
+
 // d loss / d logit = (softmax - onehot) * gscale / N: one definition for xent_bwd and the fused head backward
 __device__ __forceinline__ float xent_gain(const float* gscale, int N) { return (gscale ? *gscale : 1.f) / (float)N; }
 __device__ __forceinline__ float xent_grad(float z, float lse, bool hit, float g) {
@@ -368,6 +494,93 @@ __global__ void __launch_bounds__(256) xent_bwd_kernel(const float* __restrict__
     const int b = (int)(i / ncls), j = (int)(i % ncls);
     dl[i] = xent_grad(logits[i], lse[b], labels[b] == j, g);
   }
+}
+
+// The soft loss without the row cap (xent_fwd's two-launch form: xent_lse_kernel, then this mean): thread t
+// takes rows t, t + 256, ... as xent_mean_kernel does and sums each row's logits serially.
+__global__ void __launch_bounds__(256) xent_soft_mean_kernel(const float* __restrict__ logits,
+                                                            const int64_t* __restrict__ la,
+                                                            const int64_t* __restrict__ lb,
+                                                            const float* __restrict__ lam, float eps,
+                                                            const float* __restrict__ lse, int N, int ncls,
+                                                            float* __restrict__ loss) {
+  __shared__ float part[4];
+  const int t = threadIdx.x;
+  float acc = 0.f;
+  for (int b = t; b < N; b += 256) {
+    const float* z = logits + (int64_t)b * ncls;
+    const int64_t ya = la[b], yb = lb[b];
+    const bool ok = ya >= 0 && ya < ncls && yb >= 0 && yb < ncls;
+    float sz = 0.f;
+    if (eps > 0.f)
+      for (int j = 0; j < ncls; ++j) sz += z[j];
+    acc += xent_soft_term(lse[b], ok ? z[ya] : 0.f, ok ? z[yb] : 0.f, lam ? lam[b] : 1.f, eps, sz, ncls, ok);
+  }
+  acc = wave_sum(acc);
+  if ((t & 63) == 0) part[t >> 6] = acc;
+  __syncthreads();
+  if (t == 0) *loss = (part[0] + part[1] + part[2] + part[3]) / (float)N;
+}
+
+int xent_soft_fwd(const float* logits, const int64_t* labels_a, const int64_t* labels_b, const float* lam,
+                  float smoothing, int N, int ncls, float* loss, float* lse, hipStream_t st) {
+  DTC_CHECK_ARG(logits && labels_a && loss && lse && N > 0 && ncls > 0, "xent_soft_fwd: bad args");
+  DTC_CHECK_ARG(soft_args_ok(labels_b, lam, smoothing),
+                "xent_soft_fwd: labels_b and lam go together, smoothing = %g must be in [0, 1]", (double)smoothing);
+  DTC_KLAUNCH(xent_lse_kernel, dim3((N + 15) / 16), dim3(256), 0, st, logits, N, ncls, lse);
+  DTC_LAUNCH_CHECK();
+  DTC_KLAUNCH(xent_soft_mean_kernel, dim3(1), dim3(256), 0, st, logits, labels_a, labels_b ? labels_b : labels_a,
+                     lam, smoothing, lse, N, ncls, loss);
+  DTC_LAUNCH_CHECK();
+  return 0;
+}
+
+// Soft targets: d loss / d logit = (softmax - q) * gscale / N with q as above xent_soft_term. With eps = 0,
+// lam = 1 and yb = ya, q is 1 * (1 * hit + 0 * hit) + 0 = hit exactly (contracted or not), and the value is
+// xent_grad's bit for bit. A label out of range hits no class.
+struct SoftRow {
+  int64_t ya, yb;
+  float lam;
+};
+__device__ __forceinline__ SoftRow soft_row(const XentArgs& xa, int n) {
+  return SoftRow{xa.labels[n], xa.labels_b[n], xa.lam ? xa.lam[n] : 1.f};
+}
+__device__ __forceinline__ float xent_soft_grad(float z, float lse, const SoftRow& r, int j, float eps, float unif,
+                                                float g) {
+  const float q = (1.f - eps) * (r.lam * (r.ya == j ? 1.f : 0.f) + (1.f - r.lam) * (r.yb == j ? 1.f : 0.f)) + unif;
+  return (expf(z - lse) - q) * g;
+}
+
+__global__ void __launch_bounds__(256) xent_soft_bwd_kernel(XentArgs xa, int N, int ncls, float* __restrict__ dl) {
+  const int64_t total = (int64_t)N * ncls;
+  const float g = xent_gain(xa.gscale, N);
+  const float eps = xa.smoothing, unif = eps / (float)ncls;
+  for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int b = (int)(i / ncls), j = (int)(i % ncls);
+    dl[i] = xent_soft_grad(xa.logits[i], xa.lse[b], soft_row(xa, b), j, eps, unif, g);
+  }
+}
+
+int xent_soft_bwd(const float* logits, const int64_t* labels_a, const int64_t* labels_b, const float* lam,
+                  float smoothing, const float* lse, const float* gscale, int N, int ncls, float* dlogits,
+                  hipStream_t st) {
+  DTC_CHECK_ARG(logits && labels_a && lse && dlogits && N > 0 && ncls > 0, "xent_soft_bwd: bad args");
+  DTC_CHECK_ARG(soft_args_ok(labels_b, lam, smoothing),
+                "xent_soft_bwd: labels_b and lam go together, smoothing = %g must be in [0, 1]", (double)smoothing);
+  XentArgs xa;
+  xa.logits = logits;
+  xa.labels = labels_a;
+  xa.labels_b = labels_b ? labels_b : labels_a;
+  xa.lam = lam;
+  xa.smoothing = smoothing;
+  xa.lse = lse;
+  xa.gscale = gscale;
+  xa.soft = true;
+  const int64_t total = (int64_t)N * ncls;
+  const int blocks = (int)std::min<int64_t>(1024, (total + 255) / 256);
+  DTC_KLAUNCH(xent_soft_bwd_kernel, dim3(blocks), dim3(256), 0, st, xa, N, ncls, dlogits);
+  DTC_LAUNCH_CHECK();
+  return 0;
 }
 
 int xent_bwd(const float* logits, const int64_t* labels, const float* lse, const float* gscale, int N, int ncls,
@@ -537,7 +750,9 @@ __global__ void __launch_bounds__(256) head_bwd_x_kernel(const float* __restrict
 // XE: the CrossEntropyLoss backward fused in (xa.logits != nullptr): every dlogits value is computed where
 // it is used, by xent_grad as xent_bwd computes it, and the dact workgroups also store their image's row
 // into dl (the executor's dlogits buffer) -- one launch fewer right after the per-step barrier.
-template <typename T, bool XE>
+// SOFT (with XE): the soft-target gradient xent_soft_grad in place of xent_grad, a third instantiation for the
+// same reason XE is a template value; <T, false> and <T, true> are unchanged by it.
+template <typename T, bool XE, bool SOFT = false>
 __global__ void __launch_bounds__(256) head_bwd_fused_kernel(float* __restrict__ dl,
                                                             const float* __restrict__ feat,
                                                             const T* __restrict__ wfc, int N, int HW, int C, int ncls,
@@ -550,6 +765,7 @@ __global__ void __launch_bounds__(256) head_bwd_fused_kernel(float* __restrict__
   // from batching its loads -- 26.6 vs 10.9 us per launch at batch 256)
   constexpr bool xe = XE;
   const float xg = xe ? xent_gain(xa.gscale, N) : 0.f;
+  const float eps = SOFT ? xa.smoothing : 0.f, unif = SOFT ? xa.smoothing / (float)ncls : 0.f;
   if ((int)blockIdx.x < nw) {
     // dW[j][c..c+3] (float4 of feat per lane) and db[j]: wave w sums the images n = w, w + 4, ... (eight
     // rows in flight per lane), the four wave partials are added in LDS in a fixed order
@@ -564,7 +780,13 @@ __global__ void __launch_bounds__(256) head_bwd_fused_kernel(float* __restrict__
       float* dcol = hsx + 4 * 260;
       for (int n0 = 0; n0 < N; n0 += 256) {
         const int nn = min(256, N - n0);
-        if (t < nn) dcol[t] = xent_grad(xa.logits[(int64_t)(n0 + t) * ncls + j], xa.lse[n0 + t], xa.labels[n0 + t] == j, xg);
+        if constexpr (SOFT) {
+          if (t < nn)
+            dcol[t] = xent_soft_grad(xa.logits[(int64_t)(n0 + t) * ncls + j], xa.lse[n0 + t], soft_row(xa, n0 + t), j,
+                                     eps, unif, xg);
+        } else {
+          if (t < nn) dcol[t] = xent_grad(xa.logits[(int64_t)(n0 + t) * ncls + j], xa.lse[n0 + t], xa.labels[n0 + t] == j, xg);
+        }
         __syncthreads();
         if (c < C) {
 #pragma unroll 8
@@ -604,7 +826,15 @@ __global__ void __launch_bounds__(256) head_bwd_fused_kernel(float* __restrict__
     return;
   }
   const int n = blockIdx.x - nw;
-  if constexpr (XE) {
+  if constexpr (XE && SOFT) {
+    const float ls = xa.lse[n];
+    const SoftRow sr = soft_row(xa, n);
+    for (int j = t; j < ncls; j += 256) {
+      const float d = xent_soft_grad(xa.logits[(int64_t)n * ncls + j], ls, sr, j, eps, unif, xg);
+      hsx[j] = d;
+      dl[(int64_t)n * ncls + j] = d;
+    }
+  } else if constexpr (XE) {
     const float ls = xa.lse[n];
     const int64_t lab = xa.labels[n];
     for (int j = t; j < ncls; j += 256) {
@@ -621,7 +851,8 @@ static int head_bwd_t(const float* dlogits, const float* feat, const T* wfc, int
                       float scale, float* dw, float* db, T* dact, float* ws, size_t ws_bytes, hipStream_t st,
                       const XentArgs* xa) {
   DTC_CHECK_ARG(dlogits && feat && wfc && dw && db && dact && N > 0 && HW > 0 && C > 0 && C % 8 == 0 && C <= 2048 &&
-                    ncls > 0 && ncls <= 4096 && (!xa || (xa->logits && xa->labels && xa->lse)),
+                    ncls > 0 && ncls <= 4096 && (!xa || (xa->logits && xa->labels && xa->lse)) &&
+                    (!xa || !xa->soft || xa->labels_b),
                 "head_bwd: bad args");
   // head_dact_image / fused dW (+ the fused-xent dlogits column)
   const size_t dx_lds = (size_t)std::max(ncls + 4 * C, 4 * 260 + 256) * sizeof(float);
@@ -630,7 +861,10 @@ static int head_bwd_t(const float* dlogits, const float* feat, const T* wfc, int
   const int hf = option_get(OPT_HEAD_FUSED);
   if (ncls <= 1024 && (hf == 1 || (hf == 2 && N <= 64))) {
     const int nw = ncls * ((C + 255) / 256);
-    if (xa)
+    if (xa && xa->soft)
+      DTC_KLAUNCH((head_bwd_fused_kernel<T, true, true>), dim3(nw + N), dim3(256), dx_lds, st, (float*)dlogits, feat,
+                         wfc, N, HW, C, ncls, scale, dw, db, dact, nw, *xa);
+    else if (xa)
       DTC_KLAUNCH((head_bwd_fused_kernel<T, true>), dim3(nw + N), dim3(256), dx_lds, st, (float*)dlogits, feat,
                          wfc, N, HW, C, ncls, scale, dw, db, dact, nw, *xa);
     else
@@ -639,7 +873,11 @@ static int head_bwd_t(const float* dlogits, const float* feat, const T* wfc, int
     DTC_LAUNCH_CHECK();
     return 0;
   }
-  if (xa) DTC_TRY(xent_bwd(xa->logits, xa->labels, xa->lse, xa->gscale, N, ncls, (float*)dlogits, st));
+  if (xa && xa->soft)
+    DTC_TRY(xent_soft_bwd(xa->logits, xa->labels, xa->labels_b == xa->labels ? nullptr : xa->labels_b, xa->lam,
+                          xa->smoothing, xa->lse, xa->gscale, N, ncls, (float*)dlogits, st));
+  else if (xa)
+    DTC_TRY(xent_bwd(xa->logits, xa->labels, xa->lse, xa->gscale, N, ncls, (float*)dlogits, st));
   DTC_CHECK_ARG(ws && ws_bytes >= head_bwd_workspace(N, C, ncls), "head_bwd: workspace too small");
   const int splits = (N + HB_IMGS - 1) / HB_IMGS;
   DTC_KLAUNCH(head_bwd_w_partial_kernel, dim3((C + 63) / 64, (ncls + 15) / 16, splits), dim3(256), 0, st,

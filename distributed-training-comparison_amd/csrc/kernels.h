@@ -336,6 +336,18 @@ int eval_metrics(const float* logits, const int64_t* labels, int N, int ncls, in
 // dlogits = (softmax - onehot) * (*gscale) / N
 int xent_bwd(const float* logits, const int64_t* labels, const float* lse, const float* gscale, int N, int ncls,
              float* dlogits, hipStream_t st);
+// Soft targets q = (1 - smoothing) * (lam * onehot(labels_a) + (1 - lam) * onehot(labels_b)) + smoothing / ncls
+// per row (label smoothing, Mixup, CutMix); labels_b == lam == nullptr: lam = 1. The forward is xent_fwd_fused
+// with the same lse bits; with smoothing = 0 and no labels_b loss and dlogits are the hard kernels' bit for bit.
+int xent_soft_fwd_fused(const float* logits, const int64_t* labels_a, const int64_t* labels_b, const float* lam,
+                        float smoothing, int N, int ncls, float* loss, float* lse, const float* scale, float* scaled,
+                        float* host, hipStream_t st);
+// the same loss without the row cap, two launches (xent_fwd's form): the fallback for N > 4096
+int xent_soft_fwd(const float* logits, const int64_t* labels_a, const int64_t* labels_b, const float* lam,
+                  float smoothing, int N, int ncls, float* loss, float* lse, hipStream_t st);
+int xent_soft_bwd(const float* logits, const int64_t* labels_a, const int64_t* labels_b, const float* lam,
+                  float smoothing, const float* lse, const float* gscale, int N, int ncls, float* dlogits,
+                  hipStream_t st);
 // dW = scale*dlogits^T feat ; db = scale*sum dlogits ; dact[n][hw][c] = (dlogits . W)[c] / HW
 size_t head_bwd_workspace(int N, int C, int ncls);
 // fp32 mode: fp32 activations and fp32 Linear weights, no autocast rounding
@@ -343,11 +355,17 @@ int head_fwd(const float* act, int N, int HW, int C, const float* wfc, const flo
              float* logits, hipStream_t st);
 // xa != nullptr: the CrossEntropyLoss backward is fused in -- dlogits is computed from (logits, labels,
 // lse, gscale) exactly as xent_bwd does, used directly, and also stored into `dlogits` (an output then)
+// soft: the soft-target gradient (xent_soft_bwd) from labels (= labels_a), labels_b (never null then: labels_a
+// when there is no second label), lam (nullptr: 1) and smoothing
 struct XentArgs {
   const float* logits = nullptr;
   const int64_t* labels = nullptr;
   const float* lse = nullptr;
   const float* gscale = nullptr;
+  const int64_t* labels_b = nullptr;
+  const float* lam = nullptr;
+  float smoothing = 0.f;
+  bool soft = false;
 };
 int head_bwd(const float* dlogits, const float* feat, const float* wfc, int N, int HW, int C, int ncls, float scale,
              float* dw, float* db, float* dact, float* ws, size_t ws_bytes, hipStream_t st,
@@ -399,5 +417,11 @@ int amp_update_scale(float* scale, float* inv_scale, int* growth_tracker, int* f
 int cifar_augment(const uint8_t* images, const int64_t* targets, int64_t n_images, const int64_t* index,
                   const uint8_t* crop, const uint8_t* flip, int n, int h, int w, int pad, const float* mean,
                   const float* stdv, float* out, int64_t* labels, int* status, hipStream_t st);
+// the same launch mixing every row with a partner row of the batch (partner NULL: b - 1 cyclically): mode 1
+// Mixup out = A_b * lam + A_p * (1 - lam), mode 2 CutMix out = A_p inside box (y0, y1, x0, x1), A_b outside
+int cifar_augment_mix(const uint8_t* images, const int64_t* targets, int64_t n_images, const int64_t* index,
+                      const uint8_t* crop, const uint8_t* flip, int n, int h, int w, int pad, const float* mean,
+                      const float* stdv, const int32_t* partner, int mode, const float* lam, const uint8_t* box,
+                      float* out, int64_t* labels, int64_t* labels_b, int* status, hipStream_t st);
 
 }  // namespace dtc

@@ -2047,4 +2047,33 @@ int dtc_rn18_xent_backward(dtc_net* net, const float* logits, const int64_t* lab
   return backward(n, dl, grad_scale, (Comm*)comm, (hipStream_t)stream);
 }
 
+int dtc_rn18_xent_soft_backward(dtc_net* net, const float* logits, const int64_t* labels_a, const int64_t* labels_b,
+                                const float* lam, float smoothing, const float* lse, const float* gscale,
+                                float grad_scale, dtc_comm* comm, void* stream) {
+  DTC_CHECK_ARG(net && net->n.ws && logits && labels_a && lse,
+                "dtc_rn18_xent_soft_backward: unbound net or null pointer");
+  DTC_CHECK_ARG((labels_b != nullptr) == (lam != nullptr) && smoothing >= 0.f && smoothing <= 1.f,
+                "dtc_rn18_xent_soft_backward: labels_b and lam go together, smoothing = %g must be in [0, 1]",
+                (double)smoothing);
+  Net& n = net->n;
+  float* dl = n.at<float>(n.DLOGITS);
+  // the rule of dtc_rn18_xent_backward: fused into the eager head backward, a separate launch otherwise
+  if (option_get(OPT_XENT_FUSE) != 0 && !n.capture && !graphs_on(n, true, comm != nullptr)) {
+    n.xent.logits = logits;
+    n.xent.labels = labels_a;
+    n.xent.labels_b = labels_b ? labels_b : labels_a;
+    n.xent.lam = lam;
+    n.xent.smoothing = smoothing;
+    n.xent.soft = true;
+    n.xent.lse = lse;
+    n.xent.gscale = gscale;
+    const int rc = backward(n, dl, grad_scale, (Comm*)comm, (hipStream_t)stream);
+    n.xent = XentArgs();
+    return rc;
+  }
+  DTC_TRY(xent_soft_bwd(logits, labels_a, labels_b, lam, smoothing, lse, gscale, n.B, n.ncls, dl,
+                        (hipStream_t)stream));
+  return backward(n, dl, grad_scale, (Comm*)comm, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -16,7 +16,7 @@ from __future__ import annotations
 
 import math
 import random
-from typing import Iterator, List, Optional, Tuple
+from typing import Iterator, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -179,6 +179,51 @@ def synthetic_cifar_u8(n: int = 50000, height: int = 32, width: int = 32, num_cl
     return images, targets
 
 
+class MixParams(NamedTuple):
+    """One epoch's Mixup / CutMix parameters (host arrays, see mix_params)."""
+
+    mode: np.ndarray  # int32 [n_batches]: 0 none, 1 Mixup, 2 CutMix
+    lam: np.ndarray   # fp32 [n_batches, batch]: the weight of labels_a in the loss (and Mixup's blend weight)
+    box: np.ndarray   # uint8 [n_batches, batch, 4]: CutMix's (y0, y1, x0, x1), half open
+    draw: np.ndarray  # fp64 [n_batches]: the batch's Beta(alpha, alpha) draw (1 for mode 0)
+
+
+def mix_params(n_batches: int, batch: int, h: int, w: int, mixup_alpha: float = 0.0, cutmix_alpha: float = 0.0,
+               prob: float = 1.0, rng: Optional[np.random.Generator] = None) -> MixParams:
+    """Mixup / CutMix parameters of a whole epoch, drawn on the host with a seeded numpy Generator
+    (torchvision.transforms.v2.MixUp / CutMix's rules, one draw per batch, repeated over its rows):
+    a batch is mixed with probability `prob`, by Mixup or CutMix -- each with probability 1/2 when both alphas
+    are set; lam ~ Beta(alpha, alpha); CutMix's box has its centre uniform in the image and half sizes
+    int(0.5 * sqrt(1 - lam) * W), int(0.5 * sqrt(1 - lam) * H), clamped to the image, and the loss then uses
+    the adjusted lam = 1 - area / (H * W)."""
+    if mixup_alpha < 0 or cutmix_alpha < 0 or not 0.0 <= prob <= 1.0:
+        raise ValueError("mix_params: alphas must be >= 0 and prob in [0, 1]")
+    if not (0 < h <= 255 and 0 < w <= 255):
+        raise ValueError("mix_params: boxes are uint8, h and w must be in [1, 255]")
+    rng = rng if rng is not None else np.random.default_rng()
+    nb = int(n_batches)
+    apply = rng.random(nb) < prob
+    second = rng.random(nb) < 0.5
+    draw_m = rng.beta(mixup_alpha, mixup_alpha, nb) if mixup_alpha > 0 else np.ones(nb)
+    draw_c = rng.beta(cutmix_alpha, cutmix_alpha, nb) if cutmix_alpha > 0 else np.ones(nb)
+    cy, cx = rng.integers(0, h, nb), rng.integers(0, w, nb)
+    if mixup_alpha > 0 and cutmix_alpha > 0:
+        kind = np.where(second, 2, 1)
+    else:
+        kind = np.full(nb, 1 if mixup_alpha > 0 else (2 if cutmix_alpha > 0 else 0))
+    mode = np.where(apply, kind, 0).astype(np.int32)
+    draw = np.where(mode == 1, draw_m, np.where(mode == 2, draw_c, 1.0))
+    r = 0.5 * np.sqrt(1.0 - draw)
+    hh, hw_ = (r * h).astype(np.int64), (r * w).astype(np.int64)
+    y0, y1 = np.clip(cy - hh, 0, None), np.clip(cy + hh, None, h)
+    x0, x1 = np.clip(cx - hw_, 0, None), np.clip(cx + hw_, None, w)
+    cut = mode == 2
+    box1 = np.where(cut[:, None], np.stack([y0, y1, x0, x1], 1), 0).astype(np.uint8)
+    area = (box1[:, 1].astype(np.int64) - box1[:, 0]) * (box1[:, 3].astype(np.int64) - box1[:, 2])
+    lam1 = np.where(cut, 1.0 - area / float(h * w), draw).astype(np.float32)
+    return MixParams(mode, np.repeat(lam1[:, None], batch, 1), np.repeat(box1[:, None, :], batch, 1), draw)
+
+
 class DeviceLoader:
     """``DataLoader(Subset(dataset, subset_idx), batch_size, sampler=sampler, drop_last=...)`` with
     the reference's train (or valid/test) transform (src/ddp/dataset.py:43-64, 95-116) executed on
@@ -189,12 +234,26 @@ class DeviceLoader:
     generator seeded with ``seed + epoch`` (torchvision draws them with the worker processes' CPU
     RNG, which no run reproduces across worker counts either; distributions are the same:
     offsets uniform on [0, 2*pad], flip with p = 0.5). Out-of-range indices are detected on the
-    device and raised at the end of the epoch (one host sync per epoch)."""
+    device and raised at the end of the epoch (one host sync per epoch).
+
+    ``mixup_alpha`` / ``cutmix_alpha`` > 0 (train loaders only): every batch is mixed with probability
+    ``mix_prob`` by Mixup or CutMix with itself rolled by one row, in the same single launch
+    (``ops.cifar_augment_mix``). The epoch's parameters are drawn on the host from ``seed + epoch``
+    (``mix_params``) and uploaded once, like the index list; a mixed batch yields ``(images, nn.MixedTarget)``,
+    an unmixed one the plain launch's ``(images, labels)``. ``last_params`` is then ``(index, crop, flip, mix)``
+    with ``mix`` a dict of the batch's ``mode``, ``lam`` (the loss's), ``box`` and the Beta ``draw``."""
 
     def __init__(self, images, targets, batch_size: int, subset_idx=None, sampler=None, train: bool = True,
                  mean=CIFAR_MEAN, std=CIFAR_STD, pad: int = 4, drop_last: bool = True, seed: int = 0,
-                 device=None):
+                 device=None, mixup_alpha: float = 0.0, cutmix_alpha: float = 0.0, mix_prob: float = 1.0):
         from . import ops
+
+        self.mixup_alpha, self.cutmix_alpha, self.mix_prob = float(mixup_alpha), float(cutmix_alpha), float(mix_prob)
+        self.mixing = self.mixup_alpha > 0 or self.cutmix_alpha > 0
+        if self.mixing and not train:
+            raise ValueError("DeviceLoader: Mixup / CutMix are training transforms (train=False with an alpha > 0)")
+        if self.mixup_alpha < 0 or self.cutmix_alpha < 0 or not 0.0 <= self.mix_prob <= 1.0:
+            raise ValueError("DeviceLoader: alphas must be >= 0 and mix_prob in [0, 1]")
 
         self._ops = ops
         dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -227,6 +286,14 @@ class DeviceLoader:
         gen = torch.Generator(device=self.device)
         gen.manual_seed(self.seed + self.epoch)
         B = self.batch_size
+        mix = lam_d = box_d = None
+        if self.mixing:
+            from .nn import MixedTarget
+
+            mix = mix_params(len(self), B, self.images.shape[1], self.images.shape[2], self.mixup_alpha,
+                             self.cutmix_alpha, self.mix_prob, np.random.default_rng(self.seed + self.epoch))
+            lam_d = torch.from_numpy(mix.lam).to(self.device)
+            box_d = torch.from_numpy(mix.box).to(self.device)
         finished = False
         try:
             for k in range(len(self)):
@@ -237,7 +304,18 @@ class DeviceLoader:
                     crop = torch.randint(0, 2 * self.pad + 1, (n, 2), dtype=torch.uint8, device=self.device,
                                          generator=gen)
                     flip = torch.randint(0, 2, (n,), dtype=torch.uint8, device=self.device, generator=gen)
-                self.last_params = (idx, crop, flip)
+                if mix is not None:
+                    mode = int(mix.mode[k])
+                    self.last_params = (idx, crop, flip, {"mode": mode, "lam": lam_d[k, :n], "box": box_d[k, :n],
+                                                          "draw": float(mix.draw[k])})
+                    if mode:
+                        x, ya, yb = self._ops.cifar_augment_mix(
+                            self.images, idx, crop, flip, self.mean, self.std, self.pad, targets=self.targets,
+                            mode=mode, lam=lam_d[k, :n], box=box_d[k, :n], status=self.status)
+                        yield x, MixedTarget(ya, yb, lam_d[k, :n])
+                        continue
+                else:
+                    self.last_params = (idx, crop, flip)
                 yield self._ops.cifar_augment(self.images, idx, crop, flip, self.mean, self.std, self.pad,
                                               targets=self.targets, status=self.status)
             finished = True
@@ -246,7 +324,7 @@ class DeviceLoader:
             # and reset, so a bad index is reported for the epoch it happened in, never a later one
             if int(self.status.item()):
                 self.status.zero_()
-                msg = "DeviceLoader: a sampler index or crop offset was out of range this epoch"
+                msg = "DeviceLoader: a sampler index, crop offset or mix parameter was out of range this epoch"
                 if finished:
                     raise IndexError(msg)
                 import warnings

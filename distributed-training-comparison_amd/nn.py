@@ -192,6 +192,14 @@ class Executor:
              None if gscale is None else gscale.data_ptr(), float(grad_scale), comm.handle if comm else None,
              _raw_stream(logits.device.index))
 
+    def xent_soft_backward(self, logits, soft, lse, gscale, grad_scale: float, comm) -> None:
+        """xent_backward for a soft target (`soft`: a _Soft): dtc_rn18_xent_soft_backward."""
+        call("dtc_rn18_xent_soft_backward", self.handle, logits.data_ptr(), soft.labels_a.data_ptr(),
+             None if soft.labels_b is None else soft.labels_b.data_ptr(),
+             None if soft.lam is None else soft.lam.data_ptr(), soft.smoothing, lse.data_ptr(),
+             None if gscale is None else gscale.data_ptr(), float(grad_scale), comm.handle if comm else None,
+             _raw_stream(logits.device.index))
+
     def dlogits_buffer(self) -> torch.Tensor:
         """fp32 [batch, num_classes] view of the executor's own dlogits buffer: a loss gradient
         written here is consumed by backward() without the copy-in."""
@@ -315,6 +323,46 @@ class _XentFn(torch.autograd.Function):
         return ops.xent_bwd(logits, labels, lse, g), None
 
 
+class MixedTarget:
+    """The target of a Mixup / CutMix batch (data.DeviceLoader yields it in place of the label tensor): row b's
+    target is lam[b] * onehot(labels_a[b]) + (1 - lam[b]) * onehot(labels_b[b]). labels_a, labels_b: int64 [n],
+    lam: fp32 [n], all on the device already -- ``.to()`` returns the object itself (the trainer calls
+    ``label.to(device)`` on whatever the loader yields)."""
+
+    def __init__(self, labels_a: torch.Tensor, labels_b: torch.Tensor, lam: torch.Tensor):
+        self.labels_a, self.labels_b, self.lam = labels_a, labels_b, lam
+
+    def to(self, *args, **kwargs) -> "MixedTarget":
+        return self
+
+
+class _Soft:
+    """A soft target as the kernels take it: labels_a, optional (labels_b, lam), the launch-wide smoothing. It
+    travels in the `labels` slot of a NativeLoss's direct backward chain."""
+
+    __slots__ = ("labels_a", "labels_b", "lam", "smoothing")
+
+    def __init__(self, labels_a, labels_b, lam, smoothing: float):
+        self.labels_a, self.labels_b, self.lam, self.smoothing = labels_a, labels_b, lam, float(smoothing)
+
+
+class _XentSoftFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, soft):
+        loss, lse, _ = ops.xent_soft_fwd(logits, soft.labels_a, soft.labels_b, soft.lam, soft.smoothing)
+        ctx.save_for_backward(logits, lse)
+        ctx.soft = soft
+        ctx.lse = lse
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        logits, lse = ctx.saved_tensors
+        sf = ctx.soft
+        g = gloss.reshape(1).float().contiguous()
+        return ops.xent_soft_bwd(logits, sf.labels_a, sf.labels_b, sf.lam, sf.smoothing, lse, g), None
+
+
 class NativeLoss(torch.Tensor):
     """Scalar loss of ``CrossEntropyLoss`` applied directly to the native ResNet's logits (and its
     ``GradScaler.scale`` product). Its ``backward()`` runs the known chain
@@ -346,12 +394,20 @@ class NativeLoss(torch.Tensor):
             if model._pre_backward is not None:
                 model._pre_backward()
             exe.consume(node.gen)
-            exe.xent_backward(logits, labels, lse, gscale, model._grad_scale, model._comm)
+            if isinstance(labels, _Soft):
+                exe.xent_soft_backward(logits, labels, lse, gscale, model._grad_scale, model._comm)
+            else:
+                exe.xent_backward(logits, labels, lse, gscale, model._grad_scale, model._comm)
             model._ensure_grads()
         else:  # DataParallel's gathered logits: xent backward, then the replicas' backward + reduce-add
             from .parallel import _DPFn
 
-            _DPFn.backward(node, ops.xent_bwd(logits, labels, lse, gscale))
+            if isinstance(labels, _Soft):
+                dl = ops.xent_soft_bwd(logits, labels.labels_a, labels.labels_b, labels.lam, labels.smoothing, lse,
+                                       gscale)
+            else:
+                dl = ops.xent_bwd(logits, labels, lse, gscale)
+            _DPFn.backward(node, dl)
         if not retain_graph:
             self._dtc_fast = None
         return None
@@ -440,9 +496,73 @@ def scaled_loss(loss: torch.Tensor, scale: torch.Tensor, version: int = -1) -> t
 
 
 class CrossEntropyLoss(nn.Module):
-    """nn.CrossEntropyLoss() with mean reduction (reference trainer.py:40) on the native kernel."""
+    """nn.CrossEntropyLoss() with mean reduction (reference trainer.py:40) on the native kernel.
+    ``label_smoothing`` and a ``MixedTarget`` (Mixup / CutMix) make the target of a row the distribution
+    (1 - eps) * (lam * onehot(ya) + (1 - lam) * onehot(yb)) + eps / ncls, on the soft-target kernels through
+    the same routes; with neither, the index-label kernels run exactly as without the keyword. Class weights,
+    ``ignore_index``, other reductions and probability-tensor targets are not built."""
 
-    def forward(self, logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    def __init__(self, weight=None, size_average=None, ignore_index: int = -100, reduce=None,
+                 reduction: str = "mean", label_smoothing: float = 0.0):
+        super().__init__()
+        if weight is not None:
+            raise NotImplementedError("CrossEntropyLoss: class weights are not built natively")
+        if ignore_index != -100:
+            raise NotImplementedError("CrossEntropyLoss: ignore_index is not built natively")
+        if reduction != "mean" or size_average is not None or reduce is not None:
+            raise NotImplementedError("CrossEntropyLoss: only the mean reduction is built natively")
+        if not 0.0 <= float(label_smoothing) <= 1.0:
+            raise ValueError(f"label_smoothing must be in [0, 1], got {label_smoothing}")
+        self.label_smoothing = float(label_smoothing)
+
+    def _forward_soft(self, logits: torch.Tensor, target) -> torch.Tensor:
+        if isinstance(target, MixedTarget):
+            la, lb, lam = target.labels_a, target.labels_b, target.lam
+            require_cuda(logits, la, lb, lam)
+            soft = _Soft(la.long().contiguous(), lb.long().contiguous(), lam.float().contiguous(),
+                         self.label_smoothing)
+        else:
+            if target.is_floating_point():
+                raise NotImplementedError("CrossEntropyLoss: probability-tensor targets are not built natively "
+                                          "(pass class indices or a MixedTarget)")
+            require_cuda(logits, target)
+            soft = _Soft(target.long().contiguous(), None, None, self.label_smoothing)
+        if logits.dtype != torch.float32:
+            logits = logits.float()
+        logits = logits.contiguous()
+        node = logits.grad_fn
+        if torch.is_grad_enabled() and node is not None:
+            from .parallel import _DPFn
+
+            if isinstance(node, (_NetFn._backward_cls, _DPFn._backward_cls)):
+                if logits.shape[0] <= 4096:  # the one-launch loss, as the index-label path below
+                    sc = _prescaler()
+                    if _HOST_WORDS[0] is None:
+                        _HOST_WORDS[0] = _HostWords()
+                    ring = _HOST_WORDS[0]
+                    slot, host, gen = ring.take()
+                    loss, lse, scaled = ops.xent_soft_fwd(logits, soft.labels_a, soft.labels_b, soft.lam,
+                                                          soft.smoothing, None if sc is None else sc._scale, host)
+                    ev = torch.cuda.Event()
+                    ev.record()
+                    ring.done(slot, ev)
+                    out = _wrap_loss(loss, lambda: _XentSoftFn.apply(logits, soft), (node, logits, soft, lse, None))
+                    out._dtc_host = (host, ev, ring, slot, gen)
+                    if sc is not None:
+                        prescale(out, scaled, sc)
+                    return out
+                loss = _XentSoftFn.apply(logits, soft)
+                out = _wrap_loss(loss, lambda: loss, (node, logits, soft, loss.grad_fn.lse, None), host_copy=True)
+                prescale(out)
+                return out
+        return _XentSoftFn.apply(logits, soft)
+
+    def forward(self, logits: torch.Tensor, labels) -> torch.Tensor:
+        if isinstance(labels, MixedTarget) or self.label_smoothing > 0.0:
+            return self._forward_soft(logits, labels)
+        if labels.is_floating_point():
+            raise NotImplementedError("CrossEntropyLoss: probability-tensor targets are not built natively "
+                                      "(pass class indices or a MixedTarget)")
         require_cuda(logits, labels)
         if logits.dtype != torch.float32:
             logits = logits.float()

@@ -392,6 +392,50 @@ def xent_bwd(logits, labels, lse, gscale=None, out=None):
     return dl
 
 
+def _soft_check(logits, labels_a, labels_b, lam):
+    require_cuda(logits, labels_a, labels_b, lam)
+    n = logits.shape[0]
+    if (labels_b is None) != (lam is None):
+        raise ValueError("labels_b and lam go together (both or neither)")
+    for t, dt in ((labels_a, torch.int64), (labels_b, torch.int64), (lam, torch.float32)):
+        if t is not None and (t.dtype != dt or tuple(t.shape) != (n,) or not t.is_contiguous()):
+            raise ValueError(f"expected contiguous {dt} ({n},), got {t.dtype} {tuple(t.shape)}")
+    if logits.dtype != torch.float32 or logits.dim() != 2 or not logits.is_contiguous():
+        raise ValueError(f"logits must be contiguous fp32 [n, ncls], got {logits.dtype} {tuple(logits.shape)}")
+
+
+def xent_soft_fwd(logits, labels_a, labels_b=None, lam=None, smoothing=0.0, scale=None, host=None):
+    """Mean cross-entropy against the soft target q = (1 - smoothing) * (lam * onehot(labels_a) + (1 - lam) *
+    onehot(labels_b)) + smoothing / ncls per row (label smoothing, Mixup, CutMix; labels_b = lam = None: lam = 1).
+    Returns (loss, lse, scaled): n <= 4096 is one launch (dtc_xent_soft_fwd_ex) that also stores loss * scale
+    (`scale`: a device fp32 scalar) into `scaled` and the loss into `host` (a pinned host word); beyond, the
+    two-launch form (no scale / host there). lse is bit-identical to xent_fwd's."""
+    _soft_check(logits, labels_a, labels_b, lam)
+    n, ncls = logits.shape
+    loss = torch.empty((), dtype=torch.float32, device=logits.device)
+    lse = torch.empty(n, dtype=torch.float32, device=logits.device)
+    if n > 4096:
+        if scale is not None or host is not None:
+            raise NativeError("xent_soft_fwd: scale / host need n <= 4096")
+        call("dtc_xent_soft_fwd", ptr(logits), ptr(labels_a), ptr(labels_b), ptr(lam), float(smoothing), n, ncls,
+             ptr(loss), ptr(lse), stream_ptr())
+        return loss, lse, None
+    scaled = torch.empty((), dtype=torch.float32, device=logits.device) if scale is not None else None
+    call("dtc_xent_soft_fwd_ex", ptr(logits), ptr(labels_a), ptr(labels_b), ptr(lam), float(smoothing), n, ncls,
+         ptr(loss), ptr(lse), ptr(scale), ptr(scaled), ptr(host), stream_ptr())
+    return loss, lse, scaled
+
+
+def xent_soft_bwd(logits, labels_a, labels_b, lam, smoothing, lse, gscale=None, out=None):
+    """dlogits = (softmax(logits) - q) * gscale / n for xent_soft_fwd's q."""
+    _soft_check(logits, labels_a, labels_b, lam)
+    n, ncls = logits.shape
+    dl = torch.empty_like(logits) if out is None else out
+    call("dtc_xent_soft_bwd", ptr(logits), ptr(labels_a), ptr(labels_b), ptr(lam), float(smoothing), ptr(lse),
+         ptr(gscale), n, ncls, ptr(dl), stream_ptr())
+    return dl
+
+
 def sgd_nesterov_flat(p, g, mom, pb, lr, weight_decay, momentum, inv_scale=None, found_inf=None):
     call("dtc_sgd_nesterov_flat", ptr(p), ptr(g), ptr(mom), ptr(pb), p.numel(), float(lr), float(weight_decay),
          float(momentum), ptr(inv_scale), ptr(found_inf), stream_ptr())
@@ -472,3 +516,33 @@ def cifar_augment(images, index, crop, flip, mean, std, pad=4, targets=None, out
     call("dtc_cifar_augment", ptr(images), ptr(targets), n_images, ptr(index), ptr(crop), ptr(flip), n, h, w, int(pad),
          m, s, ptr(out), ptr(labels), ptr(status), stream_ptr())
     return out, labels
+
+
+def cifar_augment_mix(images, index, crop, flip, mean, std, pad=4, targets=None, partner=None, mode=1, lam=None,
+                      box=None, out=None, labels=None, labels_b=None, status=None):
+    """cifar_augment plus Mixup (mode 1: out[b] = A_b * lam[b] + A_p * (1 - lam[b])) or CutMix (mode 2: out[b] = A_p
+    inside box[b] = (y0, y1, x0, x1), A_b outside) in the same launch, A the augmented batch and p = partner[b]
+    (int32 [n], None: b - 1 cyclically, batch.roll(1, 0)). lam: fp32 [n]; box: uint8 [n, 4]. Returns (fp32
+    [n,3,H,W], labels, labels_b) with labels_b[b] = targets[index[partner[b]]] (None without targets)."""
+    require_cuda(images, index, crop, flip, targets, partner, lam, box, out, labels, labels_b, status)
+    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3 or not images.is_contiguous():
+        raise ValueError(f"images must be contiguous uint8 [N,H,W,3], got {images.dtype} {tuple(images.shape)}")
+    n_images, h, w, _ = images.shape
+    n = index.numel() if index is not None else (crop.shape[0] if crop is not None else n_images)
+    for t, shape, dt in ((index, (n,), torch.int64), (crop, (n, 2), torch.uint8), (flip, (n,), torch.uint8),
+                         (targets, (n_images,), torch.int64), (partner, (n,), torch.int32),
+                         (lam, (n,), torch.float32), (box, (n, 4), torch.uint8)):
+        if t is not None and (t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous()):
+            raise ValueError(f"expected contiguous {dt} {shape}, got {t.dtype} {tuple(t.shape)}")
+    if out is None:
+        out = torch.empty(n, 3, h, w, dtype=torch.float32, device=images.device)
+    if targets is not None and labels is None:
+        labels = torch.empty(n, dtype=torch.int64, device=images.device)
+    if targets is not None and labels_b is None:
+        labels_b = torch.empty(n, dtype=torch.int64, device=images.device)
+    m = (C.c_float * 3)(*[float(v) for v in mean])
+    s = (C.c_float * 3)(*[float(v) for v in std])
+    call("dtc_cifar_augment_mix", ptr(images), ptr(targets), n_images, ptr(index), ptr(crop), ptr(flip), n, h, w,
+         int(pad), m, s, ptr(partner), int(mode), ptr(lam), ptr(box), ptr(out), ptr(labels), ptr(labels_b),
+         ptr(status), stream_ptr())
+    return out, labels, labels_b

@@ -55,6 +55,16 @@ def load_config(argv=None, mode: str = "ddp"):
                    help="fused flat-buffer optimizer; --lr and --weight-decay pass through")
     p.add_argument("--clip-grad-norm", type=float, default=0.0,
                    help="clip the global gradient L2 norm to this value before each step (0 = off)")
+    # not in the reference either: the regularizers people change first at larger global batches
+    p.add_argument("--label-smoothing", type=float, default=0.0,
+                   help="CrossEntropyLoss(label_smoothing=) of the TRAINING loss; validate() and test() report "
+                        "the plain cross-entropy whatever this is (also with --fused-eval)")
+    p.add_argument("--mixup-alpha", type=float, default=0.0,
+                   help="Mixup with lam ~ Beta(alpha, alpha) per batch, on the device (needs --device-data; 0 = off)")
+    p.add_argument("--cutmix-alpha", type=float, default=0.0,
+                   help="CutMix with lam ~ Beta(alpha, alpha) per batch, on the device (needs --device-data; 0 = off)")
+    p.add_argument("--mix-prob", type=float, default=1.0,
+                   help="probability that a batch is mixed; with both alphas set each kind is picked half the time")
     # synthetic-data size knobs (not in the reference: CIFAR-100 cannot be downloaded here)
     p.add_argument("--synthetic-train", type=int, default=50000)
     p.add_argument("--synthetic-test", type=int, default=10000)
@@ -67,7 +77,14 @@ def load_config(argv=None, mode: str = "ddp"):
     if mode == "dp":  # not in the reference (nn.DataParallel takes every visible GPU): replica placement
         p.add_argument("--device-ids", type=lambda v: [int(d) for d in v.split(",")], default=None,
                        help="comma-separated GPU ids of the replicas (may repeat); default: all visible")
-    return p.parse_args(argv)
+    h = p.parse_args(argv)
+    if not 0.0 <= h.label_smoothing <= 1.0:
+        p.error("--label-smoothing must be in [0, 1]")
+    if h.mixup_alpha < 0 or h.cutmix_alpha < 0 or not 0.0 <= h.mix_prob <= 1.0:
+        p.error("--mixup-alpha / --cutmix-alpha must be >= 0 and --mix-prob in [0, 1]")
+    if (h.mixup_alpha > 0 or h.cutmix_alpha > 0) and not h.device_data:
+        p.error("--mixup-alpha / --cutmix-alpha need --device-data (the host loader does not mix)")
+    return h
 
 
 def accuracy(output, target, topk=(1,)):
@@ -94,6 +111,24 @@ class AverageMeter:
         self.avg = self.sum / self.count
 
 
+def make_criteria(hparams):
+    """(training criterion, evaluation criterion): --label-smoothing shapes the training loss only; validate()
+    and test() keep the plain cross-entropy (the number --fused-eval's device metrics report too). With the
+    default 0 both are the one CrossEntropyLoss() the reference builds (trainer.py:40)."""
+    eps = float(getattr(hparams, "label_smoothing", 0.0))
+    plain = CrossEntropyLoss()
+    return (CrossEntropyLoss(label_smoothing=eps) if eps > 0 else plain), plain
+
+
+def mix_kwargs(hparams) -> dict:
+    """The train DeviceLoader's Mixup / CutMix keywords (none with the default flags). Mixing is per process:
+    per rank under DDP, before the scatter under DataParallel (the loss sees the gathered logits)."""
+    ma, ca = float(getattr(hparams, "mixup_alpha", 0.0)), float(getattr(hparams, "cutmix_alpha", 0.0))
+    if ma <= 0 and ca <= 0:
+        return {}
+    return {"mixup_alpha": ma, "cutmix_alpha": ca, "mix_prob": float(getattr(hparams, "mix_prob", 1.0))}
+
+
 class Trainer:
     def __init__(self, hparams, model, scaler, rank: int = 0, ngpus_per_node: int = 1, distributed: bool = False,
                  data_parallel: bool = False):
@@ -110,7 +145,7 @@ class Trainer:
             hparams.batch_size = int(hparams.batch_size / ngpus_per_node)                  # ddp/trainer.py:34
         self.scaler = scaler
         self.optimizer, self.lr_scheduler = self.configure_optimizers()
-        self.criterion = CrossEntropyLoss()
+        self.criterion, self.eval_criterion = make_criteria(hparams)
         if getattr(hparams, "device_data", False):
             self._device_loaders(hparams, distributed)
         else:
@@ -150,7 +185,7 @@ class Trainer:
                    else torch.utils.data.SubsetRandomSampler(list(range(len(train_idx)))))
         bs = hparams.batch_size
         self.train_loader = D.DeviceLoader(imgs, tg, bs, subset_idx=train_idx, sampler=sampler, train=True,
-                                           seed=hparams.seed, device=self.device)
+                                           seed=hparams.seed, device=self.device, **mix_kwargs(hparams))
         self.train_sampler = self.train_loader
         self.val_loader = D.DeviceLoader(imgs, tg, bs, subset_idx=valid_idx, train=False, drop_last=False,
                                          device=self.device)
@@ -276,7 +311,7 @@ class Trainer:
             for img, label in self.val_loader:
                 img, label = img.to(self.device), label.to(self.device)
                 pred = net(img)
-                val_loss.update(self.criterion(pred, label).item())
+                val_loss.update(self.eval_criterion(pred, label).item())
                 top1.update(accuracy(pred, label, topk=(1,))[0].item())
         net.train()
         return val_loss.avg, top1.avg
@@ -293,7 +328,7 @@ class Trainer:
                 for img, label in self.test_loader:
                     img, label = img.to(self.device), label.to(self.device)
                     pred = net(img)
-                    test_loss.update(self.criterion(pred, label).item())
+                    test_loss.update(self.eval_criterion(pred, label).item())
                     p1, p5 = accuracy(pred, label, topk=(1, 5))
                     top1.update(p1.item())
                     top5.update(p5.item())

@@ -201,6 +201,28 @@ int dtc_xent_fwd_ex(const float* logits, const int64_t* labels, int n, int ncls,
                     const float* scale, float* scaled, float* host_loss, void* stream);
 int dtc_xent_bwd(const float* logits, const int64_t* labels, const float* lse, const float* gscale, int n, int ncls,
                  float* dlogits, void* stream);
+/* Soft targets: label smoothing, Mixup and CutMix as one loss. The target of row b is the distribution
+ *   q_b = (1 - smoothing) * (lam[b] * onehot(labels_a[b]) + (1 - lam[b]) * onehot(labels_b[b])) + smoothing / ncls
+ * (nn.CrossEntropyLoss(label_smoothing=) on the two-hot target torchvision's MixUp / CutMix produce), so with
+ * l_b the row's log-sum-exp
+ *   loss      = mean_b (l_b - (1 - smoothing) * (lam z[ya] + (1 - lam) z[yb]) - (smoothing / ncls) * sum_j z[b][j])
+ *   dlogits   = (exp(z[b][j] - l_b) - q_b[j]) * (*gscale) / n            (gscale NULL: 1)
+ * labels_b == NULL and lam == NULL (both or neither, else DTC_EINVAL): label smoothing only, lam = 1, yb = ya.
+ * labels_a[b] == labels_b[b] puts both terms on one class. A label outside [0, ncls) makes the loss NaN, as in
+ * dtc_xent_fwd, and hits no class in the gradient; a lam outside [0, 1] (or NaN) makes the loss NaN.
+ * smoothing outside [0, 1]: DTC_EINVAL, nothing is launched. dtc_xent_soft_fwd_ex is one launch with
+ * dtc_xent_fwd_ex's outputs (n <= 4096); lse is bit-identical to dtc_xent_fwd_ex's, and with smoothing = 0 and
+ * no labels_b so are the loss (finite logits) and dtc_xent_soft_bwd's dlogits to dtc_xent_bwd's. */
+int dtc_xent_soft_fwd_ex(const float* logits, const int64_t* labels_a, const int64_t* labels_b, const float* lam,
+                         float smoothing, int n, int ncls, float* loss, float* lse, const float* scale, float* scaled,
+                         float* host_loss, void* stream);
+/* loss and lse as dtc_xent_soft_fwd_ex without the row cap, two launches (dtc_xent_fwd's form; lse bit-identical,
+ * the loss equal to rounding: the row sums are formed in another order) */
+int dtc_xent_soft_fwd(const float* logits, const int64_t* labels_a, const int64_t* labels_b, const float* lam,
+                      float smoothing, int n, int ncls, float* loss, float* lse, void* stream);
+int dtc_xent_soft_bwd(const float* logits, const int64_t* labels_a, const int64_t* labels_b, const float* lam,
+                      float smoothing, const float* lse, const float* gscale, int n, int ncls, float* dlogits,
+                      void* stream);
 /* Evaluation metrics of one batch (reference trainer.py validate / test: `criterion(pred, label).item()` and
  * utils.py:18-31 `accuracy(pred, label, topk)`), one launch of one workgroup, no host synchronisation: writes
  * *rec (device memory, 16 bytes) and nothing else. 1 <= n <= 4096, ncls >= 1, 1 <= topk <= ncls.
@@ -275,6 +297,23 @@ int dtc_amp_update_scale(float* scale, float* inv_scale, int* growth_tracker, in
 int dtc_cifar_augment(const uint8_t* images, const int64_t* targets, int64_t n_images, const int64_t* index,
                       const uint8_t* crop, const uint8_t* flip, int n, int h, int w, int pad, const float* mean,
                       const float* std, float* out, int64_t* labels, int* status, void* stream);
+
+/* dtc_cifar_augment plus Mixup / CutMix in the same launch (torchvision.transforms.v2.MixUp / CutMix: the
+ * augmented batch mixed with a permutation of itself). With A_b what dtc_cifar_augment writes for row b
+ * (index, crop, flip of b) and p = partner[b] (int32 [n], a row of THIS batch; NULL: (b + n - 1) % n, i.e.
+ * batch.roll(1, 0)), the partner keeping its own crop and flip:
+ *   mode 1 (Mixup):  out[b] = A_b * lam[b] + A_p * (1 - lam[b])   lam fp32 [n]; two rounded fp32 products and one
+ *                    rounded add, 1 - lam[b] formed in fp32
+ *   mode 2 (CutMix): out[b] = A_p inside box[b], A_b outside      box uint8 [n][4] = (y0, y1, x0, x1), half open,
+ *                    in output coordinates
+ * labels[b] = targets[index[b]], labels_b[b] = targets[index[p]] (int64 [n] outputs, NULL: skip). Both uint8
+ * source images of a row are staged in LDS and the batch is written once. status is also set, and the row
+ * written unmixed (labels_b[b] = labels[b]), when partner[b] is outside [0, n), the box is inverted or leaves
+ * the image, or lam is outside [0, 1]. Other arguments, conditions and shape limits as dtc_cifar_augment. */
+int dtc_cifar_augment_mix(const uint8_t* images, const int64_t* targets, int64_t n_images, const int64_t* index,
+                          const uint8_t* crop, const uint8_t* flip, int n, int h, int w, int pad, const float* mean,
+                          const float* std, const int32_t* partner, int mode, const float* lam, const uint8_t* box,
+                          float* out, int64_t* labels, int64_t* labels_b, int* status, void* stream);
 
 /* ------------------------------------------------------------------ RCCL communicator
  * Replaces the NCCL traffic of DistributedDataParallel (trainer.py:31): the construction-time
@@ -405,6 +444,13 @@ int dtc_rn18_set_sync_bn(dtc_net* net, dtc_comm* comm);
  * log-sum-exp dtc_xent_fwd wrote, gscale: device fp32 scalar or NULL (1). */
 int dtc_rn18_xent_backward(dtc_net* net, const float* logits, const int64_t* labels, const float* lse,
                            const float* gscale, float grad_scale, dtc_comm* comm, void* stream);
+/* The same call for soft targets (dtc_xent_soft_bwd's dlogits; lse from dtc_xent_soft_fwd_ex), under the same
+ * rule: computed inside the head backward kernel when the backward runs eagerly and option xent_fuse != 0,
+ * otherwise one dtc_xent_soft_bwd launch into the executor's dlogits buffer, then dtc_rn18_backward. With
+ * smoothing = 0 and labels_b = lam = NULL every gradient is bit-identical to dtc_rn18_xent_backward's. */
+int dtc_rn18_xent_soft_backward(dtc_net* net, const float* logits, const int64_t* labels_a, const int64_t* labels_b,
+                                const float* lam, float smoothing, const float* lse, const float* gscale,
+                                float grad_scale, dtc_comm* comm, void* stream);
 /* One evaluation batch (reference trainer.py validate / test: `net(img)` in eval mode, the loss and
  * `accuracy`) as one call with no host synchronisation: the eval-mode forward (running statistics) of the
  * first n_valid images of x, then dtc_eval_metrics over their logits and labels into *rec (device memory).
