@@ -23,27 +23,50 @@ def conv_out_hw(h, w, r, s, stride, pad):
     return (h + 2 * pad - r) // stride + 1, (w + 2 * pad - s) // stride + 1
 
 
-def _ws(desc, mode, device):
+def _ws(desc, mode, device, workspace=None):
     nbytes = lib.dtc_conv2d_workspace_size(desc, mode)
     if nbytes == 0:
         return None, 0
+    if workspace is not None:
+        return _given_ws(workspace, nbytes), nbytes
     return torch.empty(nbytes // 4 + 1, dtype=torch.float32, device=device), nbytes
 
 
-def conv2d_fwd(x, w, stride, pad, stats=None):
-    """x [N,H,W,C] bf16, w [K,R,S,C] bf16 -> y [N,P,Q,K] bf16 (nn.Conv2d forward, net.py:18)."""
+def _given_ws(workspace, nbytes):
+    """A caller's workspace: contiguous, on the GPU, at least the `nbytes` the size query returned."""
+    require_cuda(workspace)
+    if not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < nbytes:
+        raise ValueError(f"workspace must be contiguous and hold {nbytes} bytes, got "
+                         f"{workspace.numel() * workspace.element_size()}")
+    return workspace
+
+
+def _out(out, shape, dtype, device, what):
+    """The output tensor: a fresh one (the default), or the caller's `out` checked for shape, dtype, contiguity."""
+    if out is None:
+        return torch.empty(*shape, dtype=dtype, device=device)
+    require_cuda(out)
+    if tuple(out.shape) != tuple(shape) or out.dtype != dtype or not out.is_contiguous():
+        raise ValueError(f"{what}: out must be contiguous {dtype} {tuple(shape)}, got {out.dtype} {tuple(out.shape)}")
+    return out
+
+
+def conv2d_fwd(x, w, stride, pad, stats=None, out=None, workspace=None):
+    """x [N,H,W,C] bf16, w [K,R,S,C] bf16 -> y [N,P,Q,K] bf16 (nn.Conv2d forward, net.py:18). Here and in the
+    other conv / stem wrappers, `out` (a tuple / list where several tensors are returned) and `workspace` (at
+    least the bytes the size query returns) replace the tensors allocated by default."""
     require_cuda(x, w)
     N, H, W, Cc = x.shape
     K, R, S, _ = w.shape
     d = conv_desc(N, H, W, Cc, K, R, S, stride, pad)
     P, Q = conv_out_hw(H, W, R, S, stride, pad)
-    y = torch.empty(N, P, Q, K, dtype=torch.bfloat16, device=x.device)
-    ws, nb = _ws(d, 0, x.device)
+    y = _out(out, (N, P, Q, K), torch.bfloat16, x.device, "conv2d_fwd")
+    ws, nb = _ws(d, 0, x.device, workspace)
     call("dtc_conv2d_fwd", d, ptr(x), ptr(w), ptr(y), ptr(stats), ptr(ws), nb, stream_ptr())
     return y
 
 
-def conv2d_fwd_sc(x, w, wsc, stats=None, stats_sc=None):
+def conv2d_fwd_sc(x, w, wsc, stats=None, stats_sc=None, out=None):
     """3x3 stride-2 conv + the 1x1 stride-2 projection shortcut of the same x in one launch (net.py:18-19,
     29-36): x [N,H,W,C], w [K,3,3,C], wsc [K,C] bf16 -> (y, ysc) [N,H/2,W/2,K] bf16."""
     require_cuda(x, w, wsc)
@@ -51,21 +74,20 @@ def conv2d_fwd_sc(x, w, wsc, stats=None, stats_sc=None):
     K = w.shape[0]
     d = conv_desc(N, H, W, Cc, K, 3, 3, 2, 1)
     P, Q = conv_out_hw(H, W, 3, 3, 2, 1)
-    y = torch.empty(N, P, Q, K, dtype=torch.bfloat16, device=x.device)
-    ysc = torch.empty_like(y)
+    y, ysc = (_out(o, (N, P, Q, K), torch.bfloat16, x.device, "conv2d_fwd_sc") for o in (out if out is not None else (None, None)))
     call("dtc_conv2d_fwd_sc", d, ptr(x), ptr(w), ptr(y), ptr(stats), ptr(wsc), ptr(ysc), ptr(stats_sc), stream_ptr())
     return y, ysc
 
 
-def conv2d_dgrad(dy, w, in_hw, stride, pad, res=None):
+def conv2d_dgrad(dy, w, in_hw, stride, pad, res=None, out=None, workspace=None):
     """dy [N,P,Q,K] bf16, w [K,R,S,C] -> dx [N,H,W,C] bf16 (+ res)."""
     require_cuda(dy, w)
     N = dy.shape[0]
     K, R, S, Cc = w.shape
     H, W = in_hw
     d = conv_desc(N, H, W, Cc, K, R, S, stride, pad)
-    dx = torch.empty(N, H, W, Cc, dtype=torch.bfloat16, device=dy.device)
-    ws, nb = _ws(d, 1, dy.device)
+    dx = _out(out, (N, H, W, Cc), torch.bfloat16, dy.device, "conv2d_dgrad")
+    ws, nb = _ws(d, 1, dy.device, workspace)
     call("dtc_conv2d_dgrad", d, ptr(dy), ptr(w), ptr(dx), ptr(res), ptr(ws), nb, stream_ptr())
     return dx
 
@@ -88,19 +110,19 @@ def conv2d_dgrad_bn(dy, w, in_hw, stride, pad, ymask, x1, mean1, invstd1, x2=Non
     return dz, acc1, acc2
 
 
-def conv2d_wgrad(x, dy, r, s, stride, pad, scale=1.0):
+def conv2d_wgrad(x, dy, r, s, stride, pad, scale=1.0, out=None, workspace=None):
     """x [N,H,W,C] bf16, dy [N,P,Q,K] bf16 -> dw [K,R,S,C] fp32 (scaled)."""
     require_cuda(x, dy)
     N, H, W, Cc = x.shape
     K = dy.shape[3]
     d = conv_desc(N, H, W, Cc, K, r, s, stride, pad)
-    dw = torch.empty(K, r, s, Cc, dtype=torch.float32, device=x.device)
-    ws, nb = _ws(d, 2, x.device)
+    dw = _out(out, (K, r, s, Cc), torch.float32, x.device, "conv2d_wgrad")
+    ws, nb = _ws(d, 2, x.device, workspace)
     call("dtc_conv2d_wgrad", d, ptr(x), ptr(dy), ptr(dw), float(scale), ptr(ws), nb, stream_ptr())
     return dw
 
 
-def conv2d_dgrad_sc(dy, w, dsc, wsc, in_hw):
+def conv2d_dgrad_sc(dy, w, dsc, wsc, in_hw, out=None):
     """dx through a projection block's conv1 (3x3 stride 2) and its 1x1 stride-2 shortcut in one launch
     (dtc_conv2d_dgrad_sc): dy / dsc [N,P,Q,K], w [K,3,3,C], wsc [K,C] bf16 -> dx [N,H,W,C] bf16."""
     require_cuda(dy, w, dsc, wsc)
@@ -108,12 +130,12 @@ def conv2d_dgrad_sc(dy, w, dsc, wsc, in_hw):
     Cc = w.shape[3]
     H, W = in_hw
     d = conv_desc(N, H, W, Cc, K, 3, 3, 2, 1)
-    dx = torch.empty(N, H, W, Cc, dtype=torch.bfloat16, device=dy.device)
+    dx = _out(out, (N, H, W, Cc), torch.bfloat16, dy.device, "conv2d_dgrad_sc")
     call("dtc_conv2d_dgrad_sc", d, ptr(dy), ptr(w), ptr(dx), ptr(dsc), ptr(wsc), stream_ptr())
     return dx
 
 
-def conv2d_wgrad_sc(x, dy, dsc, scale=1.0):
+def conv2d_wgrad_sc(x, dy, dsc, scale=1.0, out=None, workspace=None):
     """Weight gradients of a projection block's 3x3 stride-2 conv1 and its 1x1 stride-2 shortcut in one
     launch (dtc_conv2d_wgrad_sc): x [N,H,W,C], dy / dsc [N,H/2,W/2,K] bf16 -> (dw [K,3,3,C], dw_sc [K,C])."""
     require_cuda(x, dy, dsc)
@@ -123,15 +145,17 @@ def conv2d_wgrad_sc(x, dy, dsc, scale=1.0):
     nb = lib.dtc_conv2d_wgrad_sc_workspace_size(d)
     if nb == 0:
         raise ValueError(f"conv2d_wgrad_sc: no fused plan for {(N, H, W, Cc, K)}")
-    ws = torch.empty(nb // 4 + 64, dtype=torch.float32, device=x.device)
-    dw = torch.empty(K, 3, 3, Cc, dtype=torch.float32, device=x.device)
-    dw_sc = torch.empty(K, Cc, dtype=torch.float32, device=x.device)
+    ws = _given_ws(workspace, nb) if workspace is not None else \
+        torch.empty(nb // 4 + 64, dtype=torch.float32, device=x.device)
+    o = out if out is not None else (None, None)
+    dw = _out(o[0], (K, 3, 3, Cc), torch.float32, x.device, "conv2d_wgrad_sc")
+    dw_sc = _out(o[1], (K, Cc), torch.float32, x.device, "conv2d_wgrad_sc")
     call("dtc_conv2d_wgrad_sc", d, ptr(x), ptr(dy), ptr(dsc), ptr(dw), ptr(dw_sc), float(scale), ptr(ws), nb,
          stream_ptr())
     return dw, dw_sc
 
 
-def conv2d_wgrad_batch(xs, dys, scale=1.0):
+def conv2d_wgrad_batch(xs, dys, scale=1.0, out=None, workspace=None):
     """n (<= 4) same-shape 3x3 stride-1 weight gradients in one launch (dtc_conv2d_wgrad_batch):
     xs[i] [N,H,W,C] bf16, dys[i] [N,H,W,K] bf16 -> list of dw [K,3,3,C] fp32 (scaled)."""
     require_cuda(*xs, *dys)
@@ -142,8 +166,11 @@ def conv2d_wgrad_batch(xs, dys, scale=1.0):
     nb = lib.dtc_conv2d_wgrad_batch_workspace_size(d, n)
     if nb == 0:
         raise ValueError(f"conv2d_wgrad_batch: no batched halo plan for {(N, H, W, Cc, K)} x {n}")
-    ws = torch.empty(nb // 4 + 64, dtype=torch.float32, device=xs[0].device)
-    dws = [torch.empty(K, 3, 3, Cc, dtype=torch.float32, device=xs[0].device) for _ in range(n)]
+    ws = _given_ws(workspace, nb) if workspace is not None else \
+        torch.empty(nb // 4 + 64, dtype=torch.float32, device=xs[0].device)
+    if out is not None and len(out) != n:
+        raise ValueError(f"conv2d_wgrad_batch: out must list {n} tensors, got {len(out)}")
+    dws = [_out(o, (K, 3, 3, Cc), torch.float32, xs[0].device, "conv2d_wgrad_batch") for o in (out if out is not None else [None] * n)]
     arr = C.c_void_p * n
     call("dtc_conv2d_wgrad_batch", d, n, arr(*[ptr(t) for t in xs]), arr(*[ptr(t) for t in dys]),
          arr(*[ptr(t) for t in dws]), float(scale), ptr(ws), nb, stream_ptr())
@@ -313,20 +340,21 @@ def stem_im2col(x):
     return cols
 
 
-def stem_fwd(x, w27, stats=None):
+def stem_fwd(x, w27, stats=None, out=None):
     """Direct stem conv (dtc_stem_fwd): x [N,3,H,W] fp32, w27 [64,27] bf16 (KRSC) -> y [N,H,W,64] bf16."""
     n, _, h, w = x.shape
-    y = torch.empty(n, h, w, 64, dtype=torch.bfloat16, device=x.device)
+    y = _out(out, (n, h, w, 64), torch.bfloat16, x.device, "stem_fwd")
     call("dtc_stem_fwd", ptr(x), ptr(w27), ptr(y), ptr(stats), n, h, w, stream_ptr())
     return y
 
 
-def stem_wgrad(x, dy, scale=1.0):
+def stem_wgrad(x, dy, scale=1.0, out=None, workspace=None):
     """Direct stem weight gradient (dtc_stem_wgrad): x [N,3,H,W] fp32, dy [N,H,W,64] bf16 -> [64,27] fp32."""
     n, _, h, w = x.shape
     nb = lib.dtc_stem_wgrad_workspace_size(n, h, w)
-    ws = torch.empty(nb // 4 + 64, dtype=torch.float32, device=x.device)
-    dw = torch.empty(64, 27, dtype=torch.float32, device=x.device)
+    ws = _given_ws(workspace, nb) if workspace is not None else \
+        torch.empty(nb // 4 + 64, dtype=torch.float32, device=x.device)
+    dw = _out(out, (64, 27), torch.float32, x.device, "stem_wgrad")
     call("dtc_stem_wgrad", ptr(x), ptr(dy), ptr(dw), float(scale), n, h, w, ptr(ws), nb, stream_ptr())
     return dw
 

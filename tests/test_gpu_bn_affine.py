@@ -21,6 +21,7 @@ import pytest
 import torch
 
 from oracle import ops as O
+from tests import bounds as B
 from tests.conftest import rel_err
 from tests.test_gpu_resnet import _teacher_forced
 
@@ -181,6 +182,17 @@ def test_bn_fin_apply(dtc, cuda, C, M, mode):
     e = rel_err(yh, ref)
     print(f"bn_fin_apply mode {mode} M={M} C={C}: y rel err {e:.2e}")
     assert e < 1e-2
+    # element-wise (tests/bounds.py), against the unrounded z = x*a + b of each branch
+    z1, dz1 = B.bn_z(x, b1.gamma, b1.beta, b1.mean_ref, b1.invstd_ref)
+    if mode == 1:
+        ref_b, tol_b = B.bn_apply_ref_tol(z1, dz1)
+    elif mode == 2:
+        ref_b, tol_b = B.bn_apply_ref_tol(z1, dz1, res=x2)
+    else:
+        z2, dz2 = B.bn_z(x2, b2.gamma, b2.beta, b2.mean_ref, b2.invstd_ref)
+        ref_b, tol_b = B.bn_apply_ref_tol(z1, dz1, z2=z2, dz2=dz2)
+    ratio = B.assert_within(yh, ref_b, tol_b, f"bn_fin_apply mode {mode} M={M} C={C}")
+    print(f"bn_fin_apply mode {mode} M={M} C={C}: worst |err|/tol {ratio:.3f}")
     # the zero-gamma channel is relu(beta [+ the other branch]) whatever x holds; per channel, so that a wrong
     # shift in one channel cannot hide in the norm
     zc = C - 3
@@ -230,6 +242,8 @@ def test_bn_bwd_mask(dtc, cuda, C, dual, M, forms, refused):
                                                i1.astype(np.float64))
     dx2_ref, dg2_ref, db2_ref = O.bn_train_bwd(dz_ref, x2, gamma2.astype(np.float64), m2.astype(np.float64),
                                                i2.astype(np.float64))
+    tol1 = B.bn_bwd_tol(dx1_ref, dz_ref, x1, gamma1, m1, i1)  # element-wise bounds (tests/bounds.py)
+    tol2 = B.bn_bwd_tol(dx2_ref, dz_ref, x2, gamma2, m2, i2)
     mask = torch.from_numpy(np.packbits(bits, axis=-1, bitorder="little").reshape(-1)).to(dev)
     dy_d, x1_d, x2_d = _bf(dy, dev), _bf(x1, dev), _bf(x2, dev)
     second = dict(x2=x2_d, gamma2=_f(gamma2, dev), mean2=_f(m2, dev), invstd2=_f(i2, dev)) if dual else {}
@@ -265,6 +279,11 @@ def test_bn_bwd_mask(dtc, cuda, C, dual, M, forms, refused):
             e2 = rel_err(r["dx2"], dx2_ref)
         print(f"bn_bwd_mask C={C} M={M} dual={dual} one_launch={one_launch}: dx1 rel err {e1:.2e}, dx2 {e2:.2e}")
         assert e1 < 1e-2 and e2 < 1e-2
+        ratio = B.assert_within(r["dx1"], dx1_ref, tol1, f"bn_bwd_mask C={C} M={M} one_launch={one_launch} dx1")
+        if dual:
+            ratio = max(ratio, B.assert_within(r["dx2"], dx2_ref, tol2,
+                                               f"bn_bwd_mask C={C} M={M} one_launch={one_launch} dx2"))
+        print(f"bn_bwd_mask C={C} M={M} dual={dual} one_launch={one_launch}: worst |err|/tol {ratio:.3f}")
         if one_launch:
             assert float(r["acc"].abs().sum()) == 0.0
         else:

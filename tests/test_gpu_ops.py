@@ -3,16 +3,25 @@
 Inputs are drawn at bf16-representable values so the kernel and the oracle see identical
 operands; the oracle accumulates in float64. Tolerances: bf16 outputs 1e-2 relative (north_star
 "per-layer activations and gradients within 1e-2 relative (bf16)"); fp32-output kernels
-(wgrad, BN statistics, SGD) tighter where the arithmetic allows.
+(wgrad, BN statistics, SGD) tighter where the arithmetic allows. Beside each bf16-output norm check, every
+element is held to the derived bound of tests/bounds.py (the norm alone lets a few pixels be arbitrarily wrong).
 """
 import numpy as np
 import pytest
 import torch
 
 from oracle import ops as O
+from tests import bounds as B
 from tests.conftest import rel_err
 
 pytestmark = pytest.mark.gpu
+
+
+def _within(name, *checks):
+    """Element-wise bounds (tests/bounds.py) beside the norm criterion: checks = (what, got, ref, tol); prints
+    the worst |err| / tol of the test in one line."""
+    worst = max(B.assert_within(got, ref, tol, f"{name} {what}") for what, got, ref, tol in checks)
+    print(f"{name}: worst |err|/tol {worst:.3f}")
 
 CONV_CASES = [
     # (N, H, W, C, K, R, stride)  -> pad = 1 for 3x3, 0 for 1x1
@@ -79,6 +88,8 @@ def test_conv_fwd_stride2_halo_and_shortcut(dtc, cuda, case, cfg):
         lib.dtc_set_option(b"halo_s2", prev)
     y2, ysc = y2.float().cpu().numpy(), ysc.float().cpu().numpy()
     assert rel_err(y, ref) < 1e-2 and rel_err(y2, ref) < 1e-2 and rel_err(ysc, ref_sc) < 1e-2
+    tl, tl_sc = B.fwd_tol(ref, x, w, 2, 1), B.fwd_tol(ref_sc, x, wsc, 2, 0)
+    _within(f"halo_s2 fwd {case} cfg {cfg}", ("y", y, ref, tl), ("fused y", y2, ref, tl), ("fused ysc", ysc, ref_sc, tl_sc))
     for out, stt in ((y, st), (y2, st1), (ysc, st2)):  # BN statistics of the bf16 outputs, fp64 slots
         s_ = dtc.ops.stat_totals(stt, K).numpy()
         yb = out.reshape(-1, K).astype(np.float64)
@@ -99,6 +110,7 @@ def test_conv_fwd(dtc, cuda, case):
     yk = y.float().cpu().numpy()
     assert yk.shape == ref.shape
     assert rel_err(yk, ref) < 1e-2
+    _within(f"conv_fwd {case}", ("y", yk, ref, B.fwd_tol(ref, x, w, st, pad)))
     # BN statistics of the bf16 output, accumulated in fp64 slots
     s = dtc.ops.stat_totals(stats, K).numpy()
     yb = yk.reshape(-1, K).astype(np.float64)
@@ -122,6 +134,8 @@ def test_conv_dgrad(dtc, cuda, case, with_res):
     if with_res:
         ref = ref + res
     assert rel_err(dx.float().cpu().numpy(), ref) < 1e-2
+    _within(f"conv_dgrad {case} res={with_res}",
+            ("dx", dx.float().cpu().numpy(), ref, B.dgrad_tol(ref, dy, w, (H, W), st, pad, res=res)))
 
 
 @pytest.mark.parametrize("case", CONV_CASES)
@@ -190,6 +204,8 @@ def test_conv_dgrad_stride2_with_fused_shortcut(dtc, cuda, case):
     finally:
         lib.dtc_set_option(b"dgrad_scf", prev)
     assert rel_err(dx.float().cpu().numpy(), ref) < 1e-2
+    _within(f"dgrad_scf {case}",
+            ("dx", dx.float().cpu().numpy(), ref, B.dgrad_tol(ref, dy, w, (H, W), 2, 1, dsc=dsc, wsc=wsc)))
 
 
 @pytest.mark.parametrize("case", [c for c in CONV_CASES if c[6] == 2])
@@ -211,6 +227,8 @@ def test_conv_dgrad_stride2_paths(dtc, cuda, case, classes):
         dtc._native.call("dtc_set_option", b"dgrad_classes", 1)
     ref = O.conv2d_dgrad(dy, w, (H, W), st, pad) + res
     assert rel_err(dx.float().cpu().numpy(), ref) < 1e-2
+    _within(f"dgrad stride 2 {case} classes={classes}",
+            ("dx", dx.float().cpu().numpy(), ref, B.dgrad_tol(ref, dy, w, (H, W), st, pad, res=res)))
 
 
 def test_mfma_layout_identity(dtc, cuda):
@@ -258,6 +276,12 @@ def test_bn_forward(dtc, cuda, C):
     y_r, *_ = O.bn_train_fwd(x, gamma, beta)
     yr2 = (r - m_ref) * is_ref * gamma + beta
     assert rel_err(y3, O.relu(O.bf16(y_ref) + O.bf16(yr2))) < 1e-2
+    # element-wise, against the unrounded z = x*a + b (the second branch of the dual form applies the same a, b to r)
+    z, dzb = B.bn_z(x, gamma, beta, m_ref, is_ref)
+    zr, dzr = B.bn_z(r, gamma, beta, m_ref, is_ref)
+    _within(f"bn_apply C={C}", ("relu", y, *B.bn_apply_ref_tol(z, dzb)),
+            ("add_relu", y2, *B.bn_apply_ref_tol(z, dzb, res=r)),
+            ("dual_relu", y3, *B.bn_apply_ref_tol(z, dzb, z2=zr, dz2=dzr)))
 
 
 @pytest.mark.parametrize("C,dual", [(64, False), (128, True), (512, False)])
@@ -293,6 +317,14 @@ def test_bn_backward(dtc, cuda, C, dual):
     assert rel_err(dx1.float().cpu().numpy(), dx_ref) < 1e-2
     if dual:
         assert rel_err(dx2.float().cpu().numpy(), dx2_ref) < 1e-2
+    # element-wise: the oracle on the mean / invstd the kernel was given (their fp32 roundings)
+    f64 = lambda a: np.asarray(a, np.float32).astype(np.float64)
+    checks = []
+    for what, dx, xx, gm, mn, iv in (("dx1", dx1, x, gamma, mean, invstd),) + \
+            ((("dx2", dx2, x2, gamma2, mean2, invstd2),) if dual else ()):
+        ref_b, _, _ = O.bn_train_bwd(dz_ref, xx, f64(gm), f64(mn), f64(iv))
+        checks.append((what, dx.float().cpu().numpy(), ref_b, B.bn_bwd_tol(ref_b, dz_ref, xx, f64(gm), f64(mn), f64(iv))))
+    _within(f"bn_bwd_apply C={C} dual={dual}", *checks)
 
 
 @pytest.mark.parametrize("head_fused", [1, 0])
@@ -328,6 +360,8 @@ def _head_and_loss(dtc, cuda):
     assert rel_err(dw.cpu().numpy(), 0.25 * dw_ref) < 1e-5
     assert rel_err(db.cpu().numpy(), 0.25 * db_ref) < 1e-5
     assert rel_err(dact.float().cpu().numpy(), dact_ref) < 1e-2
+    _within("head dact", ("dact", dact.float().cpu().numpy(), dact_ref,
+                          B.head_dact_tol(dact_ref, dl.cpu().numpy(), w, (4, 4))))
 
 
 @pytest.mark.parametrize("n,ncls", [(1, 100), (6, 100), (256, 100), (300, 100), (4096, 100), (7, 10), (256, 10),
@@ -396,6 +430,7 @@ def test_stem_direct_fwd_wgrad(dtc, cuda, shape):
     y = dtc.ops.stem_fwd(xd, _to_dev_bf16(w27.reshape(64, 27), cuda), stats).float().cpu().numpy()
     ref = O.conv2d_fwd(xb, w27, 1, 1)
     assert rel_err(y, O.bf16(ref)) < 1e-2
+    _within(f"stem_fwd {shape}", ("y", y, ref, B.fwd_tol(ref, xb, w27, 1, 1)))  # L = 27
     st = dtc.ops.stat_totals(stats, 64).numpy()
     yb = y.reshape(-1, 64).astype(np.float64)
     np.testing.assert_allclose(st[0], yb.sum(0), rtol=1e-5, atol=1e-3)
@@ -571,13 +606,16 @@ def test_conv_halo_configs(dtc, cuda, case, cfg, split):
         dtc._native.call("dtc_set_option", b"halo_conv", 1)
         dtc._native.call("dtc_set_option", b"halo_split", 0)
     yk = y.float().cpu().numpy()
-    assert rel_err(yk, O.conv2d_fwd(x, w, 1, 1)) < 1e-2
+    ref_y = O.conv2d_fwd(x, w, 1, 1)
+    assert rel_err(yk, ref_y) < 1e-2
     s = dtc.ops.stat_totals(stats, K).numpy()
     yb = yk.reshape(-1, K).astype(np.float64)
     np.testing.assert_allclose(s[0], yb.sum(0), rtol=1e-5, atol=1e-3)
     np.testing.assert_allclose(s[1], (yb * yb).sum(0), rtol=1e-5, atol=1e-3)
     ref = O.conv2d_dgrad(dy, w, (H, W), 1, 1) + res
     assert rel_err(dx.float().cpu().numpy(), ref) < 1e-2
+    _within(f"conv_halo {case} cfg {cfg} split {split}", ("y", yk, ref_y, B.fwd_tol(ref_y, x, w, 1, 1)),
+            ("dx", dx.float().cpu().numpy(), ref, B.dgrad_tol(ref, dy, w, (H, W), 1, 1, res=res)))
 
 
 @pytest.mark.parametrize("case,split", [((256, 4, 4, 512, 512), 0), ((256, 8, 8, 256, 256), 2),
@@ -627,7 +665,10 @@ def test_conv_halo_splitk_in_kernel_matches_reduce_launch(dtc, cuda, case, split
         dtc._native.call("dtc_set_option", b"splitk_ink", prev)
         dtc._native.call("dtc_set_option", b"halo_split", 0)
     yk = ref[0].float().cpu().numpy()
-    assert rel_err(yk, O.conv2d_fwd(x.float().cpu().numpy(), w.float().cpu().numpy(), 1, 1)) < 1e-2
+    xh, wh = x.float().cpu().numpy(), w.float().cpu().numpy()
+    ref_y = O.conv2d_fwd(xh, wh, 1, 1)
+    assert rel_err(yk, ref_y) < 1e-2
+    _within(f"splitk_ink {case} split {split}", ("y", yk, ref_y, B.fwd_tol(ref_y, xh, wh, 1, 1)))
 
 
 GEN_CASES = [
@@ -672,6 +713,10 @@ def test_conv_halo_general_geometry(dtc, cuda, case):
     np.testing.assert_allclose(s[1], (yb * yb).sum(0), rtol=1e-5, atol=1e-3)
     assert rel_err(dxk, O.conv2d_dgrad(dy, w, (H, W), 1, 1) + res) < 1e-2
     assert rel_err(yk, yi) < 1e-2 and rel_err(dxk, dxi) < 1e-2
+    ref_y, ref_dx = O.conv2d_fwd(x, w, 1, 1), O.conv2d_dgrad(dy, w, (H, W), 1, 1) + res
+    tl_y, tl_dx = B.fwd_tol(ref_y, x, w, 1, 1), B.dgrad_tol(ref_dx, dy, w, (H, W), 1, 1, res=res)
+    _within(f"conv_halo general {case}", ("y", yk, ref_y, tl_y), ("dx", dxk, ref_dx, tl_dx),
+            ("igemm y", yi, ref_y, tl_y), ("igemm dx", dxi, ref_dx, tl_dx))
 
 
 C64_CASES = [(2, 32, 32), (3, 16, 16), (5, 32, 32)]
@@ -707,6 +752,9 @@ def test_conv_c64(dtc, cuda, case, c64_forced):
     np.testing.assert_allclose(s[0], yb.sum(0), rtol=1e-5, atol=1e-3)
     np.testing.assert_allclose(s[1], (yb * yb).sum(0), rtol=1e-5, atol=1e-3)
     assert rel_err(dx.float().cpu().numpy(), O.conv2d_dgrad(dy, w, (H, W), 1, 1) + res) < 1e-2
+    ref_y, ref_dx = O.conv2d_fwd(x, w, 1, 1), O.conv2d_dgrad(dy, w, (H, W), 1, 1) + res
+    _within(f"conv_c64 {case}", ("y", yk, ref_y, B.fwd_tol(ref_y, x, w, 1, 1)),
+            ("dx", dx.float().cpu().numpy(), ref_dx, B.dgrad_tol(ref_dx, dy, w, (H, W), 1, 1, res=res)))
 
 
 C64_GEN_CASES = [(2, 16, 224), (3, 8, 64), (2, 40, 96)]
@@ -746,6 +794,10 @@ def test_conv_c64_general_geometry(dtc, cuda, case, c64_forced):
     np.testing.assert_allclose(s[1], (yb * yb).sum(0), rtol=1e-5, atol=1e-3)
     ref = O.conv2d_dgrad(dy, w, (H, W), 1, 1)
     assert rel_err(dxk, ref + res) < 1e-2 and rel_err(dx0k, ref) < 1e-2
+    ref_y = O.conv2d_fwd(x, w, 1, 1)
+    tl_res, tl_0 = (B.dgrad_tol(r_, dy, w, (H, W), 1, 1, res=q_) for r_, q_ in ((ref + res, res), (ref, None)))
+    _within(f"conv_c64 general {case}", ("y", yk, ref_y, B.fwd_tol(ref_y, x, w, 1, 1)),
+            ("dx + res", dxk, ref + res, tl_res), ("dx", dx0k, ref, tl_0), ("conv_halo dx + res", dxh, ref + res, tl_res))
     np.testing.assert_array_equal(yk, yh)
     np.testing.assert_array_equal(dx0k, dx0h)
     assert rel_err(dxk, dxh) < 1e-2  # + residual: conv_halo rounds the same sum (fp32 order may differ)
@@ -771,6 +823,17 @@ def test_conv_c64_large_grid(dtc, cuda):
     torch.cuda.synchronize()
     assert rel_err(y1.float().cpu().numpy(), y0.float().cpu().numpy()) < 1e-2
     assert rel_err(d1.float().cpu().numpy(), d0.float().cpu().numpy()) < 1e-2
+    # against the oracle, element-wise, on the first, middle and last images of the walk (convolutions are
+    # independent per image, so the oracle runs on those six alone); x doubles as dy, as above
+    imgs = torch.tensor([0, 1, 149, 150, 298, 299], device=cuda)
+    xs, wh = x[imgs].float().cpu().numpy(), w.float().cpu().numpy()
+    ref_y, ref_d = O.conv2d_fwd(xs, wh, 1, 1), O.conv2d_dgrad(xs, wh, (32, 32), 1, 1)
+    tl_y, tl_d = B.fwd_tol(ref_y, xs, wh, 1, 1), B.dgrad_tol(ref_d, xs, wh, (32, 32), 1, 1)
+    pick = lambda t: t[imgs].float().cpu().numpy()
+    for got, ref in ((pick(y1), ref_y), (pick(y0), ref_y), (pick(d1), ref_d), (pick(d0), ref_d)):
+        assert rel_err(got, ref) < 1e-2
+    _within("conv_c64 large grid", ("y", pick(y1), ref_y, tl_y), ("dx", pick(d1), ref_d, tl_d),
+            ("igemm y", pick(y0), ref_y, tl_y), ("igemm dx", pick(d0), ref_d, tl_d))
 
 
 BNB_CASES = [
@@ -869,6 +932,8 @@ def test_conv_dgrad_stride2_halo_subpixel(dtc, cuda, case, sc):
     assert rel_err(got, ref) < 1e-2
     assert rel_err(got, dx_gemm.cpu().numpy()) < 1e-2
     assert np.isfinite(got).all()
+    tl = B.dgrad_tol(ref, dy, w, (H, W), 2, 1, dsc=dsc if sc else None, wsc=wsc if sc else None)
+    _within(f"dgrad_s2h {case} sc={sc}", ("dx", got, ref, tl), ("classes dx", dx_gemm.cpu().numpy(), ref, tl))
 
 
 @pytest.mark.parametrize("case", [(4, 32, 32, 64, 64), (12, 4, 4, 512, 512), (8, 16, 16, 128, 128),

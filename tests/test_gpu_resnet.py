@@ -18,6 +18,7 @@ import torch
 
 from oracle import ops as O
 from oracle import resnet as R
+from tests import bounds as B
 from tests.conftest import rel_err
 
 pytestmark = pytest.mark.gpu
@@ -164,10 +165,18 @@ def _teacher_forced(dtc, cuda, batch, hw=32, stages=(0, 1, 2, 3, 4), imgs=None, 
     sel = slice(None) if imgs is None else np.asarray(imgs)
     errs = {}
 
-    def chk(name, got, ref, tol=BF):
+    ratios, el_bad = {}, []
+
+    def chk(name, got, ref, tol=BF, el=None):
+        """el (bf16 mode only): ref -> (reference, element-wise bound) of tests/bounds.py, checked beside the norm."""
         if perturbed:
             assert np.linalg.norm(np.asarray(ref, np.float64).ravel()) > 0, f"vacuous check: {name} has a zero reference"
         errs[name] = (rel_err(got, ref), tol if bf else 1e-5)  # fp32 mode: 1e-5 for everything
+        if bf and el is not None:
+            try:
+                ratios[name] = B.assert_within(got, *el(ref), name)
+            except AssertionError as e:
+                el_bad.append(str(e))
 
     def conv_f(inp, w, st, pad):
         return O.conv2d_fwd(inp[sel], w, st, pad)
@@ -175,12 +184,42 @@ def _teacher_forced(dtc, cuda, batch, hw=32, stages=(0, 1, 2, 3, 4), imgs=None, 
     def conv_d(dy, w, shape_hw, st, pad):
         return O.conv2d_dgrad(dy[sel], w, shape_hw, st, pad)
 
+    def el_f(inp, w, st, pad):
+        return lambda ref: (ref, B.fwd_tol(ref, inp[sel], w, st, pad))
+
+    def el_d(dy, w, shape_hw, st, pad, res=None):
+        """`res`: what the executor adds in the epilogue before the rounding, folded into `ref` by the caller."""
+        return lambda ref: (ref, B.dgrad_tol(ref, dy[sel], w, shape_hw, st, pad, res=res))
+
+    def bn_z(x, g, b):
+        C = x.shape[-1]
+        _, mean, invstd, _, _ = O.bn_train_fwd(x.reshape(-1, C), g, b)
+        return B.bn_z(x, g, b, mean, invstd)
+
+    def el_bn(x, g, b, res=None, x2=None, g2=None, b2=None):
+        """The forward applies against the unrounded z (relu / + residual / + the shortcut's BN)."""
+        def f(_):
+            z2 = bn_z(x2, g2, b2) if x2 is not None else (None, None)
+            return B.bn_apply_ref_tol(*bn_z(x, g, b), res=res, z2=z2[0], dz2=z2[1])
+        return f
+
+    def el_bnb(dz, x, g):
+        """The BN backward's dx, unrounded; the oracle's float64 mean / invstd stand for the fp32 ones the
+        executor saved (one rounding each, two of the chain's eight)."""
+        def f(_):
+            C = x.shape[-1]
+            _, mean, invstd, _, _ = O.bn_train_fwd(x.reshape(-1, C), g, np.zeros(C))
+            dx, _, _ = O.bn_train_bwd(dz.reshape(-1, C), x.reshape(-1, C), g, mean, invstd)
+            dx = dx.reshape(x.shape)
+            return dx, B.bn_bwd_tol(dx, dz, x, g, mean, invstd)
+        return f
+
     # ---------------- forward, layer by layer
     xb = rnd(O.nchw_to_nhwc(x))
     if 0 in stages:
-        chk("stem.conv", A["stem.conv"][sel], conv_f(xb, W["conv1.weight"], 1, 1))
+        chk("stem.conv", A["stem.conv"][sel], conv_f(xb, W["conv1.weight"], 1, 1), el=el_f(xb, W["conv1.weight"], 1, 1))
         a0, _, _ = _bn_fwd(A["stem.conv"], P["bn1.weight"], P["bn1.bias"], rnd)
-        chk("stem.out", A["stem.out"], O.relu(a0))
+        chk("stem.out", A["stem.out"], O.relu(a0), el=el_bn(A["stem.conv"], P["bn1.weight"], P["bn1.bias"]))
     inp = A["stem.out"]
     blocks = []
     for L in range(1, 5):
@@ -190,18 +229,25 @@ def _teacher_forced(dtc, cuda, batch, hw=32, stages=(0, 1, 2, 3, 4), imgs=None, 
             proj = f"{pre}.shortcut.0.weight" in P
             blocks.append((L, pre, st, proj, inp))
             if L in stages:
-                chk(pre + ".conv1", A[pre + ".conv1"][sel], conv_f(inp, W[pre + ".conv1.weight"], st, 1))
+                chk(pre + ".conv1", A[pre + ".conv1"][sel], conv_f(inp, W[pre + ".conv1.weight"], st, 1),
+                    el=el_f(inp, W[pre + ".conv1.weight"], st, 1))
                 z1, _, _ = _bn_fwd(A[pre + ".conv1"], P[pre + ".bn1.weight"], P[pre + ".bn1.bias"], rnd)
-                chk(pre + ".relu1", A[pre + ".relu1"], O.relu(z1))
-                chk(pre + ".conv2", A[pre + ".conv2"][sel], conv_f(A[pre + ".relu1"], W[pre + ".conv2.weight"], 1, 1))
+                chk(pre + ".relu1", A[pre + ".relu1"], O.relu(z1),
+                    el=el_bn(A[pre + ".conv1"], P[pre + ".bn1.weight"], P[pre + ".bn1.bias"]))
+                chk(pre + ".conv2", A[pre + ".conv2"][sel], conv_f(A[pre + ".relu1"], W[pre + ".conv2.weight"], 1, 1),
+                    el=el_f(A[pre + ".relu1"], W[pre + ".conv2.weight"], 1, 1))
                 z2, _, _ = _bn_fwd(A[pre + ".conv2"], P[pre + ".bn2.weight"], P[pre + ".bn2.bias"], rnd)
                 if proj:
-                    chk(pre + ".shortcut", A[pre + ".shortcut"][sel], conv_f(inp, W[pre + ".shortcut.0.weight"], st, 0))
+                    chk(pre + ".shortcut", A[pre + ".shortcut"][sel], conv_f(inp, W[pre + ".shortcut.0.weight"], st, 0),
+                        el=el_f(inp, W[pre + ".shortcut.0.weight"], st, 0))
                     zs, _, _ = _bn_fwd(A[pre + ".shortcut"], P[pre + ".shortcut.1.weight"],
                                        P[pre + ".shortcut.1.bias"], rnd)
-                    chk(pre + ".out", A[pre + ".out"], O.relu(z2 + zs))
+                    chk(pre + ".out", A[pre + ".out"], O.relu(z2 + zs),
+                        el=el_bn(A[pre + ".conv2"], P[pre + ".bn2.weight"], P[pre + ".bn2.bias"], x2=A[pre + ".shortcut"],
+                                 g2=P[pre + ".shortcut.1.weight"], b2=P[pre + ".shortcut.1.bias"]))
                 else:
-                    chk(pre + ".out", A[pre + ".out"], O.relu(z2 + inp))
+                    chk(pre + ".out", A[pre + ".out"], O.relu(z2 + inp),
+                        el=el_bn(A[pre + ".conv2"], P[pre + ".bn2.weight"], P[pre + ".bn2.bias"], res=inp))
             inp = A[pre + ".out"]
     feat, lg = O.head_fwd(inp, P["linear.weight"], P["linear.bias"], bf16_mode=bf)
     if 0 in stages:
@@ -222,16 +268,17 @@ def _teacher_forced(dtc, cuda, batch, hw=32, stages=(0, 1, 2, 3, 4), imgs=None, 
         gp = "grad." + pre
         np.testing.assert_array_equal(G[gp + ".dz"][sel], np.where(A[pre + ".out"] > 0, G[gp + ".dy"], 0)[sel])
         dc2, dg2, db2 = _bn_bwd(G[gp + ".dz"], A[pre + ".conv2"], P[pre + ".bn2.weight"], rnd)
-        chk(gp + ".dc2", G[gp + ".dc2"], dc2)
+        chk(gp + ".dc2", G[gp + ".dc2"], dc2, el=el_bnb(G[gp + ".dz"], A[pre + ".conv2"], P[pre + ".bn2.weight"]))
         chk(pre + ".bn2.weight.grad", grads[pre + ".bn2.weight"], dg2, 1e-3)
         chk(pre + ".bn2.bias.grad", grads[pre + ".bn2.bias"], db2, 1e-3)
         chk(pre + ".conv2.weight.grad", O.kcrs_to_krsc(grads[pre + ".conv2.weight"]),
             O.conv2d_wgrad(A[pre + ".relu1"], G[gp + ".dc2"], 3, 3, 1, 1), F32)
         chk(gp + ".da1", G[gp + ".da1"][sel], conv_d(G[gp + ".dc2"], W[pre + ".conv2.weight"],
-                                                     A[pre + ".relu1"].shape[1:3], 1, 1))
+                                                     A[pre + ".relu1"].shape[1:3], 1, 1),
+            el=el_d(G[gp + ".dc2"], W[pre + ".conv2.weight"], A[pre + ".relu1"].shape[1:3], 1, 1))
         np.testing.assert_array_equal(G[gp + ".dz1"][sel], np.where(A[pre + ".relu1"] > 0, G[gp + ".da1"], 0)[sel])
         dc1, dg1, db1 = _bn_bwd(G[gp + ".dz1"], A[pre + ".conv1"], P[pre + ".bn1.weight"], rnd)
-        chk(gp + ".dc1", G[gp + ".dc1"], dc1)
+        chk(gp + ".dc1", G[gp + ".dc1"], dc1, el=el_bnb(G[gp + ".dz1"], A[pre + ".conv1"], P[pre + ".bn1.weight"]))
         chk(pre + ".bn1.weight.grad", grads[pre + ".bn1.weight"], dg1, 1e-3)
         if perturbed:
             chk(pre + ".bn1.bias.grad", grads[pre + ".bn1.bias"], db1, 1e-3)
@@ -240,21 +287,25 @@ def _teacher_forced(dtc, cuda, batch, hw=32, stages=(0, 1, 2, 3, 4), imgs=None, 
         dx = conv_d(G[gp + ".dc1"], W[pre + ".conv1.weight"], inp.shape[1:3], st, 1)
         if proj:
             ds, dgs, dbs = _bn_bwd(G[gp + ".dz"], A[pre + ".shortcut"], P[pre + ".shortcut.1.weight"], rnd)
-            chk(gp + ".ds", G[gp + ".ds"], ds)
+            chk(gp + ".ds", G[gp + ".ds"], ds, el=el_bnb(G[gp + ".dz"], A[pre + ".shortcut"], P[pre + ".shortcut.1.weight"]))
             chk(pre + ".shortcut.1.weight.grad", grads[pre + ".shortcut.1.weight"], dgs, 1e-3)
             if perturbed:
                 chk(pre + ".shortcut.1.bias.grad", grads[pre + ".shortcut.1.bias"], dbs, 1e-3)
             chk(pre + ".shortcut.0.weight.grad", O.kcrs_to_krsc(grads[pre + ".shortcut.0.weight"]),
                 O.conv2d_wgrad(inp, G[gp + ".ds"], 1, 1, st, 0), F32)
             chk(gp + ".dxs", G[gp + ".dxs"][sel], conv_d(G[gp + ".ds"], W[pre + ".shortcut.0.weight"],
-                                                         inp.shape[1:3], st, 0))
-            chk(gp + ".dx", G[gp + ".dx"][sel], dx + G[gp + ".dxs"][sel])
+                                                         inp.shape[1:3], st, 0),
+                el=el_d(G[gp + ".ds"], W[pre + ".shortcut.0.weight"], inp.shape[1:3], st, 0))
+            # (a capture-enabled executor adds the stored bf16 dxs as conv1's dgrad residual: no fused shortcut)
+            chk(gp + ".dx", G[gp + ".dx"][sel], dx + G[gp + ".dxs"][sel],
+                el=el_d(G[gp + ".dc1"], W[pre + ".conv1.weight"], inp.shape[1:3], st, 1, res=G[gp + ".dxs"][sel]))
         else:
-            chk(gp + ".dx", G[gp + ".dx"][sel], dx + G[gp + ".dz"][sel])
+            chk(gp + ".dx", G[gp + ".dx"][sel], dx + G[gp + ".dz"][sel],
+                el=el_d(G[gp + ".dc1"], W[pre + ".conv1.weight"], inp.shape[1:3], st, 1, res=G[gp + ".dz"][sel]))
     if 0 in stages:
         np.testing.assert_array_equal(G["grad.stem.dz"], np.where(A["stem.out"] > 0, G["grad.layer1.0.dx"], 0))
         dc0, dg0, db0 = _bn_bwd(G["grad.stem.dz"], A["stem.conv"], P["bn1.weight"], rnd)
-        chk("grad.stem.dc", G["grad.stem.dc"], dc0)
+        chk("grad.stem.dc", G["grad.stem.dc"], dc0, el=el_bnb(G["grad.stem.dz"], A["stem.conv"], P["bn1.weight"]))
         chk("bn1.weight.grad", grads["bn1.weight"], dg0, 1e-3)
         if perturbed:
             chk("bn1.bias.grad", grads["bn1.bias"], db0, 1e-3)
@@ -265,6 +316,16 @@ def _teacher_forced(dtc, cuda, batch, hw=32, stages=(0, 1, 2, 3, 4), imgs=None, 
     print(f"teacher-forced {precision} B={batch} {hw}x{hw} stages={stages}: {len(errs)} checks, worst {worst[0]} "
           f"{worst[1][0]:.2e} (tol {worst[1][1]:.0e})")
     assert not bad, f"per-layer parity failures: {bad}"
+    if ratios:
+        wr = max(ratios.items(), key=lambda kv: kv[1])
+        fam = {f: max((v for k, v in ratios.items() if sel_(k)), default=0.0) for f, sel_ in (
+            ("conv fwd", lambda k: not k.startswith("grad.") and (".conv" in k or k.endswith(".shortcut"))),
+            ("bn apply", lambda k: k.endswith((".out", ".relu1"))),
+            ("conv dgrad", lambda k: k.endswith((".da1", ".dxs", ".dx"))),
+            ("bn bwd", lambda k: k.endswith((".dc2", ".dc1", ".ds", ".dc"))))}
+        print(f"teacher-forced {precision} B={batch} {hw}x{hw} stages={stages}: {len(ratios)} element-wise checks, worst "
+              f"|err|/tol {wr[1]:.3f} ({wr[0]}); " + ", ".join(f"{f} {v:.3f}" for f, v in fam.items()))
+    assert not el_bad, "element-wise bound failures:\n" + "\n".join(el_bad)
     if perturbed:
         _check_bn_state_after(sd, sd_after, A, stages)
     if eval_after:
