@@ -17,7 +17,7 @@ from .amp import GradScaler, autocast  # noqa: F401
 from .nn import (BasicBlock, CrossEntropyLoss, EvalResult, MixedTarget, ResNet, ResNet18,  # noqa: F401
                  SyncBatchNorm)
 from . import optim  # noqa: F401
-from .optim import SGD, Adam, AdamW, clip_grad_norm_  # noqa: F401
+from .optim import LARS, SGD, Adam, AdamW, clip_grad_norm_  # noqa: F401
 from .parallel import DDP, Comm, DataParallel, DistributedDataParallel, barrier  # noqa: F401
 from . import parallel  # noqa: F401
 from . import trainer  # noqa: F401

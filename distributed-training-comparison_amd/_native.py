@@ -55,6 +55,16 @@ class EvalRecord(C.Structure):
     _fields_ = [("loss", C.c_float), ("n", C.c_int32), ("top1", C.c_int32), ("topk", C.c_int32)]
 
 
+class Seg(C.Structure):
+    """dtc_seg: one parameter tensor of the flat buffers (flags bit 0 = ADAPT)."""
+
+    _fields_ = [("offset", C.c_int64), ("numel", C.c_int64), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+PSeg = C.POINTER(Seg)
+SEG_ADAPT = 1
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "dtc_abi_version": (i32, []),
@@ -106,6 +116,14 @@ _SIGS = {
     "dtc_adam_flat": (i32, [vp, vp, vp, vp, vp, i64, vp, f64, f64, f64, f64, f64, i32, vp, vp, vp]),
     "dtc_grad_norm_workspace_bytes": (sz, [i64]),
     "dtc_grad_norm_clip": (i32, [vp, i64, vp, f64, vp, vp, vp, vp]),
+    "dtc_segplan_create": (i32, [C.POINTER(vp), PSeg, i32]),
+    "dtc_segplan_destroy": (i32, [vp]),
+    "dtc_segplan_num_segments": (i32, [vp]),
+    "dtc_segplan_chunk_elems": (i64, []),
+    "dtc_segplan_device_bytes": (sz, [vp]),
+    "dtc_segplan_bind": (i32, [vp, vp, sz, vp]),
+    "dtc_seg_norms": (i32, [vp, vp, vp, vp, vp, vp]),
+    "dtc_lars_flat": (i32, [vp, vp, vp, vp, vp, f64, f64, f64, i32, f64, f64, i32, vp, vp, vp, vp]),
     "dtc_cast_f32_bf16": (i32, [vp, vp, i64, vp]),
     "dtc_amp_scale": (i32, [vp, vp, vp, i64, vp]),
     "dtc_amp_check_finite": (i32, [vp, i64, vp, vp]),

@@ -494,6 +494,30 @@ int dtc_grad_norm_clip(const float* g, int64_t n, const float* inv_scale, double
                        float* total_norm, float* grad_mult, void* stream) {
   return grad_norm_clip(g, n, inv_scale, max_norm, workspace, total_norm, grad_mult, S(stream));
 }
+static_assert(sizeof(dtc_seg) == sizeof(SegDesc) && offsetof(dtc_seg, numel) == offsetof(SegDesc, numel) &&
+                  offsetof(dtc_seg, flags) == offsetof(SegDesc, flags) &&
+                  offsetof(dtc_seg, reserved) == offsetof(SegDesc, reserved),
+              "dtc_seg is SegDesc");
+int dtc_segplan_create(dtc_segplan** out, const dtc_seg* segs, int nseg) {
+  GUARD(return segplan_create((SegPlan**)out, (const SegDesc*)segs, nseg);)
+}
+int dtc_segplan_destroy(dtc_segplan* plan) { return segplan_destroy((SegPlan*)plan); }
+int dtc_segplan_num_segments(const dtc_segplan* plan) { return segplan_num_segments((const SegPlan*)plan); }
+int64_t dtc_segplan_chunk_elems(void) { return segplan_chunk_elems(); }
+size_t dtc_segplan_device_bytes(const dtc_segplan* plan) { return segplan_device_bytes((const SegPlan*)plan); }
+int dtc_segplan_bind(dtc_segplan* plan, void* dev, size_t bytes, void* stream) {
+  return segplan_bind((SegPlan*)plan, dev, bytes, S(stream));
+}
+int dtc_seg_norms(dtc_segplan* plan, const float* p, const float* g, const float* gmul, float* seg_out,
+                  void* stream) {
+  return seg_norms((SegPlan*)plan, p, g, gmul, seg_out, S(stream));
+}
+int dtc_lars_flat(dtc_segplan* plan, float* p, const float* g, float* mom, uint16_t* pb, double lr, double wd,
+                  double mu, int nesterov, double trust_coef, double eps, int trust_clip, const float* inv_scale,
+                  const int* found_inf, float* seg_out, void* stream) {
+  return lars_flat((SegPlan*)plan, p, g, mom, pb, lr, wd, mu, nesterov, trust_coef, eps, trust_clip, inv_scale,
+                   found_inf, seg_out, S(stream));
+}
 int dtc_cast_f32_bf16(const float* src, uint16_t* dst, int64_t n, void* stream) {
   return cast_f32_bf16(src, dst, n, S(stream));
 }

@@ -390,6 +390,28 @@ int adam_flat(float* p, const float* g, float* m, float* v, u16* p_bf16, int64_t
 size_t grad_norm_workspace_bytes(int64_t n);
 int grad_norm_clip(const float* g, int64_t n, const float* inv_scale, double max_norm, void* workspace,
                    float* total_norm, float* grad_mult, hipStream_t st);
+// Segment plan (lars.hip): where each parameter tensor lies in the flat buffers. The handle holds host data only
+// (the validated table and the chunk -> segment work map); bind uploads both into caller-owned device memory of
+// segplan_device_bytes() bytes (tables, one partial slot of two doubles per chunk, per-segment results).
+struct SegDesc {  // layout of the ABI's dtc_seg
+  int64_t offset, numel;
+  int32_t flags, reserved;  // flags bit 0: ADAPT (trust ratio and weight decay apply)
+};
+struct SegPlan;
+int64_t segplan_chunk_elems();
+int segplan_create(SegPlan** out, const SegDesc* segs, int nseg);
+int segplan_destroy(SegPlan* plan);
+int segplan_num_segments(const SegPlan* plan);
+size_t segplan_device_bytes(const SegPlan* plan);
+int segplan_bind(SegPlan* plan, void* dev, size_t bytes, hipStream_t st);
+// seg_out[s] (optional, fp32 [nseg][3]) = (||p_s||, |*gmul| * ||g_s||, ratio_s); double sums in a fixed order. Two
+// launches. Here ratio_s is the bare norm ratio ||p_s|| / (|*gmul| ||g_s||) of an ADAPT segment (1 where a norm is
+// zero and for the others); lars_flat writes the trust ratio it applied.
+int seg_norms(SegPlan* plan, const float* p, const float* g, const float* gmul, float* seg_out, hipStream_t st);
+// LARS over the plan's segments: the norm pass, the ratios, the momentum update with the bf16 shadow. Three launches.
+int lars_flat(SegPlan* plan, float* p, const float* g, float* mom, u16* p_bf16, double lr, double wd, double mu,
+              int nesterov, double trust_coef, double eps, int trust_clip, const float* inv_scale,
+              const int* found_inf, float* seg_out, hipStream_t st);
 int cast_f32_bf16(const float* src, u16* dst, int64_t n, hipStream_t st);
 // zero an 8-byte aligned range (a kernel node, unlike hipMemsetAsync's fill dispatch)
 int zero_bytes(void* p, size_t bytes, hipStream_t st);

@@ -11,7 +11,7 @@ import ctypes as C
 
 import torch
 
-from ._native import ConvDesc, NativeError, call, lib, ptr, require_cuda, stream_ptr
+from ._native import SEG_ADAPT, ConvDesc, NativeError, Seg, call, lib, ptr, require_cuda, stream_ptr
 
 
 
@@ -499,6 +499,84 @@ def grad_norm_clip(g, max_norm, inv_scale=None, workspace=None, total_norm=None,
     call("dtc_grad_norm_clip", ptr(g), g.numel(), ptr(inv_scale), float(max_norm), ptr(workspace), ptr(total_norm),
          ptr(grad_mult), stream_ptr())
     return total_norm, grad_mult
+
+
+class SegPlan:
+    """A segment plan (dtc_segplan) with the device memory it is bound to. `names` follow the segments, which are
+    in offset order; `end` is the first element past the last segment (the least size of a flat buffer)."""
+
+    def __init__(self, segments, names=None, device=None):
+        segments = [(int(o), int(n), bool(a)) for o, n, a in segments]
+        table = (Seg * max(1, len(segments)))(*[Seg(o, n, SEG_ADAPT if a else 0, 0) for o, n, a in segments])
+        self.handle = C.c_void_p()
+        self._destroy = lib.dtc_segplan_destroy  # held here: module globals are gone at interpreter exit
+        call("dtc_segplan_create", C.byref(self.handle), table, len(segments))
+        self.nseg = len(segments)
+        self.names = list(names) if names is not None else [str(i) for i in range(self.nseg)]
+        self.segments = segments
+        self.end = segments[-1][0] + segments[-1][1]
+        self.mem = None
+        if device is not None:
+            self.bind(device)
+
+    def bind(self, device):
+        """Upload the tables into fresh device memory (the only copy: nothing is copied per step)."""
+        nbytes = lib.dtc_segplan_device_bytes(self.handle)
+        self.mem = torch.empty(nbytes, dtype=torch.uint8, device=device)  # the allocator aligns to 512 bytes
+        require_cuda(self.mem)
+        call("dtc_segplan_bind", self.handle, ptr(self.mem), nbytes, stream_ptr())
+
+    def __del__(self):
+        h, self.handle = getattr(self, "handle", None), None
+        if h:
+            self._destroy(h)
+
+
+def seg_plan(layout_or_segments, device=None) -> SegPlan:
+    """The segment plan of a model's Layout (one segment per parameter, ADAPT for those with more than one
+    dimension: conv and linear weights) or of a list of (offset, numel, adapt) triples in offset order, bound to
+    fresh memory on `device` (None: left unbound)."""
+    params = getattr(layout_or_segments, "params", None)
+    if params is None:
+        return SegPlan(layout_or_segments, None, device)
+    params = sorted(params, key=lambda q: q.offset)
+    return SegPlan([(q.offset, q.numel, len(q.shape) > 1) for q in params], [q.name for q in params], device)
+
+
+def _seg_check(plan, *flat):
+    require_cuda(*flat)
+    if plan.mem is None:
+        raise NativeError("the segment plan is not bound to a device (ops.seg_plan(..., device))")
+    for t in flat:
+        if t is not None and (t.numel() < plan.end or not t.is_contiguous() or t.device != plan.mem.device):
+            raise NativeError(f"flat buffers must be contiguous, on the plan's device and hold the plan's "
+                              f"{plan.end} elements, got {t.numel()} on {t.device}")
+
+
+def _seg_out(plan, out):
+    return _out(out, (plan.nseg, 3), torch.float32, plan.mem.device, "seg_out")
+
+
+def seg_norms(plan, p, g, gmul=None, out=None):
+    """Per-tensor L2 norms over flat buffers: fp32 [nseg, 3] = (||p_s||, |gmul| * ||g_s||, ||p_s|| / that) on the
+    device, double accumulation in a fixed order (bit-identical run to run), no host synchronisation."""
+    _seg_check(plan, p, g)
+    out = _seg_out(plan, out)
+    call("dtc_seg_norms", plan.handle, ptr(p), ptr(g), ptr(gmul), ptr(out), stream_ptr())
+    return out
+
+
+def lars_flat(plan, p, g, mom, pb, lr, weight_decay, momentum, nesterov=False, trust_coef=1e-3, eps=1e-8,
+              trust_clip=False, inv_scale=None, found_inf=None, seg_out=None):
+    """One LARS step over the plan's segments of the flat fp32 buffers (include/dtc.h: dtc_lars_flat), the bf16
+    shadow `pb` refreshed in the same pass. `seg_out` (optional fp32 [nseg, 3]) receives the norms and the trust
+    ratio of every segment."""
+    _seg_check(plan, p, g, mom, pb)
+    if seg_out is not None:
+        seg_out = _seg_out(plan, seg_out)
+    call("dtc_lars_flat", plan.handle, ptr(p), ptr(g), ptr(mom), ptr(pb), float(lr), float(weight_decay),
+         float(momentum), int(bool(nesterov)), float(trust_coef), float(eps), int(bool(trust_clip)), ptr(inv_scale),
+         ptr(found_inf), ptr(seg_out), stream_ptr())
 
 
 def cast_f32_bf16(src, dst):

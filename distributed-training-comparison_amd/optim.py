@@ -1,4 +1,4 @@
-"""optim.SGD / Adam / AdamW mirrors running fused flat-buffer kernels, and clip_grad_norm_.
+"""optim.SGD / Adam / AdamW mirrors and LARS running fused flat-buffer kernels, and clip_grad_norm_.
 
 Reference: ``optim.SGD(self.model.parameters(), lr, weight_decay, momentum=0.9, nesterov=True)``
 (src/ddp/trainer.py:92-98) stepped through ``GradScaler.step`` (trainer.py:158); the reference's README
@@ -145,6 +145,50 @@ class AdamW(Adam):
                          maximize=maximize)
 
 
+class LARS(_FlatOptimizer):
+    """LARS (You et al. 2017): SGD with momentum whose step is scaled per parameter tensor by the trust ratio
+    ``trust_coef * ||p|| / (||g|| + weight_decay * ||p|| + eps)``; with ``trust_clip`` (LARC's "clip" mode) by
+    ``min(ratio / lr, 1)``. The ratio and the weight decay apply to parameters with more than one dimension (conv
+    and linear weights); BatchNorm weights / biases and ``linear.bias`` take the plain momentum step. The norms are
+    recomputed on the device at every step (three launches, no host synchronisation, bit-reproducible)."""
+
+    def __init__(self, params, lr, momentum=0.9, weight_decay=0.0, nesterov=False, trust_coef=1e-3, eps=1e-8,
+                 trust_clip=False):
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= momentum < 1.0:
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if not 0.0 < trust_coef:
+            raise ValueError(f"Invalid trust_coef value: {trust_coef}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        defaults = dict(lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov,
+                        trust_coef=trust_coef, eps=eps, trust_clip=trust_clip)
+        super().__init__(params, defaults)
+        self._mom = self._plan = self._norms = None
+
+    def _init_state(self, flat):
+        self._mom = torch.zeros_like(flat.params)
+        self._plan = ops.seg_plan(flat.layout, flat.device)  # the handle keeps its device memory (plan.mem)
+        self._norms = torch.zeros(self._plan.nseg, 3, dtype=torch.float32, device=flat.device)
+
+    def _update(self, flat, g, grad_mult, found_inf):
+        ops.lars_flat(self._plan, flat.params, flat.grads, self._mom, flat.params_bf16, g["lr"], g["weight_decay"],
+                      g["momentum"], g["nesterov"], g["trust_coef"], g["eps"], g["trust_clip"], grad_mult, found_inf,
+                      self._norms)
+
+    def layer_norms(self):
+        """(norms, names): the last step's fp32 [n, 3] device tensor of (||p||, ||g|| of the unscaled, clipped
+        gradient, trust ratio applied) per parameter -- both norms taken before the update -- and the parameter
+        names, in flat-buffer order. No synchronisation: the tensor is the one the next step overwrites (clone to
+        keep)."""
+        if self._plan is None:
+            raise NativeError("LARS.layer_norms: no step has run yet")
+        return self._norms, self._plan.names
+
+
 def clip_grad_norm_(parameters, max_norm, norm_type=2.0, scaler=None) -> torch.Tensor:
     """torch.nn.utils.clip_grad_norm_ for a native model: one read pass over the flat gradient buffer and a
     tiny finalize, nothing leaves the GPU.
@@ -155,7 +199,7 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, scaler=None) -> torch.T
     tensor, without a host synchronisation.
 
     Deviation from torch: the gradients are NOT rewritten. The multiplier is stored on the model's
-    FlatState and the next ``step()`` of SGD / Adam / AdamW applies it where it would apply ``inv_scale``
+    FlatState and the next ``step()`` of SGD / Adam / AdamW / LARS applies it where it would apply ``inv_scale``
     (no extra read-modify-write pass over the gradients); ``p.grad`` keeps showing the unclipped values.
     """
     if float(norm_type) != 2.0:

@@ -22,7 +22,7 @@ import torch.distributed as dist
 from . import data as D
 from .amp import GradScaler, autocast
 from .nn import CrossEntropyLoss, ResNet18, SyncBatchNorm
-from .optim import SGD, Adam, AdamW, clip_grad_norm_
+from .optim import LARS, SGD, Adam, AdamW, clip_grad_norm_
 from .parallel import DDP, DataParallel, barrier
 
 
@@ -51,8 +51,16 @@ def load_config(argv=None, mode: str = "ddp"):
     p.add_argument("--lr-decay-step-size", type=int, default=60)
     p.add_argument("--lr-decay-gamma", type=float, default=0.1)
     # not in the reference, whose README suggests the experiment ("e.g. using ADAM optimizer")
-    p.add_argument("--optimizer", type=str, default="sgd", choices=("sgd", "adam", "adamw"),
-                   help="fused flat-buffer optimizer; --lr and --weight-decay pass through")
+    p.add_argument("--optimizer", type=str, default="sgd", choices=("sgd", "adam", "adamw", "lars"),
+                   help="fused flat-buffer optimizer; --lr and --weight-decay pass through (lars: the sgd branch's "
+                        "momentum 0.9 + Nesterov with a per-tensor trust ratio, for large global batches)")
+    p.add_argument("--lars-trust-coef", type=float, default=1e-3,
+                   help="--optimizer lars: ratio = coef * ||p|| / (||g|| + weight_decay * ||p|| + eps)")
+    p.add_argument("--lars-clip", action="store_true", default=False,
+                   help="--optimizer lars: LARC clipping, ratio = min(ratio / lr, 1)")
+    p.add_argument("--warmup-epochs", type=int, default=0,
+                   help="linear warm-up: epoch e < N runs at lr * (e + 1) / N and StepLR's count starts at epoch N "
+                        "(0 = off: the reference's plain StepLR)")
     p.add_argument("--clip-grad-norm", type=float, default=0.0,
                    help="clip the global gradient L2 norm to this value before each step (0 = off)")
     # not in the reference either: the regularizers people change first at larger global batches
@@ -82,6 +90,8 @@ def load_config(argv=None, mode: str = "ddp"):
         p.error("--label-smoothing must be in [0, 1]")
     if h.mixup_alpha < 0 or h.cutmix_alpha < 0 or not 0.0 <= h.mix_prob <= 1.0:
         p.error("--mixup-alpha / --cutmix-alpha must be >= 0 and --mix-prob in [0, 1]")
+    if h.warmup_epochs < 0 or not h.lars_trust_coef > 0:
+        p.error("--warmup-epochs must be >= 0 and --lars-trust-coef > 0")
     if (h.mixup_alpha > 0 or h.cutmix_alpha > 0) and not h.device_data:
         p.error("--mixup-alpha / --cutmix-alpha need --device-data (the host loader does not mix)")
     return h
@@ -127,6 +137,18 @@ def mix_kwargs(hparams) -> dict:
     if ma <= 0 and ca <= 0:
         return {}
     return {"mixup_alpha": ma, "cutmix_alpha": ca, "mix_prob": float(getattr(hparams, "mix_prob", 1.0))}
+
+
+def make_scheduler(optimizer, hparams):
+    """The per-epoch learning-rate schedule. Without --warmup-epochs: the reference's StepLR (trainer.py:101-105),
+    the same object as ever. With N warm-up epochs: epoch e < N runs at lr * (e + 1) / N, and from epoch N on
+    StepLR's rule counted from there, lr * gamma ** ((e - N) // step_size). Host-only: every optimizer passes its
+    lr to the kernel per launch."""
+    n, step, gamma = int(getattr(hparams, "warmup_epochs", 0)), hparams.lr_decay_step_size, hparams.lr_decay_gamma
+    if n <= 0:
+        return torch.optim.lr_scheduler.StepLR(optimizer, step_size=step, gamma=gamma)
+    return torch.optim.lr_scheduler.LambdaLR(
+        optimizer, lambda e: (e + 1) / n if e < n else gamma ** ((e - n) // step))
 
 
 class Trainer:
@@ -206,12 +228,13 @@ class Trainer:
         if h.optimizer == "sgd":
             optimizer = SGD(self.model.parameters(), lr=h.lr, weight_decay=h.weight_decay,
                             momentum=0.9, nesterov=True)                                  # trainer.py:92-98
+        elif h.optimizer == "lars":  # the sgd branch plus the trust ratio
+            optimizer = LARS(self.model.parameters(), lr=h.lr, weight_decay=h.weight_decay, momentum=0.9,
+                             nesterov=True, trust_coef=h.lars_trust_coef, trust_clip=h.lars_clip)
         else:
             cls = {"adam": Adam, "adamw": AdamW}[h.optimizer]
             optimizer = cls(self.model.parameters(), lr=h.lr, weight_decay=h.weight_decay)
-        scheduler = torch.optim.lr_scheduler.StepLR(optimizer, step_size=self.hparams.lr_decay_step_size,
-                                                    gamma=self.hparams.lr_decay_gamma)    # trainer.py:101-105
-        return optimizer, scheduler
+        return optimizer, make_scheduler(optimizer, h)
 
     def save_checkpoint(self, epoch: int, val_acc: float, model) -> None:
         logging.info(f"Val acc increased ({self.global_top1_acc:.4f} -> {val_acc:.4f}). Saving model ...")

@@ -276,6 +276,51 @@ int dtc_adam_flat(float* p, const float* g, float* exp_avg, float* exp_avg_sq, u
 size_t dtc_grad_norm_workspace_bytes(int64_t n);
 int dtc_grad_norm_clip(const float* g, int64_t n, const float* inv_scale, double max_norm, void* workspace,
                        float* total_norm, float* grad_mult, void* stream);
+/* Segment plan: where each parameter tensor lies in the flat buffers (p, g, optimizer state and the bf16 shadow
+ * share one layout), for the per-tensor reductions and LARS below. Segments are given in strictly increasing,
+ * non-overlapping order; offset is a non-negative multiple of 4 elements, numel >= 1 (any value: linear.bias with
+ * 10 classes has 10 elements), flags bit 0 = ADAPT (the trust ratio and weight decay apply; clear for BatchNorm
+ * weights / biases and linear.bias), every other flag bit and `reserved` zero, 1 <= nseg <= 4096. Anything else:
+ * DTC_EINVAL and *out = NULL. dtc_segplan_create is pure host code (no device call): the handle holds the table and
+ * the work map derived from it, one entry per chunk of dtc_segplan_chunk_elems() elements of one segment.
+ * dtc_segplan_device_bytes: the device memory the plan wants (the two tables, one partial slot of two doubles per
+ * chunk, the per-segment results), a multiple of 16. dtc_segplan_bind uploads the tables into such a region (16-byte
+ * aligned, caller-owned, to be kept until the plan is destroyed or bound elsewhere), enqueued on `stream`: once per
+ * model, the only copy -- nothing is copied per step. A plan serves one stream at a time (its slots are reused). */
+typedef struct { int64_t offset, numel; int32_t flags; int32_t reserved; } dtc_seg; /* flags bit 0: ADAPT */
+#define DTC_SEG_ADAPT 1
+typedef struct dtc_segplan dtc_segplan;
+int dtc_segplan_create(dtc_segplan** out, const dtc_seg* segs_host, int nseg);
+int dtc_segplan_destroy(dtc_segplan* plan);
+int dtc_segplan_num_segments(const dtc_segplan* plan);
+int64_t dtc_segplan_chunk_elems(void);
+size_t dtc_segplan_device_bytes(const dtc_segplan* plan);
+int dtc_segplan_bind(dtc_segplan* plan, void* dev, size_t bytes, void* stream);
+/* Per-tensor L2 norms of p and g (16-byte aligned flat buffers covering every segment): seg_out (optional, device
+ * fp32 [nseg][3]) = (||p_s||, |mult| * ||g_s||, ratio_s) with mult = *gmul (NULL: 1). Squares are summed in double
+ * in a fixed order -- per thread in index order, a butterfly over the wave, the waves in index order, one slot per
+ * chunk, the slots in index order -- so the result is bit-identical from run to run; each norm is rounded to fp32
+ * once. Elements outside the segments are not read. Here ratio_s is the bare ||p_s|| / (|mult| ||g_s||) of an ADAPT
+ * segment, and 1 where a norm is zero and for the other segments. Two launches, no host synchronisation. */
+int dtc_seg_norms(dtc_segplan* plan, const float* p, const float* g, const float* gmul, float* seg_out, void* stream);
+/* lars: LARS (You et al. 2017) = SGD with momentum whose step is scaled per tensor by a trust ratio; with
+ * momentum 0.9 and nesterov it is the reference's optimizer (trainer.py:92-98) plus that ratio. With mult =
+ * *inv_scale (NULL: 1; GradScaler's 1/scale or dtc_grad_norm_clip's grad_mult), for every segment s:
+ *   wn = ||p_s||, gn = |mult| * ||g_s||                                       (as dtc_seg_norms)
+ *   ADAPT:      ratio = trust_coef * wn / (gn + weight_decay * wn + eps), with trust_clip != 0 (LARC's "clip" mode)
+ *               min(ratio / lr, 1); ratio = 1 when wn or gn is zero; rounded once to fp32;
+ *               d = (g * mult + weight_decay * p) * ratio
+ *   otherwise:  ratio = 1 and no weight decay;  d = g * mult
+ *   buf = momentum * buf + d ;  u = nesterov ? d + momentum * buf : buf ;  p -= lr * u ;  p_bf16 = bf16(p)
+ * The whole step is skipped when *found_inf != 0 (NULL: never): p, momentum_buf and p_bf16 stay bit-unchanged.
+ * Elements outside the segments are neither read nor written. The norms are recomputed from the buffers at every
+ * call. seg_out (optional) as for dtc_seg_norms, ratio_s being the ratio applied. Three launches (norm pass, ratios,
+ * update), no host synchronisation, no floating-point atomics, bit-identical from run to run. Requires lr,
+ * weight_decay, eps >= 0, momentum in [0, 1), trust_coef > 0, lr > 0 with trust_clip; p, g, momentum_buf 16-byte
+ * aligned, p_bf16 8-byte aligned; a bound plan. */
+int dtc_lars_flat(dtc_segplan* plan, float* p, const float* g, float* momentum_buf, uint16_t* p_bf16, double lr,
+                  double weight_decay, double momentum, int nesterov, double trust_coef, double eps, int trust_clip,
+                  const float* inv_scale, const int* found_inf, float* seg_out, void* stream);
 int dtc_cast_f32_bf16(const float* src, uint16_t* dst, int64_t n, void* stream);
 int dtc_amp_check_finite(const float* g, int64_t n, int* found_inf, void* stream);
 /* GradScaler.scale(loss): out = x * (*scale) with the scale device-resident (no host sync) */

@@ -1,17 +1,20 @@
-"""Optimizer-stage timing: adam_flat against sgd_nesterov, grad_norm_clip against amp_check_finite, and the
-training step with AdamW + clip against SGD.
+"""Optimizer-stage timing: adam_flat and lars_flat against sgd_nesterov, grad_norm_clip against amp_check_finite,
+and the training step with AdamW + clip and with LARS against SGD.
 
     python tools/optim_bench.py [--reps 20] [--inner 20] [--steps 40] [--batch 256] [--out FILE]
 
 Kernels: the model's own flat buffers (11.22 M parameters + slot padding). After a warm-up of every kernel,
 each repetition times `inner` back-to-back launches of one kernel between two device events, and the
 repetitions of the kernels of a pair ALTERNATE, so both see the same machine state. Bytes per element by the
-algorithm: sgd 5 x 4 + 2 = 22 B, adam 7 x 4 + 2 = 30 B, the two read passes 4 B. adam_flat's time includes
-its one-thread tick launch, grad_norm_clip's its finalize launch (what a step pays).
+algorithm: sgd 5 x 4 + 2 = 22 B, adam 7 x 4 + 2 = 30 B, lars sgd's 22 B + the norm pass's 8 B = 30 B, seg_norms
+(lars_flat's first two launches on their own: the norm pass over p and g and the ratios) 8 B, the two read passes
+4 B. adam_flat's time includes its one-thread tick launch, lars_flat's all three of its launches, grad_norm_clip's
+its finalize launch (what a step pays).
 
 Step: bench.py's single-GPU loop body (autocast forward + CrossEntropy, scaler.scale(loss).backward(),
-scaler.step, scaler.update, loss.item()) at batch 256, bf16, once with SGD and once with AdamW +
-unscale_ + clip_grad_norm_, `steps` steps each in alternating blocks. Prints one JSON line."""
+scaler.step, scaler.update, loss.item()) at batch 256, bf16, with SGD, with AdamW + unscale_ + clip_grad_norm_
+and with LARS (the SGD arm's hyper-parameters plus the trust ratio), `steps` steps each in alternating blocks.
+Prints one JSON line."""
 import argparse
 import json
 import os
@@ -57,12 +60,17 @@ def main():
     inv = torch.ones(1, device=dev)
     ws = ops.grad_norm_workspace(n, dev)
     tn, gm = torch.empty(1, device=dev), torch.empty(1, device=dev)
+    plan = ops.seg_plan(flat.layout, dev)
+    seg_out = torch.empty(plan.nseg, 3, device=dev)
 
     kernels = {
         "sgd_nesterov": (lambda: ops.sgd_nesterov_flat(flat.params, flat.grads, mom, flat.params_bf16, 1e-3, 1e-4, 0.9,
                                                        inv, found), 22),
         "adam_flat": (lambda: ops.adam_flat(flat.params, flat.grads, m, v, flat.params_bf16, state, 1e-3, 0.9, 0.999,
                                             1e-8, 1e-2, True, inv, found), 30),
+        "lars_flat": (lambda: ops.lars_flat(plan, flat.params, flat.grads, mom, flat.params_bf16, 1e-3, 1e-4, 0.9, True,
+                                            1e-3, 1e-8, False, inv, found, seg_out), 30),
+        "seg_norms": (lambda: ops.seg_norms(plan, flat.params, flat.grads, inv, seg_out), 8),
         "amp_check_finite": (lambda: ops.amp_check_finite(flat.grads, found), 4),
         "grad_norm_clip": (lambda: ops.grad_norm_clip(flat.grads, 1.0, inv, ws, tn, gm), 4),
     }
@@ -81,7 +89,7 @@ def main():
             fn()
     torch.cuda.synchronize()
     times = {k: [] for k in kernels}
-    for pair in (("sgd_nesterov", "adam_flat"), ("amp_check_finite", "grad_norm_clip")):
+    for pair in (("sgd_nesterov", "adam_flat", "lars_flat", "seg_norms"), ("amp_check_finite", "grad_norm_clip")):
         for _ in range(a.reps):
             for k in pair:
                 times[k].append(timed(kernels[k][0]))
@@ -96,20 +104,24 @@ def main():
         line["kernels"][k] = s
     ks = line["kernels"]
     line["adam_over_sgd_bandwidth"] = ks["adam_flat"]["TBps_median"] / ks["sgd_nesterov"]["TBps_median"]
+    line["lars_over_sgd_bandwidth"] = ks["lars_flat"]["TBps_median"] / ks["sgd_nesterov"]["TBps_median"]
+    line["lars_over_adam_time"] = ks["lars_flat"]["median_ms"] / ks["adam_flat"]["median_ms"]
     line["norm_over_check_bandwidth"] = ks["grad_norm_clip"]["TBps_median"] / ks["amp_check_finite"]["TBps_median"]
 
     if not a.no_step:
-        del model, flat, mom, m, v
+        del model, flat, mom, m, v, plan
         templates = dtc.data.class_templates(100, 32, 32)
         pool = [tuple(t.contiguous() for t in dtc.data.synthetic_batch(i, a.batch, 32, 32, 100, dev, templates))
                 for i in range(4)]
         crit = dtc.CrossEntropyLoss()
         runs = {}
-        for name in ("sgd", "adamw_clip"):
+        for name in ("sgd", "adamw_clip", "lars"):
             torch.manual_seed(42)
             net = dtc.ResNet18().to(dev)
             if name == "sgd":
                 opt = dtc.SGD(net.parameters(), lr=0.1, weight_decay=1e-4, momentum=0.9, nesterov=True)
+            elif name == "lars":
+                opt = dtc.LARS(net.parameters(), lr=0.1, weight_decay=1e-4, momentum=0.9, nesterov=True)
             else:
                 opt = dtc.AdamW(net.parameters(), lr=1e-3, weight_decay=1e-2)
             runs[name] = (net, opt, dtc.GradScaler())
@@ -146,6 +158,7 @@ def main():
                         "last_loss": last, **{k: _stats(v) for k, v in step_ms.items()}}
         line["step"]["adamw_clip_over_sgd"] = (line["step"]["adamw_clip"]["median_ms"] /
                                                line["step"]["sgd"]["median_ms"])
+        line["step"]["lars_over_sgd"] = line["step"]["lars"]["median_ms"] / line["step"]["sgd"]["median_ms"]
     text = json.dumps(line)
     print(text, flush=True)
     if a.out:
