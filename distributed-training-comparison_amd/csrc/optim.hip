@@ -13,6 +13,8 @@
 
 namespace dtc {
 
+static bool aligned16(const void* a) { return ((uintptr_t)a & 15) == 0; }
+
 __global__ void __launch_bounds__(256) sgd_nesterov_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                           float* __restrict__ m, u16* __restrict__ pb, int64_t n4,
                                                           float lr, float wd, float mu,
@@ -40,6 +42,8 @@ __global__ void __launch_bounds__(256) sgd_nesterov_kernel(float* __restrict__ p
 int sgd_nesterov(float* p, const float* g, float* mom, u16* p_bf16, int64_t n, float lr, float wd, float mu,
                  const float* inv_scale, const int* found_inf, hipStream_t st) {
   DTC_CHECK_ARG(p && g && mom && p_bf16 && n > 0 && (n % 4) == 0, "sgd_nesterov: bad args (n=%lld)", (long long)n);
+  DTC_CHECK_ARG(aligned16(p) && aligned16(g) && aligned16(mom) && ((uintptr_t)p_bf16 & 7) == 0,
+                "sgd_nesterov: p, g and momentum must be 16-byte aligned, p_bf16 8-byte aligned");
   const int64_t n4 = n / 4;
   const int blocks = (int)std::min<int64_t>(2048, (n4 + 255) / 256);
   DTC_KLAUNCH(sgd_nesterov_kernel, dim3(blocks), dim3(256), 0, st, p, g, mom, p_bf16, n4, lr, wd, mu, inv_scale,
@@ -121,8 +125,6 @@ __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, const 
     *(uint2*)(pb + i * 4) = w;
   }
 }
-
-static bool aligned16(const void* a) { return ((uintptr_t)a & 15) == 0; }
 
 int adam_flat(float* p, const float* g, float* m, float* v, u16* p_bf16, int64_t n, void* state, double lr,
               double beta1, double beta2, double eps, double wd, int decoupled, const float* inv_scale,

@@ -366,25 +366,34 @@ def stem_pack_weight(w27):
     return w64
 
 
-def head_fwd(act, wfc, bfc):
-    """act [N,h,w,C] bf16, wfc [ncls,C] bf16, bfc [ncls] fp32 -> (feat fp32 [N,C], logits fp32 [N,ncls])."""
+def head_fwd(act, wfc, bfc, out=None):
+    """act [N,h,w,C] bf16, wfc [ncls,C] bf16, bfc [ncls] fp32 -> (feat fp32 [N,C], logits fp32 [N,ncls]);
+    `out`: a (feat, logits) pair to write instead of fresh tensors."""
+    require_cuda(act, wfc, bfc)
     n, h, w, c = act.shape
     ncls = wfc.shape[0]
-    feat = torch.empty(n, c, dtype=torch.float32, device=act.device)
-    logits = torch.empty(n, ncls, dtype=torch.float32, device=act.device)
+    o = out if out is not None else (None, None)
+    feat = _out(o[0], (n, c), torch.float32, act.device, "head_fwd")
+    logits = _out(o[1], (n, ncls), torch.float32, act.device, "head_fwd")
     call("dtc_head_fwd", ptr(act), n, h * w, c, ptr(wfc), ptr(bfc), ncls, ptr(feat), ptr(logits), stream_ptr())
     return feat, logits
 
 
-def head_bwd(dlogits, feat, wfc, hw, scale=1.0):
+def head_bwd(dlogits, feat, wfc, hw, scale=1.0, out=None, workspace=None):
+    """dlogits [N,ncls] fp32, feat [N,C] fp32, wfc [ncls,C] bf16 -> (dw fp32 [ncls,C], db fp32 [ncls], dact bf16
+    [N,h,w,C]); `out`: a (dw, db, dact) triple, `workspace`: at least dtc_head_bwd_workspace_size bytes (the
+    default is exactly that many)."""
+    require_cuda(dlogits, feat, wfc)
     n, c = feat.shape
     ncls = wfc.shape[0]
-    dw = torch.empty(ncls, c, dtype=torch.float32, device=feat.device)
-    db = torch.empty(ncls, dtype=torch.float32, device=feat.device)
     h, w = hw
-    dact = torch.empty(n, h, w, c, dtype=torch.bfloat16, device=feat.device)
+    o = out if out is not None else (None, None, None)
+    dw = _out(o[0], (ncls, c), torch.float32, feat.device, "head_bwd")
+    db = _out(o[1], (ncls,), torch.float32, feat.device, "head_bwd")
+    dact = _out(o[2], (n, h, w, c), torch.bfloat16, feat.device, "head_bwd")
     nb = lib.dtc_head_bwd_workspace_size(n, c, ncls)
-    ws = torch.empty(nb // 4 + 1, dtype=torch.float32, device=feat.device)
+    ws = _given_ws(workspace, nb) if workspace is not None else \
+        torch.empty(nb // 4, dtype=torch.float32, device=feat.device)
     call("dtc_head_bwd", ptr(dlogits), ptr(feat), ptr(wfc), n, h * w, c, ncls, float(scale), ptr(dw), ptr(db),
          ptr(dact), ptr(ws), nb, stream_ptr())
     return dw, db, dact

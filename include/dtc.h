@@ -245,6 +245,7 @@ int dtc_eval_metrics(const float* logits, const int64_t* labels, int n, int ncls
  * sgd: optim.SGD(lr, weight_decay, momentum, nesterov=True).step() (trainer.py:92-98, 158) over a
  * flat fp32 buffer; grads are multiplied by *inv_scale (GradScaler.unscale_) and the step is skipped
  * when *found_inf != 0 (GradScaler.step); p_bf16 receives the bf16 shadow of the new parameters.
+ * p, g and momentum_buf 16-byte aligned, p_bf16 8-byte aligned, n a positive multiple of 4 (else DTC_EINVAL).
  * amp: GradScaler's _amp_foreach_non_finite_check_and_unscale_ / _amp_update_scale_ (main.py:25). */
 int dtc_sgd_nesterov_flat(float* p, const float* g, float* momentum_buf, uint16_t* p_bf16, int64_t n, float lr,
                           float weight_decay, float momentum, const float* inv_scale, const int* found_inf,

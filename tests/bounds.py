@@ -32,6 +32,23 @@ T = |a| * (|dz| + |mean(dz)| + invstd * (|x| + |mean|) * mean(|dz * xhat|)), d =
 roundings in the chain, doubled).
 
 Head dact: d = 2 * ncls * U * (|dlogits| @ |W|) / HW.
+
+Head pool: feat = bf16(mean_p act). HW - 1 fp32 adds in any order plus the divide: d = (HW + 1) * U * mean_p |act|
+against the float64 mean; bound tol(ref, d) (fp32 executor: no rounding of the result, bound d).
+
+Head Linear: logits = bf16(feat . W[j] + bf16(b[j])) from the kernel's own feat (exact bf16 values), the products
+and the bias summed in fp32 in any order: S = |feat| @ |W|.T + |bf16(b)|, d = 2 * (C + 1) * U * S (the dot-product
+bound of C + 1 terms, doubled as CONV_FACTOR is); bound tol(ref, d). fp32 executor: b unrounded, bound d.
+
+Head dW / db (fp32 outputs, no bf16 term): scale * sum_n dl[n][j] * feat[n][c] over N images in any order, then
+the multiply by scale: 2 * (N + 1) * U * scale * (|dl|.T @ |feat|), and 2 * (N + 1) * U * scale * sum_n |dl|.
+
+SGD (Nesterov), all fp32: m' = mu*m + (g*is + wd*p), p' = p - lr*((g*is + wd*p) + mu*m'). With
+Tm = mu|m| + |g|*is + wd|p| every intermediate of the first chain is at most Tm in magnitude and the chain holds at
+most four roundings (g*is, wd*p, their sum, mu*m + that; fewer with FMA contraction): tol_m = 4 * U * Tm. With
+Tp = |p| + lr*((|g|*is + wd|p|) + mu*Tm) the second chain adds at most four more (mu*m', the sum, the product with
+lr, the subtraction) on values bounded by Tp: tol_p = 8 * U * Tp. The reference is float64 arithmetic on the fp32
+inputs with the scalars at their fp32 values.
 """
 import numpy as np
 
@@ -143,11 +160,66 @@ def bn_bwd_tol(ref, dz, x, gamma, mean, invstd):
     return tol(ref, (16 * U * T).reshape(x.shape))
 
 
-def head_dact_tol(ref, dlogits, w, hw):
-    """dact [N,h,w,C] = (dlogits @ W) / (h*w) broadcast over the pixels."""
+def head_dact_tol(ref, dlogits, w, hw, bf=True):
+    """dact [N,h,w,C] = (dlogits @ W) / (h*w) broadcast over the pixels (bf=False: the fp32 executor, d alone)."""
     ncls = np.shape(w)[0]
     d = 2 * ncls * U * (np.abs(_f64(dlogits)) @ np.abs(_f64(w))) / (hw[0] * hw[1])
-    return tol(ref, d[:, None, None, :])
+    d = d[:, None, None, :]
+    return tol(ref, d) if bf else np.broadcast_to(d, np.shape(ref))
+
+
+def head_feat_tol(ref, act, bf=True):
+    """feat [N,C] = mean over the pixels of act [N,h,w,C]; ref: that mean in float64."""
+    a = np.abs(_f64(act)).reshape(np.shape(act)[0], -1, np.shape(act)[-1])
+    d = (a.shape[1] + 1) * U * a.mean(axis=1)
+    return tol(ref, d) if bf else d
+
+
+def head_logits_ref_tol(feat, w, b, bf=True):
+    """(ref, bound) of the Linear on the kernel's own feat: ref = feat @ W.T + bf16(b) in float64 (fp32 executor:
+    b unrounded)."""
+    feat, w = _f64(feat), _f64(w)
+    bb = _f64(O.bf16(b)) if bf else _f64(b)
+    ref = feat @ w.T + bb
+    return ref, head_logits_tol(ref, feat, w, b, bf)
+
+
+def head_logits_tol(ref, feat, w, b, bf=True):
+    feat, w = _f64(feat), _f64(w)
+    bb = _f64(O.bf16(b)) if bf else _f64(b)
+    S = np.abs(feat) @ np.abs(w).T + np.abs(bb)
+    d = 2 * (feat.shape[1] + 1) * U * S
+    return tol(ref, d) if bf else d
+
+
+def head_dw_tol(dl, feat, scale):
+    """dW [ncls,C] = scale * dl.T @ feat, fp32."""
+    dl, feat = _f64(dl), _f64(feat)
+    return 2 * (dl.shape[0] + 1) * U * abs(scale) * (np.abs(dl).T @ np.abs(feat))
+
+
+def head_db_tol(dl, scale):
+    dl = _f64(dl)
+    return 2 * (dl.shape[0] + 1) * U * abs(scale) * np.abs(dl).sum(axis=0)
+
+
+# ----------------------------------------------------------------------------- SGD (Nesterov)
+def sgd_ref(p, g, m, lr, wd, mu, inv_scale=1.0):
+    """(p', m') of one step in float64 on the fp32 inputs, the scalars at their fp32 values."""
+    p, g, m = _f64(p), _f64(g), _f64(m)
+    lr, wd, mu, is_ = (float(np.float32(v)) for v in (lr, wd, mu, inv_scale))
+    d = g * is_ + wd * p
+    m2 = mu * m + d
+    return p - lr * (d + mu * m2), m2
+
+
+def sgd_tol(p, g, m, lr, wd, mu, inv_scale=1.0):
+    """(tol_p, tol_m) for sgd_ref's outputs."""
+    p, g, m = (np.abs(_f64(v)) for v in (p, g, m))
+    lr, wd, mu, is_ = (abs(float(np.float32(v))) for v in (lr, wd, mu, inv_scale))
+    Tm = mu * m + g * is_ + wd * p
+    Tp = p + lr * ((g * is_ + wd * p) + mu * Tm)
+    return 8 * U * Tp, 4 * U * Tm
 
 
 # ----------------------------------------------------------------------------- guard-band arenas

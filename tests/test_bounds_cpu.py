@@ -237,3 +237,166 @@ def test_assert_within_reports_and_flags_non_finite():
     d = np.abs(v) * 1e-3
     r = v.astype(np.float64) + d * g.uniform(-1, 1, v.shape)
     assert B.assert_within(O.bf16(v), r, B.tol(r, d), "tol") <= 1.0
+
+
+# ----------------------------------------------------------------------------- head and SGD bounds
+# (N, HW, C, ncls): the prefetch path's limits, groups > HW, tpr not dividing 256, two 64-chunk rounds, largest /
+# smallest C -- the shapes tests/test_gpu_head.py runs on the device
+HEAD_SHAPES = [(3, 49, 512, 128), (2, 1, 512, 10), (3, 15, 96, 129), (2, 16, 1024, 1000), (2, 4, 2048, 33),
+               (5, 64, 32, 7)]
+
+
+def _head_data(shape, seed):
+    """Seeded head operands. The bias is of the logits' own size (scale 2): an unrounded bias differs from the
+    rounded one by at most 2^-9 |b|, which can only show beside the output's own half-ulp when |b| ~ |logit|."""
+    Nn, HW, Cn, ncls = shape
+    g = np.random.default_rng(seed)
+    act = O.relu(_rand_bf16((Nn, HW, 1, Cn), g))
+    w = _rand_bf16((ncls, Cn), g, 0.05)
+    b = (g.standard_normal(ncls) * 2).astype(np.float32)
+    dl = (g.standard_normal((Nn, ncls)) * 0.25).astype(np.float32)
+    return act, w, b, dl
+
+
+def _pool_emu(act, skip=None):
+    """fp32 pool, pixels summed last to first (the kernels: strided groups, first to last); skip = (n, p) drops
+    that pixel from image n's sum."""
+    Nn, HW = act.shape[0], act.shape[1] * act.shape[2]
+    a = act.reshape(Nn, HW, -1).astype(np.float32)
+    s = np.zeros((Nn, a.shape[2]), np.float32)
+    for p in range(HW - 1, -1, -1):
+        v = a[:, p].copy()
+        if skip is not None and skip[1] == p:
+            v[skip[0]] = 0
+        s = s + v
+    return O.bf16(s / np.float32(HW))
+
+
+def _linear_emu(feat, w, b, round_bias=True):
+    """fp32 Linear in 16-channel chunks, last chunk first, + the bias, rounded to bf16."""
+    f, wt = feat.astype(np.float32), np.ascontiguousarray(w.astype(np.float32).T)
+    acc = np.zeros((f.shape[0], wt.shape[1]), np.float32)
+    for k0 in range(f.shape[1] - 16, -1, -16):
+        acc = acc + f[:, k0:k0 + 16] @ wt[k0:k0 + 16]
+    return O.bf16(acc + (O.bf16(b) if round_bias else b.astype(np.float32)))
+
+
+def _dact_emu(dl, w, HW, skip=None):
+    """fp32 dact row per image (the same at every pixel): classes summed last to first; skip = (n, j)."""
+    acc = np.zeros((dl.shape[0], w.shape[1]), np.float32)
+    for j in range(w.shape[0] - 1, -1, -1):
+        d = dl[:, j].astype(np.float32).copy()
+        if skip is not None and skip[1] == j:
+            d[skip[0]] = 0
+        acc = acc + d[:, None] * w[j].astype(np.float32)[None, :]
+    return O.bf16(acc * (np.float32(1) / np.float32(HW)))
+
+
+def _dw_emu(dl, feat, scale, skip=None):
+    """fp32 dW / db, images summed last to first; skip = (n, j) drops image n from row j and from db[j]."""
+    dw = np.zeros((dl.shape[1], feat.shape[1]), np.float32)
+    db = np.zeros(dl.shape[1], np.float32)
+    for n in range(dl.shape[0] - 1, -1, -1):
+        d = dl[n].astype(np.float32).copy()
+        if skip is not None and skip[0] == n:
+            d[skip[1]] = 0
+        dw = dw + d[:, None] * feat[n].astype(np.float32)[None, :]
+        db = db + d
+    return dw * np.float32(scale), db * np.float32(scale)
+
+
+def _outside(got, ref, tol, name):
+    with pytest.raises(AssertionError, match="outside the bound") as ei:
+        B.assert_within(got, ref, tol, name)
+    print(f"{name}: {str(ei.value).split(':', 1)[1][:110]}")
+
+
+def test_head_bounds_hold_for_fp32_emulation_and_reject_planted_defects():
+    worst = {"feat": 0.0, "logits": 0.0, "dact": 0.0, "dW": 0.0, "db": 0.0}
+    scale = 0.25
+    for i, shape in enumerate(HEAD_SHAPES):
+        Nn, HW, Cn, ncls = shape
+        act, w, b, dl = _head_data(shape, 100 + i)
+        f_ref = act.astype(np.float64).reshape(Nn, HW, Cn).mean(axis=1)
+        f_tol = B.head_feat_tol(f_ref, act)
+        feat = _pool_emu(act)
+        l_ref, l_tol = B.head_logits_ref_tol(feat, w, b)
+        logits = _linear_emu(feat, w, b)
+        dw_ref, db_ref, dact_ref = O.head_bwd(dl, feat.astype(np.float64), w, (HW, 1))
+        dw_ref, db_ref = scale * dw_ref, scale * db_ref
+        dact_tol = B.head_dact_tol(dact_ref, dl, w, (HW, 1))
+        dw_tol, db_tol = B.head_dw_tol(dl, feat, scale), B.head_db_tol(dl, scale)
+        dact = np.broadcast_to(_dact_emu(dl, w, HW)[:, None, None, :], dact_ref.shape)
+        dw, db = _dw_emu(dl, feat, scale)
+        r = {"feat": B.assert_within(feat, f_ref, f_tol, f"feat {shape}"),
+             "logits": B.assert_within(logits, l_ref, l_tol, f"logits {shape}"),
+             "dact": B.assert_within(dact, dact_ref, dact_tol, f"dact {shape}"),
+             "dW": B.assert_within(dw, dw_ref, dw_tol, f"dW {shape}"),
+             "db": B.assert_within(db, db_ref, db_tol, f"db {shape}")}
+        print(f"head {shape}: clean emulation |err|/tol " + ", ".join(f"{k} {v:.3f}" for k, v in r.items()))
+        worst = {k: max(v, r[k]) for k, v in worst.items()}
+        # fp32 executor: the same sums without the bf16 rounding are inside the d-only bounds
+        a32 = act.reshape(Nn, HW, Cn).astype(np.float32)
+        f32 = a32[:, ::-1].sum(axis=1, dtype=np.float32) / np.float32(HW)
+        assert B.assert_within(f32, f_ref, B.head_feat_tol(f_ref, act, bf=False), "feat fp32") <= 1.0
+        l32_ref, l32_tol = B.head_logits_ref_tol(f32, w, b, bf=False)
+        l32 = (f32 @ w.astype(np.float32).T + b).astype(np.float32)
+        assert B.assert_within(l32, l32_ref, l32_tol, "logits fp32") <= 1.0
+        # planted defects
+        n = Nn - 1
+        if HW > 1:
+            _outside(_pool_emu(act, skip=(n, HW // 2)), f_ref, f_tol, f"feat {shape} / one pixel dropped")
+        m = np.array(dact)
+        m[n] = _dact_emu(dl, w, HW, skip=(n, ncls // 2))[n][None, None, :]
+        _outside(m, dact_ref, dact_tol, f"dact {shape} / one class dropped from one image")
+        dw_m, db_m = _dw_emu(dl, feat, scale, skip=(n, ncls - 1))
+        assert np.array_equal(dw_m[:-1], dw[:-1]) and np.array_equal(db_m[:-1], db[:-1])
+        _outside(dw_m, dw_ref, dw_tol, f"dW {shape} / one image dropped from one row")
+        _outside(db_m, db_ref, db_tol, f"db {shape} / one image dropped")
+        if Nn * ncls >= 256:  # (an element must sit at a half-ulp edge: enough elements)
+            _outside(_linear_emu(feat, w, b, round_bias=False), l_ref, l_tol, f"logits {shape} / bias unrounded")
+    print("head bounds, worst clean |err|/tol: " + ", ".join(f"{k} {v:.3f}" for k, v in worst.items()))
+
+
+def _sgd_emu(p, g, m, lr, wd, mu, is_, once=False):
+    """Unfused fp32 step (every product and sum rounded; the kernel may contract to FMAs), the decay term first.
+    once: the look-ahead adds m' instead of mu * m' (momentum applied once)."""
+    f = np.float32
+    d = f(wd) * p + g * f(is_)
+    m2 = d + f(mu) * m
+    d2 = (m2 if once else f(mu) * m2) + d
+    return p - f(lr) * d2, m2
+
+
+def test_sgd_bound_holds_for_fp32_emulation_and_rejects_planted_defects():
+    n = 4096
+    g_ = np.random.default_rng(9)
+    worst = [0.0, 0.0]
+    for lr, wd, mu, is_ in ((0.1, 5e-4, 0.9, 1.0), (3.2, 5e-4, 0.9, 1.0 / 65536), (0.1, 0.0, 0.0, 1.0)):
+        p = g_.standard_normal(n).astype(np.float32)
+        m = np.zeros(n, np.float32)
+        for step in range(3):
+            g = (g_.standard_normal(n) / is_).astype(np.float32)
+            (p_ref, m_ref), (tp, tm) = B.sgd_ref(p, g, m, lr, wd, mu, is_), B.sgd_tol(p, g, m, lr, wd, mu, is_)
+            p2, m2 = _sgd_emu(p, g, m, lr, wd, mu, is_)
+            assert p2.dtype == np.float32 and m2.dtype == np.float32
+            worst[0] = max(worst[0], B.assert_within(p2, p_ref, tp, "sgd p"))
+            worst[1] = max(worst[1], B.assert_within(m2, m_ref, tm, "sgd m"))
+            if mu > 0:
+                _outside(_sgd_emu(p, g, m, lr, wd, mu, is_, once=True)[0], p_ref, tp, "sgd p / momentum applied once")
+            p, m = p2, m2
+    print(f"sgd n={n}: clean emulation worst |err|/tol p {worst[0]:.3f}, m {worst[1]:.3f}")
+    assert worst[0] < 1.0 and worst[1] < 1.0
+
+
+def test_bf16_shadow_truncation_differs_from_rounding_on_ties_and_random_data():
+    """The shadow's criterion is bit equality with O.bf16_bits: a truncating conversion differs on the exact ties
+    with an odd upper half, one ulp above any tie, and on about half of random data."""
+    u = np.array([0x3F808000, 0x3F818000, 0xBF808000, 0xBF818000, 0x3F808001, 0x3F807FFF, 0x00000000, 0x80000000,
+                  0x00800000, 0x7F7FFFFF], np.uint32)
+    want = np.array([0x3F80, 0x3F82, 0xBF80, 0xBF82, 0x3F81, 0x3F80, 0x0000, 0x8000, 0x0080, 0x7F80], np.uint16)
+    np.testing.assert_array_equal(O.bf16_bits(u.view(np.float32)), want)
+    trunc = (u >> 16).astype(np.uint16)
+    assert (trunc != want).sum() == 4  # the odd ties, the value above the tie, the largest finite
+    r = np.random.default_rng(5).standard_normal(4096).astype(np.float32)
+    assert 0.4 < np.mean((r.view(np.uint32) >> 16).astype(np.uint16) != O.bf16_bits(r)) < 0.6

@@ -29,6 +29,20 @@ def test_fp32_per_layer_teacher_forced_b64_224(dtc, cuda):
     _teacher_forced(dtc, cuda, 1, hw=224, seed=32, precision="fp32")
 
 
+@pytest.mark.parametrize("num_classes", [10, 1000])
+def test_fp32_per_layer_teacher_forced_class_counts(dtc, cuda, num_classes):
+    """The fp32 head templates off 100 classes (reachable only through the network): stem, layer4 and the head at
+    10 and 1000 classes, the Linear's gradients element-wise."""
+    errs = _teacher_forced(dtc, cuda, 3, stages=(0, 4), seed=41, precision="fp32", num_classes=num_classes)
+    assert len(errs) >= 30
+
+
+def test_fp32_per_layer_teacher_forced_non_square(dtc, cuda):
+    """24x40 input (maps 24x40 ... 3x5, a 15-pixel pool), every layer, fp32."""
+    errs = _teacher_forced(dtc, cuda, 3, hw=(24, 40), seed=43, precision="fp32")
+    assert len(errs) > 90
+
+
 def test_fp32_end_to_end_matches_oracle(dtc, cuda):
     """Free-running fp32 forward + backward vs the fp32 oracle (no rounding points anywhere): unlike
     bf16, fp32 stays close end to end -- logits and loss to 1e-5, every activation to 1e-4, every

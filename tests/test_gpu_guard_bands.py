@@ -13,7 +13,9 @@ options and therefore the same plan:
 * the BN statistics totals are exactly equal,
 * every guard word of every arena, the inputs' included, is bit-unchanged (a stray store shows there).
 
-The shapes and forced options are those of the existing tests of each kernel (tests/test_gpu_ops.py).
+The shapes and forced options are those of the existing tests of each kernel (tests/test_gpu_ops.py); the head
+cases (pool + Linear, cross-entropy backward into an embedded dlogits, the head backward through both of its paths)
+are two of tests/test_gpu_head.py's: ragged image splits and class tiles, C below one 256-channel strip.
 """
 import numpy as np
 import pytest
@@ -185,6 +187,34 @@ def _stem(x, w27, dy):
     return op
 
 
+def _head(act, w, bias, labels):
+    """head_fwd -> xent_bwd -> head_bwd: activations, weights, bias, dlogits, feat, every output and the workspace
+    embedded."""
+    def op(dtc, a):
+        N, h, w_, C = act.shape
+        ncls = w.shape[0]
+        moat = isinstance(a, _Moat)
+        wd = a.inp(w)
+        feat, logits = dtc.ops.head_fwd(a.inp(act), wd, a.inp(bias, F32),
+                                        out=(a.out((N, C), F32), a.out((N, ncls), F32)) if moat else None)
+        lab = torch.from_numpy(labels).to(a.dev)
+        _, lse = dtc.ops.xent_fwd(logits, lab)
+        dl = dtc.ops.xent_bwd(logits, lab, lse, torch.full((1,), 16.0, device=a.dev), out=a.out((N, ncls), F32))
+        dw, db, dact = dtc.ops.head_bwd(dl, feat, wd, (h, w_), scale=0.25,
+                                        out=(a.out((ncls, C), F32), a.out((ncls,), F32), a.out((N, h, w_, C)))
+                                        if moat else None,
+                                        workspace=a.ws(dtc._native.lib.dtc_head_bwd_workspace_size(N, C, ncls)))
+        return [feat, logits, dl, dw, db, dact], []
+    return op
+
+
+def _head_ops(case, seed):
+    N, h, w_, C, ncls = case
+    g = np.random.default_rng(seed)
+    return [_head(O.relu(_rand_bf16((N, h, w_, C), g)), _rand_bf16((ncls, C), g, 0.05),
+                  g.standard_normal(ncls).astype(np.float32), g.integers(0, ncls, N))]
+
+
 def _conv_ops(case, seed, modes="fdw"):
     """FWD (+ statistics), DGRAD + residual and WGRAD of one (N, H, W, C, K, R, stride) geometry."""
     N, H, W, C, K, R, st = case
@@ -253,6 +283,10 @@ CASES = [
     ("wgrad-batch-n3", {}, lambda: _batch_ops((2, 14, 28, 128, 128, 3), 11)),
     ("wgrad-s2-sc-fused", {"wgrad_s2": 1}, lambda: _s2_ops((5, 16, 16, 128, 256), 7, "wgrad_sc")),
     ("stem-3x7x9", {}, lambda: _stem_ops((3, 7, 9), 12)),
+    ("head-33x7x7x512x128-fused", {"head_fused": 1}, lambda: _head_ops((33, 7, 7, 512, 128), 51)),
+    ("head-33x7x7x512x128-unfused", {"head_fused": 0}, lambda: _head_ops((33, 7, 7, 512, 128), 51)),
+    ("head-70x2x3x96x129-fused", {"head_fused": 1}, lambda: _head_ops((70, 2, 3, 96, 129), 52)),
+    ("head-70x2x3x96x129-unfused", {"head_fused": 0}, lambda: _head_ops((70, 2, 3, 96, 129), 52)),
 ]
 
 

@@ -37,16 +37,21 @@ def _autocast_bf16(dtc):
     dtc.nn.set_autocast_enabled(prev)
 
 
-def _setup(dtc, cuda, batch, seed=0, capture=False, hw=32):
+def _hw(hw):
+    """hw: a side length, or an (h, w) pair."""
+    return (hw, hw) if isinstance(hw, int) else (int(hw[0]), int(hw[1]))
+
+
+def _setup(dtc, cuda, batch, seed=0, capture=False, hw=32, num_classes=100):
     torch.manual_seed(42)
-    model = dtc.ResNet18()
+    model = dtc.ResNet18(num_classes=num_classes)
     sd = {k: v.detach().numpy().copy() for k, v in model.state_dict().items()}
     model = model.to(cuda)
     if capture:
         model.enable_capture()
     g = np.random.default_rng(seed)
-    x = g.standard_normal((batch, 3, hw, hw)).astype(np.float32)
-    y = g.integers(0, 100, batch)
+    x = g.standard_normal((batch, 3) + _hw(hw)).astype(np.float32)
+    y = g.integers(0, num_classes, batch)
     return model, sd, x, y
 
 
@@ -106,8 +111,9 @@ def _bn_state_draw(sd, seed):
 
 
 def _teacher_forced(dtc, cuda, batch, hw=32, stages=(0, 1, 2, 3, 4), imgs=None, seed=0, precision="bf16",
-                    bn_state_seed=None, sync_comm=None, eval_after=False):
-    """Run one capture-enabled training forward/backward of the executor at (batch, hw x hw) and
+                    bn_state_seed=None, sync_comm=None, eval_after=False, num_classes=100):
+    """Run one capture-enabled training forward/backward of the executor at (batch, hw x hw; hw may be an (h, w)
+    pair) with a `num_classes`-wide head and
     check every layer of the listed stages (0 = stem + head, 1..4 = layer1..4) against the oracle
     evaluated on THAT layer's executor inputs. `imgs` (index array) restricts the per-image ops
     (conv forward / dgrad, the ReLU masks) to those images -- BN statistics and weight gradients,
@@ -126,7 +132,7 @@ def _teacher_forced(dtc, cuda, batch, hw=32, stages=(0, 1, 2, 3, 4), imgs=None, 
     all zero). `sync_comm`: run as SyncBatchNorm over that communicator. `eval_after`: then an eval-mode
     forward of the same model against the oracle's eval forward on the post-training buffers (3e-2), which
     must leave the buffers bit-unchanged."""
-    model, sd, x, y = _setup(dtc, cuda, batch, seed=seed, capture=True, hw=hw)
+    model, sd, x, y = _setup(dtc, cuda, batch, seed=seed, capture=True, hw=hw, num_classes=num_classes)
     model.precision = precision
     perturbed = bn_state_seed is not None
     if perturbed:
@@ -144,7 +150,8 @@ def _teacher_forced(dtc, cuda, batch, hw=32, stages=(0, 1, 2, 3, 4), imgs=None, 
     loss = crit(logits, yd)
     loss.backward()
     torch.cuda.synchronize()
-    exe = model.executor(batch, hw, hw, precision)
+    exe = model.executor(batch, *_hw(hw), precision)
+    DL = _np(exe.dlogits_buffer()).astype(np.float64)  # the dlogits the head backward consumed
     A = {k: _np(v) for k, v in exe.activations().items()}
     G = {k: _np(v) for k, v in exe.activations(captures=True).items()}
     P = {k: v for k, v in _split_state(sd)[0].items()}
@@ -250,18 +257,38 @@ def _teacher_forced(dtc, cuda, batch, hw=32, stages=(0, 1, 2, 3, 4), imgs=None, 
                         el=el_bn(A[pre + ".conv2"], P[pre + ".bn2.weight"], P[pre + ".bn2.bias"], res=inp))
             inp = A[pre + ".out"]
     feat, lg = O.head_fwd(inp, P["linear.weight"], P["linear.bias"], bf16_mode=bf)
+    kfeat = A["head.feat_f32"].reshape(feat.shape)  # the executor's own pooled features
     if 0 in stages:
-        chk("head.feat", A["head.feat_f32"].reshape(feat.shape), feat, 1e-5)
-        chk("logits", _np(logits), lg)
+        fmean = inp.astype(np.float64).mean(axis=(1, 2))
+        chk("head.feat", kfeat, feat, 1e-5, el=lambda _: (fmean, B.head_feat_tol(fmean, inp)))
+        chk("logits", _np(logits), lg,
+            el=lambda _: B.head_logits_ref_tol(kfeat, rnd(P["linear.weight"]), P["linear.bias"]))
 
     # ---------------- backward, layer by layer (inputs = the executor's own intermediates)
     _, dl, _ = O.cross_entropy(_np(logits), y)
     if 0 in stages:
         dw, db, dact = O.head_bwd(dl, A["head.feat_f32"].reshape(feat.shape), rnd(P["linear.weight"]),
                                   inp.shape[1:3])
+        # element-wise from the dlogits the kernel itself consumed; dW / db in both precisions (fp32 outputs)
+        np.testing.assert_allclose(DL, dl, rtol=1e-4, atol=1e-6)
+        dw_k, db_k, dact_k = O.head_bwd(DL, kfeat, rnd(P["linear.weight"]), inp.shape[1:3])
         chk("linear.weight.grad", grads["linear.weight"], dw, F32)
         chk("linear.bias.grad", grads["linear.bias"], db, F32)
-        chk("grad.layer4.1.dy", G["grad.layer4.1.dy"], dact)
+        chk("grad.layer4.1.dy", G["grad.layer4.1.dy"], dact,
+            el=lambda _: (dact_k, B.head_dact_tol(dact_k, DL, rnd(P["linear.weight"]), inp.shape[1:3])))
+        wl = rnd(P["linear.weight"])
+        head_el = [("linear.weight.grad", grads["linear.weight"], dw_k, B.head_dw_tol(DL, kfeat, 1.0)),
+                   ("linear.bias.grad", grads["linear.bias"], db_k, B.head_db_tol(DL, 1.0))]
+        if not bf:  # the fp32 executor's head outputs against the unrounded forms of the same bounds
+            head_el += [("head.feat", kfeat, fmean, B.head_feat_tol(fmean, inp, bf=False)),
+                        ("logits", _np(logits)) + B.head_logits_ref_tol(kfeat, wl, P["linear.bias"], bf=False),
+                        ("grad.layer4.1.dy", G["grad.layer4.1.dy"], dact_k,
+                         B.head_dact_tol(dact_k, DL, wl, inp.shape[1:3], bf=False))]
+        for name, got, ref, bound in head_el:
+            try:
+                ratios[name] = B.assert_within(got, ref, bound, name)
+            except AssertionError as e:
+                el_bad.append(str(e))
     for L, pre, st, proj, inp in reversed(blocks):
         if L not in stages:
             continue
@@ -313,7 +340,8 @@ def _teacher_forced(dtc, cuda, batch, hw=32, stages=(0, 1, 2, 3, 4), imgs=None, 
             O.conv2d_wgrad(xb, G["grad.stem.dc"], 3, 3, 1, 1), F32)
     bad = {k: v for k, v in errs.items() if v[0] > v[1]}
     worst = max(errs.items(), key=lambda kv: kv[1][0] / kv[1][1])
-    print(f"teacher-forced {precision} B={batch} {hw}x{hw} stages={stages}: {len(errs)} checks, worst {worst[0]} "
+    hw = "x".join(str(v) for v in _hw(hw))
+    print(f"teacher-forced {precision} B={batch} {hw} stages={stages}: {len(errs)} checks, worst {worst[0]} "
           f"{worst[1][0]:.2e} (tol {worst[1][1]:.0e})")
     assert not bad, f"per-layer parity failures: {bad}"
     if ratios:
@@ -322,8 +350,11 @@ def _teacher_forced(dtc, cuda, batch, hw=32, stages=(0, 1, 2, 3, 4), imgs=None, 
             ("conv fwd", lambda k: not k.startswith("grad.") and (".conv" in k or k.endswith(".shortcut"))),
             ("bn apply", lambda k: k.endswith((".out", ".relu1"))),
             ("conv dgrad", lambda k: k.endswith((".da1", ".dxs", ".dx"))),
-            ("bn bwd", lambda k: k.endswith((".dc2", ".dc1", ".ds", ".dc"))))}
-        print(f"teacher-forced {precision} B={batch} {hw}x{hw} stages={stages}: {len(ratios)} element-wise checks, worst "
+            ("bn bwd", lambda k: k.endswith((".dc2", ".dc1", ".ds", ".dc"))),
+            ("head feat", lambda k: k == "head.feat"), ("head logits", lambda k: k == "logits"),
+            ("head dact", lambda k: k == "grad.layer4.1.dy"), ("head dW", lambda k: k == "linear.weight.grad"),
+            ("head db", lambda k: k == "linear.bias.grad"))}
+        print(f"teacher-forced {precision} B={batch} {hw} stages={stages}: {len(ratios)} element-wise checks, worst "
               f"|err|/tol {wr[1]:.3f} ({wr[0]}); " + ", ".join(f"{f} {v:.3f}" for f, v in fam.items()))
     assert not el_bad, "element-wise bound failures:\n" + "\n".join(el_bad)
     if perturbed:
@@ -379,6 +410,21 @@ def _check_bn_state_after(sd, sd_after, A, stages):
 @pytest.mark.parametrize("batch", [2, 8])
 def test_per_layer_teacher_forced(dtc, cuda, batch):
     errs = _teacher_forced(dtc, cuda, batch)
+    assert len(errs) > 90
+
+
+@pytest.mark.parametrize("num_classes", [10, 1000])
+def test_per_layer_teacher_forced_class_counts(dtc, cuda, num_classes):
+    """The head off 100 classes (ResNet18(num_classes=)): 10 keeps the C == 512 && ncls <= 128 paths at another
+    width, 1000 takes the generic Linear and dact loops; stem, layer4 and the head, element-wise."""
+    errs = _teacher_forced(dtc, cuda, 3, stages=(0, 4), seed=41, num_classes=num_classes)
+    assert len(errs) >= 30
+
+
+def test_per_layer_teacher_forced_non_square(dtc, cuda):
+    """24x40 input: maps of 24x40, 12x20, 6x10 and 3x5 (a 15-pixel pool), every layer. A height / width mix-up in
+    the executor's planning, workspace sizing or stride-2 bookkeeping shows here and in no square case."""
+    errs = _teacher_forced(dtc, cuda, 3, hw=(24, 40), seed=43)
     assert len(errs) > 90
 
 
@@ -523,7 +569,18 @@ def test_eval_mode_matches_oracle(dtc, cuda):
 def test_sgd_step_in_situ(dtc, cuda):
     """After a real backward, the fused step equals torch.optim.SGD(nesterov) math on the
     executor's own gradients (oracle.ops.sgd_nesterov), two consecutive steps."""
-    model, sd, x, y = _setup(dtc, cuda, 4, seed=3)
+    _sgd_step_in_situ(dtc, cuda, 100)
+
+
+def test_sgd_step_in_situ_10_classes(dtc, cuda):
+    """The same at num_classes = 10: the 10-element bias sits in a 64-aligned slot of the flat buffer, and the
+    step runs over the padding beside it."""
+    _sgd_step_in_situ(dtc, cuda, 10)
+
+
+def _sgd_step_in_situ(dtc, cuda, num_classes):
+    model, sd, x, y = _setup(dtc, cuda, 4, seed=3, num_classes=num_classes)
+    assert tuple(model.linear.bias.shape) == (num_classes,)
     crit = dtc.CrossEntropyLoss()
     opt = dtc.SGD(model.parameters(), lr=0.1, momentum=0.9, weight_decay=1e-4, nesterov=True)
     xd, yd = torch.from_numpy(x).to(cuda), torch.from_numpy(y).to(cuda)
@@ -1111,12 +1168,13 @@ def test_native_loss_backward_matches_autograd(dtc, cuda):
 
 
 @pytest.mark.parametrize("head_fused", [1, 0])
-@pytest.mark.parametrize("precision,batch", [("bf16", 8), ("bf16", 64), ("fp32", 8)])
+@pytest.mark.parametrize("precision,batch", [("bf16", 8), ("bf16", 64), ("fp32", 8), ("bf16", 260)])
 def test_xent_fused_into_head_backward_bit_identical(dtc, cuda, head_fused, precision, batch):
     """Option xent_fuse (default on): the CrossEntropyLoss backward is computed inside the head backward
     kernel instead of a launch of its own. Every gradient and the executor's dlogits buffer are
     bit-identical to the separate xent_bwd launch, for the one-launch head backward and the three-kernel
-    one (head_fused 0, where the fused call falls back to xent_bwd first), bf16 and fp32 executors."""
+    one (head_fused 0, where the fused call falls back to xent_bwd first), bf16 and fp32 executors. Batch 260:
+    the fused kernel's dlogits column loop takes a second 256-image trip, holding 4 images."""
     lib = dtc._native.lib
     prev_hf = lib.dtc_get_option(b"head_fused")
     lib.dtc_set_option(b"head_fused", head_fused)

@@ -57,6 +57,28 @@ def test_layout_matches_module_tree(dtc):
     assert len(lay.bns) == 20 and sum(b.channels for b in lay.bns) * 2 == 9600
 
 
+@pytest.mark.parametrize("num_classes", [10, 1000])
+def test_layout_matches_module_tree_other_class_counts(dtc, num_classes):
+    """The structural assertions of test_layout_matches_module_tree off 100 classes: only the Linear's 513
+    elements per class change."""
+    import torch
+    torch.manual_seed(0)
+    m = dtc.ResNet18(num_classes=num_classes)
+    lay = dtc.nn.Layout(num_classes)
+    assert [p.name for p in lay.params] == [n for n, _ in m.named_parameters()]
+    assert {p.name: tuple(p.shape) for p in lay.params} == {n: tuple(q.shape) for n, q in m.named_parameters()}
+    assert sum(p.numel for p in lay.params) == 11_220_132 + (num_classes - 100) * 513
+    offs = [p.offset for p in lay.params]
+    assert offs == sorted(offs, reverse=True)
+    for p in lay.params:
+        assert p.offset % 64 == 0
+    spans = sorted((p.offset, p.offset + p.numel) for p in lay.params)
+    assert all(a[1] <= b[0] for a, b in zip(spans, spans[1:]))
+    assert lay.flat_numel >= spans[-1][1] and lay.flat_numel % 64 == 0
+    by_name = {p.name: p for p in lay.params}
+    assert by_name["linear.weight"].shape == (num_classes, 512) and by_name["linear.bias"].numel == num_classes
+
+
 @pytest.mark.parametrize("cap_mb", [1, 5, 25, 100, 1000])
 def test_buckets_tile_the_gradient_buffer(dtc, cap_mb):
     lay = dtc.nn.Layout(100, cap_mb)
