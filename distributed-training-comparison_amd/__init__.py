@@ -16,7 +16,8 @@ from . import data, ops  # noqa: F401
 from .amp import GradScaler, autocast  # noqa: F401
 from .nn import (BasicBlock, CrossEntropyLoss, EvalResult, MixedTarget, ResNet, ResNet18,  # noqa: F401
                  SyncBatchNorm)
-from . import optim  # noqa: F401
+from . import ema, optim  # noqa: F401
+from .ema import ModelEma  # noqa: F401
 from .optim import LARS, SGD, Adam, AdamW, clip_grad_norm_  # noqa: F401
 from .parallel import DDP, Comm, DataParallel, DistributedDataParallel, barrier  # noqa: F401
 from . import parallel  # noqa: F401

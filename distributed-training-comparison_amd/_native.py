@@ -65,6 +65,15 @@ PSeg = C.POINTER(Seg)
 SEG_ADAPT = 1
 
 
+class EmaRange(C.Structure):
+    """dtc_ema_range: one flat range of dtc_ema_update (ema_bf16 may be NULL)."""
+
+    _fields_ = [("ema", C.c_void_p), ("src", C.c_void_p), ("ema_bf16", C.c_void_p), ("n", C.c_int64)]
+
+
+PEmaRange = C.POINTER(EmaRange)
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "dtc_abi_version": (i32, []),
@@ -124,6 +133,8 @@ _SIGS = {
     "dtc_segplan_bind": (i32, [vp, vp, sz, vp]),
     "dtc_seg_norms": (i32, [vp, vp, vp, vp, vp, vp]),
     "dtc_lars_flat": (i32, [vp, vp, vp, vp, vp, f64, f64, f64, i32, f64, f64, i32, vp, vp, vp, vp]),
+    "dtc_ema_state_words": (i32, []),
+    "dtc_ema_update": (i32, [PEmaRange, i32, vp, f64, i32, vp, vp]),
     "dtc_cast_f32_bf16": (i32, [vp, vp, i64, vp]),
     "dtc_amp_scale": (i32, [vp, vp, vp, i64, vp]),
     "dtc_amp_check_finite": (i32, [vp, i64, vp, vp]),
@@ -184,6 +195,7 @@ _SIGS = {
     "dtc_rn18_xent_backward": (i32, [vp, vp, vp, vp, vp, f32, vp, vp]),
     "dtc_rn18_xent_soft_backward": (i32, [vp, vp, vp, vp, vp, f32, vp, vp, f32, vp, vp]),
     "dtc_rn18_eval_batch": (i32, [vp, vp, vp, i32, i32, vp, vp, vp]),
+    "dtc_rn18_eval_batch_weights": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp]),
     "dtc_rn18_set_sync_bn": (i32, [vp, vp]),
     "dtc_rn18_dlogits_buffer": (i32, [vp, C.POINTER(sz)]),
 }

@@ -62,6 +62,13 @@ class GradScaler:
     def is_enabled(self):
         return self._enabled
 
+    @property
+    def found_inf(self):
+        """The device int32 word the finiteness check sets and update() clears (None before the first step): what
+        a consumer between step() and update() passes to a kernel that must honour a skipped step, e.g.
+        ModelEma.update. Read-only: the word never leaves the GPU."""
+        return self._found_inf
+
     def scale(self, outputs: torch.Tensor) -> torch.Tensor:
         if not self._enabled:
             return outputs

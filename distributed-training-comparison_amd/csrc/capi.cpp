@@ -518,6 +518,15 @@ int dtc_lars_flat(dtc_segplan* plan, float* p, const float* g, float* mom, uint1
   return lars_flat((SegPlan*)plan, p, g, mom, pb, lr, wd, mu, nesterov, trust_coef, eps, trust_clip, inv_scale,
                    found_inf, seg_out, S(stream));
 }
+static_assert(sizeof(dtc_ema_range) == sizeof(EmaRange) && offsetof(dtc_ema_range, src) == offsetof(EmaRange, src) &&
+                  offsetof(dtc_ema_range, ema_bf16) == offsetof(EmaRange, ema_bf16) &&
+                  offsetof(dtc_ema_range, n) == offsetof(EmaRange, n),
+              "dtc_ema_range is EmaRange");
+int dtc_ema_state_words(void) { return DTC_EMA_STATE_WORDS; }
+int dtc_ema_update(const dtc_ema_range* ranges, int nranges, void* state, double decay, int warmup,
+                   const int* found_inf, void* stream) {
+  return ema_update((const EmaRange*)ranges, nranges, state, decay, warmup, found_inf, S(stream));
+}
 int dtc_cast_f32_bf16(const float* src, uint16_t* dst, int64_t n, void* stream) {
   return cast_f32_bf16(src, dst, n, S(stream));
 }

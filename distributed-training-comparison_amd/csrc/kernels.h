@@ -412,6 +412,19 @@ int seg_norms(SegPlan* plan, const float* p, const float* g, const float* gmul, 
 int lars_flat(SegPlan* plan, float* p, const float* g, float* mom, u16* p_bf16, double lr, double wd, double mu,
               int nesterov, double trust_coef, double eps, int trust_clip, const float* inv_scale,
               const int* found_inf, float* seg_out, hipStream_t st);
+// Weight EMA (ema.hip) over 1..DTC_EMA_MAX_RANGES flat ranges in one update launch behind a one-thread tick:
+// ema += (src - ema) * w, ema_bf16 = bf16(ema) where given; `state` is DTC_EMA_STATE_WORDS zeroed 32-bit words
+// (16-byte aligned): word 0 the int32 count of updates, word 1 the fp32 w of the last one. Skipped when *found_inf.
+#define DTC_EMA_STATE_WORDS 4
+#define DTC_EMA_MAX_RANGES 4
+struct EmaRange {  // layout of the ABI's dtc_ema_range
+  float* ema;
+  const float* src;
+  u16* ema_bf16;
+  int64_t n;
+};
+int ema_update(const EmaRange* ranges, int nranges, void* state, double decay, int warmup, const int* found_inf,
+               hipStream_t st);
 int cast_f32_bf16(const float* src, u16* dst, int64_t n, hipStream_t st);
 // zero an 8-byte aligned range (a kernel node, unlike hipMemsetAsync's fill dispatch)
 int zero_bytes(void* p, size_t bytes, hipStream_t st);

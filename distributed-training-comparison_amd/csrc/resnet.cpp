@@ -2022,6 +2022,43 @@ int dtc_rn18_eval_batch(dtc_net* net, const float* x, const int64_t* labels, int
   return eval_batch(net->n, x, labels, n_valid, topk, logits, rec, (hipStream_t)stream);
 }
 
+// The executor reads parameters, bf16 shadow and running statistics only through n.p / n.pb / n.bufs (pf(), wbf(),
+// the BN tables), and nothing derived from them outlives a forward: the stem's packed weight (WSTEM) is re-packed
+// by every forward body, the BN coefficients are recomputed by every eval_batch. So evaluating other weights is
+// the same eager eval_batch with the three pointers swapped for its duration; the destructor puts the bound ones
+// back on every exit path. Captured graphs hold the bound pointers and are not touched (eval_batch replays none).
+int dtc_rn18_eval_batch_weights(dtc_net* net, const float* params, const uint16_t* params_bf16, const float* bufs,
+                                const float* x, const int64_t* labels, int n_valid, int topk, float* logits,
+                                dtc_eval_record* rec, void* stream) {
+  DTC_CHECK_ARG(net != nullptr, "dtc_rn18_eval_batch_weights: null net");
+  DTC_CHECK_ARG(params && params_bf16 && bufs, "dtc_rn18_eval_batch_weights: null weight pointer");
+  DTC_CHECK_ARG(((uintptr_t)params & 15) == 0 && ((uintptr_t)params_bf16 & 15) == 0,
+                "dtc_rn18_eval_batch_weights: parameter buffers must be 16-byte aligned");
+  DTC_CHECK_ARG(n_valid >= 1 && n_valid <= net->n.B && n_valid <= 4096,
+                "dtc_rn18_eval_batch_weights: n_valid = %d outside [1, min(batch = %d, 4096)]", n_valid, net->n.B);
+  DTC_CHECK_ARG(topk >= 1 && topk <= net->n.ncls,
+                "dtc_rn18_eval_batch_weights: topk = %d outside [1, num_classes = %d]", topk, net->n.ncls);
+  DTC_CHECK_ARG(net->n.ws && x && labels && rec, "dtc_rn18_eval_batch_weights: unbound net or null pointer");
+  struct Swap {
+    Net& n;
+    float* p;
+    u16* pb;
+    float* bufs;
+    Swap(Net& net_, const float* p_, const uint16_t* pb_, const float* bufs_)
+        : n(net_), p(net_.p), pb(net_.pb), bufs(net_.bufs) {
+      n.p = const_cast<float*>(p_);  // the eval-mode forward only reads all three
+      n.pb = const_cast<u16*>(pb_);
+      n.bufs = const_cast<float*>(bufs_);
+    }
+    ~Swap() {
+      n.p = p;
+      n.pb = pb;
+      n.bufs = bufs;
+    }
+  } swap(net->n, params, params_bf16, bufs);
+  return eval_batch(net->n, x, labels, n_valid, topk, logits, rec, (hipStream_t)stream);
+}
+
 int dtc_rn18_backward(dtc_net* net, const float* dlogits, float grad_scale, dtc_comm* comm, void* stream) {
   DTC_CHECK_ARG(net && net->n.ws && dlogits, "dtc_rn18_backward: unbound net or null pointer");
   return backward(net->n, dlogits, grad_scale, (Comm*)comm, (hipStream_t)stream);

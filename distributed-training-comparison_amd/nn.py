@@ -120,6 +120,15 @@ class FlatState:
         ops.cast_f32_bf16(self.params, self.params_bf16)
 
 
+def _check_weights(flat: FlatState, weights) -> None:
+    """`weights` must hold params / params_bf16 / bufs tensors shaped and placed as `flat`'s."""
+    for attr in ("params", "params_bf16", "bufs"):
+        t, own = getattr(weights, attr, None), getattr(flat, attr)
+        if not isinstance(t, torch.Tensor) or t.dtype != own.dtype or t.shape != own.shape or t.device != own.device:
+            raise NativeError(f"weights.{attr} must be a {own.dtype} tensor of {own.numel()} elements on {own.device} "
+                              "(the model's flat layout)")
+
+
 class Executor:
     """One native executor (plan + workspace) for a fixed (batch, height, width)."""
 
@@ -153,15 +162,22 @@ class Executor:
         return self.generation
 
     def eval_batch(self, x: torch.Tensor, labels: torch.Tensor, n_valid: int, topk: int, rec: torch.Tensor,
-                   logits: Optional[torch.Tensor] = None) -> int:
+                   logits: Optional[torch.Tensor] = None, weights=None) -> int:
         """One evaluation batch (dtc_rn18_eval_batch): the eval-mode forward of the first `n_valid` images of
         x (fp32 NCHW, contiguous) and their loss / top-1 / top-k counts against `labels` (int64) into `rec`
         (a contiguous int32 [4] device tensor, see ops.eval_metrics), enqueued with no host synchronisation.
         `logits` (fp32 [batch, num_classes]) receives the logits when given. The call overwrites the
         BatchNorm statistics a training forward saved, so it starts a new generation: a backward still
-        pending on an earlier training forward is refused by consume()."""
-        call("dtc_rn18_eval_batch", self.handle, ptr(x), ptr(labels), int(n_valid), int(topk), ptr(logits), ptr(rec),
-             stream_ptr())
+        pending on an earlier training forward is refused by consume(). `weights` (anything with `params`,
+        `params_bf16` and `bufs` tensors of the model's layout on its device, e.g. a ModelEma) evaluates those
+        instead of the bound buffers (dtc_rn18_eval_batch_weights), which stay bound and untouched."""
+        if weights is not None:
+            _check_weights(self.flat, weights)
+            ops.eval_batch_weights(self.handle, weights.params, weights.params_bf16, weights.bufs, x, labels, n_valid,
+                                   topk, rec, logits)
+        else:
+            call("dtc_rn18_eval_batch", self.handle, ptr(x), ptr(labels), int(n_valid), int(topk), ptr(logits),
+                 ptr(rec), stream_ptr())
         self.generation += 1
         return self.generation
 
@@ -847,7 +863,7 @@ class ResNet(nn.Module):
         return _NetFn.apply(x, self._anchor, self, exe)
 
     # ------------------------------------------------------------------ evaluation
-    def evaluate(self, batches, topk: int = 5) -> EvalResult:
+    def evaluate(self, batches, topk: int = 5, weights=None) -> EvalResult:
         """The reference's validate / test loop (trainer.py:170-215) on the device: for every (images, labels)
         batch one native call enqueues the eval-mode forward and the batch's loss / top-1 / top-k counts into
         the next slot of one device record buffer -- no host synchronisation per batch -- and ONE
@@ -855,8 +871,12 @@ class ResNet(nn.Module):
         recorded for autograd, running statistics are used and left untouched, whatever ``self.training``
         says) in the current ``compute_precision()``. The executor is the one for the first batch's size; a
         smaller batch (the short last one) runs on it through ``n_valid``, a larger one takes the executor
-        of its own size. `batches` needs a length (a list or a loader), else it is materialised first."""
+        of its own size. `batches` needs a length (a list or a loader), else it is materialised first.
+        `weights` (see Executor.eval_batch; e.g. a ModelEma) evaluates other weights of this model's layout in
+        place of its own, which are left untouched."""
         flat = self.flat
+        if weights is not None:
+            _check_weights(flat, weights)
         if not hasattr(batches, "__len__"):
             batches = list(batches)
         precision = self.compute_precision()
@@ -885,7 +905,7 @@ class ResNet(nn.Module):
                 exe = first
                 if n > exe.batch or (h, w) != (exe.height, exe.width):
                     exe = self.executor(n, h, w, precision)
-                exe.eval_batch(x, y, n, topk, recs[i])
+                exe.eval_batch(x, y, n, topk, recs[i], weights=weights)
                 i += 1
         return EvalResult.from_records(recs[:i].cpu(), topk)  # the one device-to-host copy (and wait)
 

@@ -11,7 +11,7 @@ import ctypes as C
 
 import torch
 
-from ._native import SEG_ADAPT, ConvDesc, NativeError, Seg, call, lib, ptr, require_cuda, stream_ptr
+from ._native import SEG_ADAPT, ConvDesc, EmaRange, NativeError, Seg, call, lib, ptr, require_cuda, stream_ptr
 
 
 
@@ -586,6 +586,44 @@ def lars_flat(plan, p, g, mom, pb, lr, weight_decay, momentum, nesterov=False, t
     call("dtc_lars_flat", plan.handle, ptr(p), ptr(g), ptr(mom), ptr(pb), float(lr), float(weight_decay),
          float(momentum), int(bool(nesterov)), float(trust_coef), float(eps), int(bool(trust_clip)), ptr(inv_scale),
          ptr(found_inf), ptr(seg_out), stream_ptr())
+
+
+def eval_batch_weights(net, params, params_bf16, bufs, x, labels, n_valid, topk, rec, logits=None):
+    """dtc_rn18_eval_batch_weights on the executor handle `net`: one evaluation batch read from the given flat
+    parameter / bf16 shadow / running-statistics tensors (the bound buffers' layout) instead of the bound ones."""
+    require_cuda(params, params_bf16, bufs, x, labels, rec, logits)
+    if params.dtype != torch.float32 or params_bf16.dtype != torch.bfloat16 or bufs.dtype != torch.float32:
+        raise NativeError("eval_batch_weights: params / bufs must be fp32 tensors, params_bf16 a bf16 tensor")
+    if not (params.is_contiguous() and params_bf16.is_contiguous() and bufs.is_contiguous()):
+        raise NativeError("eval_batch_weights: contiguous weight tensors only")
+    call("dtc_rn18_eval_batch_weights", net, ptr(params), ptr(params_bf16), ptr(bufs), ptr(x), ptr(labels),
+         int(n_valid), int(topk), ptr(logits), ptr(rec), stream_ptr())
+
+
+def ema_state(device):
+    """The zeroed device state record of one EMA (word 0: the int32 count of updates, word 1: the fp32 weight
+    1 - decay_t of the last update)."""
+    return torch.zeros(lib.dtc_ema_state_words(), dtype=torch.int32, device=device)
+
+
+def ema_update(ranges, state, decay, warmup=False, found_inf=None):
+    """One EMA update over 1..4 flat ranges in one launch behind a one-thread tick (include/dtc.h: dtc_ema_update).
+    `ranges`: (ema, src, ema_bf16 or None) triples of contiguous tensors -- ema += (src - ema) * w, ema_bf16 =
+    bf16(ema); `state` from ema_state(). Nothing changes when `found_inf` (a device int32 word) is non-zero."""
+    ranges = list(ranges)
+    table = (EmaRange * max(1, len(ranges)))()
+    for k, (ema, src, bf) in enumerate(ranges):
+        require_cuda(ema, src, bf)
+        if ema.dtype != torch.float32 or src.dtype != torch.float32 or (bf is not None and bf.dtype != torch.bfloat16):
+            raise NativeError("ema_update: ema and src must be fp32 tensors, ema_bf16 a bf16 tensor")
+        if src.numel() != ema.numel() or (bf is not None and bf.numel() != ema.numel()):
+            raise NativeError(f"ema_update: range {k}: ema, src and ema_bf16 must have one size")
+        if not (ema.is_contiguous() and src.is_contiguous() and (bf is None or bf.is_contiguous())):
+            raise NativeError(f"ema_update: range {k}: contiguous tensors only")
+        table[k] = EmaRange(ptr(ema), ptr(src), ptr(bf), ema.numel())
+    require_cuda(state, found_inf)
+    call("dtc_ema_update", table, len(ranges), ptr(state), float(decay), int(bool(warmup)), ptr(found_inf),
+         stream_ptr())
 
 
 def cast_f32_bf16(src, dst):

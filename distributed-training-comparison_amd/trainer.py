@@ -21,6 +21,7 @@ import torch.distributed as dist
 
 from . import data as D
 from .amp import GradScaler, autocast
+from .ema import ModelEma
 from .nn import CrossEntropyLoss, ResNet18, SyncBatchNorm
 from .optim import LARS, SGD, Adam, AdamW, clip_grad_norm_
 from .parallel import DDP, DataParallel, barrier
@@ -73,6 +74,14 @@ def load_config(argv=None, mode: str = "ddp"):
                    help="CutMix with lam ~ Beta(alpha, alpha) per batch, on the device (needs --device-data; 0 = off)")
     p.add_argument("--mix-prob", type=float, default=1.0,
                    help="probability that a batch is mixed; with both alphas set each kind is picked half the time")
+    # timm's / torchvision's --model-ema: the weights worth keeping at large batches and under Mixup / CutMix
+    p.add_argument("--model-ema", action="store_true", default=False,
+                   help="keep an exponential moving average of the weights and running statistics on the device "
+                        "(ema.ModelEma); validate() reports it, the best checkpoint stores it")
+    p.add_argument("--model-ema-decay", type=float, default=0.9998, help="--model-ema: decay, in [0, 1)")
+    p.add_argument("--model-ema-warmup", action="store_true", default=False,
+                   help="--model-ema: decay_t = min(decay, (1 + t) / (10 + t)) over the updates t")
+    p.add_argument("--model-ema-steps", type=int, default=1, help="--model-ema: update on every N-th global step")
     # synthetic-data size knobs (not in the reference: CIFAR-100 cannot be downloaded here)
     p.add_argument("--synthetic-train", type=int, default=50000)
     p.add_argument("--synthetic-test", type=int, default=10000)
@@ -94,6 +103,8 @@ def load_config(argv=None, mode: str = "ddp"):
         p.error("--warmup-epochs must be >= 0 and --lars-trust-coef > 0")
     if (h.mixup_alpha > 0 or h.cutmix_alpha > 0) and not h.device_data:
         p.error("--mixup-alpha / --cutmix-alpha need --device-data (the host loader does not mix)")
+    if not 0.0 <= h.model_ema_decay < 1.0 or h.model_ema_steps < 1:
+        p.error("--model-ema-decay must be in [0, 1) and --model-ema-steps >= 1")
     return h
 
 
@@ -168,6 +179,12 @@ class Trainer:
         self.scaler = scaler
         self.optimizer, self.lr_scheduler = self.configure_optimizers()
         self.criterion, self.eval_criterion = make_criteria(hparams)
+        # --model-ema: every DDP rank keeps its own (identical) EMA; under DataParallel it follows the master
+        # module on device_ids[0]. Built behind the wrappers, so it starts from the broadcast weights.
+        self.ema = None
+        self.val_raw_acc = None
+        if getattr(hparams, "model_ema", False):
+            self.ema = ModelEma(self.model, decay=hparams.model_ema_decay, warmup=hparams.model_ema_warmup)
         if getattr(hparams, "device_data", False):
             self._device_loaders(hparams, distributed)
         else:
@@ -241,7 +258,12 @@ class Trainer:
         new_path = os.path.join(self.save_path, f"best_model_epoch_{epoch}_acc_{val_acc:.4f}.pt")
         for filename in glob.glob(os.path.join(self.save_path, "*.pt")):
             os.remove(filename)
-        torch.save({k: v.contiguous() for k, v in model.state_dict().items()}, new_path)
+        state = model.state_dict()
+        if self.ema is not None:  # the averaged weights under the model's own keys: test() loads them as ever
+            ema_state = self.ema.state_dict()
+            prefix = "module." if (self.distributed or self.data_parallel) else ""
+            state = {k: ema_state[k[len(prefix):]] for k in state}
+        torch.save({k: v.contiguous() for k, v in state.items()}, new_path)
         self.global_top1_acc = val_acc
 
     def fit(self):
@@ -275,6 +297,7 @@ class Trainer:
                     self.scaler.unscale_(self.optimizer)
                     clip_grad_norm_(self.model.parameters(), self.hparams.clip_grad_norm, scaler=self.scaler)
                 self.scaler.step(self.optimizer)
+                self._ema_update(self.scaler.found_inf)  # before update(), which clears found_inf
                 self.scaler.update()
             else:
                 logit = self.model(img)
@@ -285,6 +308,7 @@ class Trainer:
                 if self.hparams.clip_grad_norm > 0:
                     clip_grad_norm_(self.model.parameters(), self.hparams.clip_grad_norm)
                 self.optimizer.step()
+                self._ema_update(None)
             train_loss.update(loss.item())
             self.global_step += 1
             if self.rank == 0 and self.global_step % self.eval_step == 0:
@@ -296,7 +320,10 @@ class Trainer:
             val_loss, val_acc = self.validate(epoch)
             self._log_scalar("lr", {"lr": self.optimizer.param_groups[0]["lr"]}, epoch)
             self._log_scalar("loss/epoch", {"val": val_loss, "train": train_loss.avg}, epoch)
-            self._log_scalar("acc/epoch", {"val": val_acc}, epoch)
+            acc = {"val": val_acc}
+            if self.ema is not None:
+                acc["val_raw"] = self.val_raw_acc
+            self._log_scalar("acc/epoch", acc, epoch)
             logging.info(f"** global step: {self.global_step}, val loss: {val_loss:.3f}, val_acc: {val_acc:.2f}%")
             result.update(val_loss=val_loss, val_acc=val_acc)
         return result
@@ -323,7 +350,23 @@ class Trainer:
             out.append(meter)
         return out
 
+    def _ema_update(self, found_inf) -> None:
+        """--model-ema: one update right after the optimizer step, on every --model-ema-steps-th global step (the
+        step in progress is global_step + 1). A GradScaler-skipped step updates nothing: the kernel reads
+        `found_inf` on the device."""
+        if self.ema is not None and (self.global_step + 1) % self.hparams.model_ema_steps == 0:
+            self.ema.update(found_inf=found_inf)
+
     def validate(self, epoch: int) -> Tuple[float, float]:
+        """With --model-ema: the EMA's loss and accuracy (on the device, whatever --fused-eval says), which
+        therefore select the best checkpoint; the raw weights' accuracy is kept in ``val_raw_acc`` for the log."""
+        if self.ema is None:
+            return self._validate_raw(epoch)
+        m = self.ema.evaluate(self.val_loader, topk=1).reference_meters()
+        self.val_raw_acc = self._validate_raw(epoch)[1]
+        return m["loss"], m["top1"]
+
+    def _validate_raw(self, epoch: int) -> Tuple[float, float]:
         if getattr(self.hparams, "fused_eval", False):
             val_loss, top1, _ = self._fused_meters(self.val_loader, 1)
             return val_loss.avg, top1.avg

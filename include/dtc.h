@@ -322,6 +322,25 @@ int dtc_seg_norms(dtc_segplan* plan, const float* p, const float* g, const float
 int dtc_lars_flat(dtc_segplan* plan, float* p, const float* g, float* momentum_buf, uint16_t* p_bf16, double lr,
                   double weight_decay, double momentum, int nesterov, double trust_coef, double eps, int trust_clip,
                   const float* inv_scale, const int* found_inf, float* seg_out, void* stream);
+/* ema: an exponential moving average of the weights (timm ModelEma, torchvision's --model-ema,
+ * tf.train.ExponentialMovingAverage) over 1..4 flat ranges in ONE update launch -- a model's parameters and its
+ * BatchNorm running statistics together. Per element of every range
+ *   ema += (src - ema) * w   (one fused multiply-add);   ema_bf16 = bf16(ema) where ema_bf16 != NULL
+ *                             (dtc_cast_f32_bf16's rounding: the EMA's own GEMM-operand shadow)
+ * with w = (float)(1 - decay), or with warmup != 0 w = (float)(1 - min(decay, (1 + t) / (10 + t))), formed in double
+ * and rounded once, t being the count of updates including this one. `state` is dtc_ema_state_words() (= 4) 32-bit
+ * words of device memory, 16-byte aligned, zeroed by the caller before the first call: word 0 is the int32 count t
+ * of updates applied, word 1 the fp32 w of the last update, the rest reserved. When *found_inf != 0 (NULL: never)
+ * nothing happens: ema, ema_bf16 and state stay bit-unchanged -- a skipped optimizer step is not an update. Two
+ * launches (a one-thread tick that advances t and writes w, then the update, its blocks shared among the ranges in
+ * proportion to their lengths), no host synchronisation, no atomics, bit-identical from run to run; 14 bytes of
+ * HBM traffic per element with a bf16 copy. Requires (else DTC_EINVAL, before any device call): 1 <= nranges <= 4;
+ * n a positive multiple of 4; ema and src 16-byte, ema_bf16 8-byte aligned; [ema, ema + n) overlapping neither
+ * [src, src + n) nor another entry's ema; decay in [0, 1). */
+typedef struct { float* ema; const float* src; uint16_t* ema_bf16; int64_t n; } dtc_ema_range;
+int dtc_ema_state_words(void);
+int dtc_ema_update(const dtc_ema_range* ranges, int nranges, void* state, double decay, int warmup,
+                   const int* found_inf, void* stream);
 int dtc_cast_f32_bf16(const float* src, uint16_t* dst, int64_t n, void* stream);
 int dtc_amp_check_finite(const float* g, int64_t n, int* found_inf, void* stream);
 /* GradScaler.scale(loss): out = x * (*scale) with the scale device-resident (no host sync) */
@@ -510,6 +529,14 @@ int dtc_rn18_xent_soft_backward(dtc_net* net, const float* logits, const int64_t
  * saved mean / invstd of every BatchNorm, so a backward of an earlier training forward must not follow. */
 int dtc_rn18_eval_batch(dtc_net* net, const float* x, const int64_t* labels, int n_valid, int topk, float* logits,
                         dtc_eval_record* rec, void* stream);
+/* dtc_rn18_eval_batch reading the parameters, their bf16 shadow and the running statistics from the three given
+ * buffers (e.g. an EMA of the weights, dtc_ema_update) instead of the bound ones: the bound buffers' layout, all
+ * three non-NULL, params and params_bf16 16-byte aligned as for dtc_rn18_bind. The bound buffers are neither read
+ * nor written and stay bound; no graph is dropped or captured (always eager, both precisions -- the fp32 executor
+ * does not read params_bf16). Everything else, the overwritten saved mean / invstd included, as dtc_rn18_eval_batch. */
+int dtc_rn18_eval_batch_weights(dtc_net* net, const float* params, const uint16_t* params_bf16, const float* bufs,
+                                const float* x, const int64_t* labels, int n_valid, int topk, float* logits,
+                                dtc_eval_record* rec, void* stream);
 /* Byte offset into the workspace of the executor's own fp32 [batch][num_classes] dlogits buffer.
  * A caller that writes the loss gradient there (e.g. the fused cross-entropy backward) and passes
  * that pointer to dtc_rn18_backward saves the graph path's copy-in. */
