@@ -1,7 +1,8 @@
 // BatchNorm-backward arguments of a data gradient (conv_dgrad's `bnb`, dtc_conv2d_dgrad_bn): in the
 // executor's backward every data gradient a conv produces is the gradient dy of a post-ReLU BN output,
 // y = relu(bn(x) [+ shortcut]) (reference src/*/net.py:41-44, 108); with these arguments the conv is followed
-// by that BN's backward reduction (bn_bwd_reduce / _mask, bn.hip: sum(dz), sum(dz * xhat) into fp64 slots).
+// by that BN's backward reduction (bn_bwd_reduce / _mask, bn.hip: sum(dz), sum(dz * xhat) into the exact
+// int64 fixed-point slots of common.h).
 // (Rounds 3-4 also accumulated the sums in the dgrad epilogues -- options bnb_fuse / bnb_mask -- which
 // measured slower than the separate pass in-step and were removed in round 5: DESIGN.md.)
 #pragma once

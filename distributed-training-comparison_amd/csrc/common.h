@@ -2,7 +2,7 @@
 //
 // Conventions used by every kernel in this library:
 //   * activations are NHWC bf16 (raw 16-bit words, `u16`), channels innermost;
-//   * master parameters / gradients are fp32 in one flat buffer (see resnet.cpp);
+//   * master parameters / gradients are fp32 in one flat buffer (see net_plan.cpp);
 //   * conv weights are K x R x S x C ("KRSC"), so one output channel's filter is a
 //     contiguous row of R*S*C elements: that row is the GEMM operand directly;
 //   * every launch takes the caller's hipStream_t; nothing here allocates memory.
@@ -41,7 +41,7 @@ const char* last_error();
 
 // ---------------------------------------------------------------- launches
 // Every kernel of the library is launched through DTC_KLAUNCH, which notes a launch on the stream a side stream
-// was last forked from (resnet.cpp: a second fork from the same point -- a bucket's collective right after its
+// was last forked from (net_run.cpp: a second fork from the same point -- a bucket's collective right after its
 // weight-gradient flush -- then needs no second event record; a record costs the recording stream a ~2.7 us
 // bubble before its next kernel, tools/probes/fork_gap.hip).
 namespace dtc {

@@ -104,25 +104,26 @@ int conv_fwd(const ConvShape& s, const u16* x, const u16* w, u16* y, int64_t* st
 bool conv_fwd_sc_ok(const ConvShape& s, const ConvShape& sc);
 int conv_fwd_sc(const ConvShape& s, const ConvShape& sc, const u16* x, const u16* w, u16* y, int64_t* stats,
                 const u16* wsc, u16* ysc, int64_t* stats_sc, hipStream_t st, u64* ts = nullptr);
-// dx = conv_transpose(dy, w) (+ res), bf16 NHWC.
-// bnb (optional): dx is the gradient of a post-ReLU BN output; store dz = dx * [bnb->ym > 0] instead
-// and accumulate the BN-backward sums (bn_bwd_reduce's work) -- in the epilogue where the kernel
-// supports it (conv_c64, conv_halo, split-K reduce), else by a bn_bwd_reduce pass after the conv.
-// dx may alias res (in place: each element is read and written by the same lane).
 // true when conv_dgrad(s) takes the stride-2 parity-class path (the one a compact residual needs)
 bool dgrad_class_ok(const ConvShape& s);
-// res_compact: res is [N][H/2][W/2][C] (a 1x1 stride-2 shortcut's dx at its only nonzero parity),
-// added at the (even, even) pixels only -- stride-2 parity-class dgrads.
-// dx = dgrad(dy, w) + dgrad_1x1_s2(dsc, wsc) for a projection block's 3x3 stride-2 conv1 and its shortcut
-// in one parity-class launch (dsc [N][H/2][W/2][K], wsc [K][C])
+// true when conv_dgrad_sc takes s (a projection block's 3x3 stride-2 conv1)
 bool conv_dgrad_sc_ok(const ConvShape& s);
 // stride-2 3x3 pad-1 dgrad as a halo-tiled sub-pixel convolution (dgrad_s2.hip), optionally + the 1x1 stride-2
 // shortcut's dgrad (dsc [N][H/2][W/2][K], wsc [K][C]) at the even / even pixels
 bool dgrad_s2_halo_ok(const ConvShape& s);
 int conv_dgrad_s2_halo(const ConvShape& s, const u16* dy, const u16* w, u16* dx, const u16* dsc, const u16* wsc,
                        hipStream_t st, u64* ts = nullptr);
+// dx = dgrad(dy, w) + dgrad_1x1_s2(dsc, wsc) for a projection block's 3x3 stride-2 conv1 and its shortcut
+// in one parity-class launch (dsc [N][H/2][W/2][K], wsc [K][C])
 int conv_dgrad_sc(const ConvShape& s, const u16* dy, const u16* w, u16* dx, const u16* dsc, const u16* wsc,
                   hipStream_t st, u64* ts = nullptr, const BnbArgs* bnb = nullptr);
+// dx = conv_transpose(dy, w) (+ res), bf16 NHWC.
+// bnb (optional): dx is the gradient of a post-ReLU BN output; store dz = dx * [bnb->ym > 0] instead
+// and accumulate the BN-backward sums (bn_bwd_reduce's work) -- in the epilogue where the kernel
+// supports it (conv_c64, conv_halo, split-K reduce), else by a bn_bwd_reduce pass after the conv.
+// dx may alias res (in place: each element is read and written by the same lane).
+// res_compact: res is [N][H/2][W/2][C] (a 1x1 stride-2 shortcut's dx at its only nonzero parity),
+// added at the (even, even) pixels only -- stride-2 parity-class dgrads.
 int conv_dgrad(const ConvShape& s, const u16* dy, const u16* w, u16* dx, const u16* res, float* slab,
                size_t slab_bytes, hipStream_t st, u64* ts = nullptr, const BnbArgs* bnb = nullptr,
                int res_compact = 0, unsigned* tick = nullptr);

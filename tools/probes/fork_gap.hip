@@ -1,7 +1,7 @@
 // Probe: the main-stream bubble a side-stream fork costs (round 6). Two busy kernels K1, K2 on stream A with,
 // between them, one of:
 //   0  nothing
-//   1  hipEventRecord(e, A) + hipStreamWaitEvent(B, e) + a busy kernel on B  (resnet.cpp fork_side today)
+//   1  hipEventRecord(e, A) + hipStreamWaitEvent(B, e) + a busy kernel on B  (net_run.cpp fork_side today)
 //   2  K1 launched with hipExtLaunchKernelGGL(..., stop event e) + hipStreamWaitEvent(B, e) + kernel on B
 //   3  hipEventRecord(e, A) alone (no waiter)
 //   4  K1 launched with a stop event, no waiter (the cost of the event on a kernel nobody waits for)
