@@ -527,6 +527,9 @@ int dtc_ema_update(const dtc_ema_range* ranges, int nranges, void* state, double
                    const int* found_inf, void* stream) {
   return ema_update((const EmaRange*)ranges, nranges, state, decay, warmup, found_inf, S(stream));
 }
+int dtc_grad_accum_flat(float* acc, float* g, int64_t n, int mode, void* stream) {
+  return grad_accum(acc, g, n, mode, S(stream));
+}
 int dtc_cast_f32_bf16(const float* src, uint16_t* dst, int64_t n, void* stream) {
   return cast_f32_bf16(src, dst, n, S(stream));
 }

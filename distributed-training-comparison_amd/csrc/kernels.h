@@ -426,6 +426,13 @@ struct EmaRange {  // layout of the ABI's dtc_ema_range
 };
 int ema_update(const EmaRange* ranges, int nranges, void* state, double decay, int warmup, const int* found_inf,
                hipStream_t st);
+// Gradient accumulation (accum.hip) over one fp32 range, mode = the ABI's DTC_ACCUM_STORE / ADD / FINISH: acc = g,
+// acc = acc + g, g = g + acc, one rounded fp32 add per element. A workgroup of DTC_ACCUM_THREADS takes chunks of
+// DTC_ACCUM_THREADS * DTC_ACCUM_UNROLL float4 rows; the grid is capped at DTC_ACCUM_MAX_BLOCKS. One launch.
+#define DTC_ACCUM_THREADS 256
+#define DTC_ACCUM_UNROLL 4
+#define DTC_ACCUM_MAX_BLOCKS 1024
+int grad_accum(float* acc, float* g, int64_t n, int mode, hipStream_t st);
 int cast_f32_bf16(const float* src, u16* dst, int64_t n, hipStream_t st);
 // zero an 8-byte aligned range (a kernel node, unlike hipMemsetAsync's fill dispatch)
 int zero_bytes(void* p, size_t bytes, hipStream_t st);

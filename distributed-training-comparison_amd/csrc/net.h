@@ -169,6 +169,10 @@ struct Net {
   // (its own, never the Reducer's, so the two collective streams cannot interleave on one comm)
   Comm* sync = nullptr;
   int sync_world = 1;
+  // Gradient accumulation (dtc_rn18_set_grad_accum): the mode of the next backwards (DTC_ACCUM_*) and the
+  // caller-owned buffer in the gradient buffer's layout; applied per bucket at the plan's bucket points
+  int accum_mode = 0;
+  float* accum = nullptr;
   // layers
   std::vector<ParamEntry> params;
   int64_t flat_numel = 0;

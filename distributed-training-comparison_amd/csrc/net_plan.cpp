@@ -382,6 +382,8 @@ int dtc_rn18_bind(dtc_net* net, void* workspace, float* params, float* grads, ui
   n.mem.pb = params_bf16;
   n.mem.bufs = bufs;
   n.mem.nbt = num_batches_tracked;
+  n.accum_mode = DTC_ACCUM_OFF;  // the accumulation buffer was checked against the previous gradients
+  n.accum = nullptr;
   n.prof.ts = n.at<u64>(n.plan.PROF_TS);
   n.prof.acc = n.at<u64>(n.plan.PROF_ACC);
   drop_graphs(n);  // captured launches hold the previous pointers
@@ -419,6 +421,26 @@ int dtc_rn18_activation_info(const dtc_net* net, int idx, const char** name, siz
 int dtc_rn18_dlogits_buffer(const dtc_net* net, size_t* ws_offset) {
   DTC_CHECK_ARG(net && ws_offset, "dtc_rn18_dlogits_buffer: bad args");
   *ws_offset = net->n.plan.DLOGITS;
+  return 0;
+}
+
+int dtc_rn18_set_grad_accum(dtc_net* net, float* acc, int mode) {
+  DTC_CHECK_ARG(net != nullptr, "dtc_rn18_set_grad_accum: null net");
+  DTC_CHECK_ARG(mode >= DTC_ACCUM_OFF && mode <= DTC_ACCUM_FINISH, "dtc_rn18_set_grad_accum: mode = %d outside [0, 3]",
+                mode);
+  Net& n = net->n;
+  if (mode != DTC_ACCUM_OFF) {
+    DTC_CHECK_ARG(acc != nullptr, "dtc_rn18_set_grad_accum: mode %d needs an accumulation buffer (acc is NULL)", mode);
+    DTC_CHECK_ARG(n.mem.g != nullptr, "dtc_rn18_set_grad_accum: call after dtc_rn18_bind");
+  }
+  if (acc != nullptr) {
+    DTC_CHECK_ARG(((uintptr_t)acc & 15) == 0, "dtc_rn18_set_grad_accum: acc must be 16-byte aligned");
+    const uintptr_t a0 = (uintptr_t)acc, g0 = (uintptr_t)n.mem.g, bytes = (uintptr_t)n.flat_numel * 4;
+    DTC_CHECK_ARG(n.mem.g == nullptr || a0 + bytes <= g0 || g0 + bytes <= a0,
+                  "dtc_rn18_set_grad_accum: acc overlaps the bound gradient buffer");
+  }
+  n.accum = acc;
+  n.accum_mode = mode;
   return 0;
 }
 

@@ -77,6 +77,9 @@ static int graph_launch(Net& n, hipGraphExec_t ex, hipStream_t st) {
 static bool graphs_on(Net& n, bool bwd, bool comm = false) {
   const int g = option_get(OPT_GRAPHS);
   if (n.capture || n.sync || g == 0 || (g == 2 && bwd) || (g == 3 && !bwd)) return false;
+  // an accumulating backward (dtc_rn18_set_grad_accum) runs eagerly and leaves the captured graphs alone: the
+  // mode alternates from step to step, and the next plain backward replays what was captured before
+  if (bwd && n.accum_mode != DTC_ACCUM_OFF) return false;
   if (g == 4 && (!bwd || !(comm && option_get(OPT_COMM_ON_SIDE) == 0))) return false;
   if (n.graph.epoch != option_epoch()) {  // options are baked into captured launches
     drop_graphs(n);
@@ -553,7 +556,8 @@ static int issue_bucket(Net& n, Comm* comm, int i, hipStream_t stream, bool on_s
 // are complete now. Capturing: close the current graph segment there and open the next one; the
 // replay issues the all-reduces between segments.
 static int maybe_bucket(Net& n, int after_block, const BwdCtx& cx, hipStream_t st) {
-  if (!cx.comm) return 0;
+  const int accum = n.accum_mode;
+  if (!cx.comm && accum == DTC_ACCUM_OFF) return 0;
   std::vector<int> ids;
   for (size_t i = 0; i < n.plan.bucket_off.size(); ++i)
     if (n.plan.bucket_after_block[i] == after_block) ids.push_back((int)i);
@@ -569,6 +573,20 @@ static int maybe_bucket(Net& n, int after_block, const BwdCtx& cx, hipStream_t s
       // (a flush's fork right before this point already ordered it: no second marker)
       if (!side_covers(st)) DTC_TRY(side_wait(n, st));
       prod = n.side.st;
+    }
+    // Gradient accumulation (dtc_rn18_set_grad_accum): one launch over the contiguous range of the buckets
+    // complete here, on the stream that holds both producers, so it overlaps the rest of the backward as the
+    // collective does. STORE / ADD keep the sum in n.accum and reduce nothing (the entry points refuse a
+    // communicator); FINISH adds the sum onto the gradients ahead of the buckets' collectives below, which are
+    // ordered after `prod`.
+    if (accum != DTC_ACCUM_OFF) {
+      int64_t lo = n.plan.bucket_off[ids[0]], hi = lo;
+      for (int i : ids) {
+        lo = std::min(lo, n.plan.bucket_off[i]);
+        hi = std::max(hi, n.plan.bucket_off[i] + n.plan.bucket_len[i]);
+      }
+      DTC_TRY(grad_accum(n.accum + lo, n.mem.g + lo, hi - lo, accum, prod));
+      if (!cx.comm) return 0;
     }
     // option comm_on_side: the collective on the weight-gradient stream itself (it holds both producers
     // now; the stream is joined into the compute stream at the end of the backward) -- one HIP stream
@@ -1109,6 +1127,15 @@ static int xent_backward(Net& n, const XentArgs& xa, Unfused unfused, float gs, 
   return backward(n, dl, gs, comm, st);
 }
 
+// STORE / ADD accumulate locally and reduce nothing (DDP's no_sync): a communicator there is a caller's mistake,
+// refused before any launch
+static int accum_args_ok(const char* fn, const Net& n, const void* comm) {
+  DTC_CHECK_ARG(!(comm && (n.accum_mode == DTC_ACCUM_STORE || n.accum_mode == DTC_ACCUM_ADD)),
+                "%s: gradient accumulation mode %d (STORE / ADD) takes no communicator: pass comm = NULL and "
+                "all-reduce in the finishing backward", fn, n.accum_mode);
+  return 0;
+}
+
 // the checks the two eval_batch entry points share, reported under the caller's name
 static int eval_args_ok(const char* fn, const dtc_net* net, const float* x, const int64_t* labels, int n_valid,
                         int topk, const dtc_eval_record* rec) {
@@ -1166,12 +1193,14 @@ int dtc_rn18_eval_batch_weights(dtc_net* net, const float* params, const uint16_
 
 int dtc_rn18_backward(dtc_net* net, const float* dlogits, float grad_scale, dtc_comm* comm, void* stream) {
   DTC_CHECK_ARG(net && net->n.mem.ws && dlogits, "dtc_rn18_backward: unbound net or null pointer");
+  DTC_TRY(accum_args_ok("dtc_rn18_backward", net->n, comm));
   return backward(net->n, dlogits, grad_scale, (Comm*)comm, (hipStream_t)stream);
 }
 
 int dtc_rn18_xent_backward(dtc_net* net, const float* logits, const int64_t* labels, const float* lse,
                            const float* gscale, float grad_scale, dtc_comm* comm, void* stream) {
   DTC_CHECK_ARG(net && net->n.mem.ws && logits && labels && lse, "dtc_rn18_xent_backward: unbound net or null pointer");
+  DTC_TRY(accum_args_ok("dtc_rn18_xent_backward", net->n, comm));
   Net& n = net->n;
   hipStream_t st = (hipStream_t)stream;
   const XentArgs xa{logits, labels, lse, gscale};
@@ -1187,6 +1216,7 @@ int dtc_rn18_xent_soft_backward(dtc_net* net, const float* logits, const int64_t
   DTC_CHECK_ARG((labels_b != nullptr) == (lam != nullptr) && smoothing >= 0.f && smoothing <= 1.f,
                 "dtc_rn18_xent_soft_backward: labels_b and lam go together, smoothing = %g must be in [0, 1]",
                 (double)smoothing);
+  DTC_TRY(accum_args_ok("dtc_rn18_xent_soft_backward", net->n, comm));
   Net& n = net->n;
   hipStream_t st = (hipStream_t)stream;
   const XentArgs xa{logits, labels_a, lse, gscale, labels_b ? labels_b : labels_a, lam, smoothing, true};

@@ -15,6 +15,7 @@ Mirror of the reference's operator boundary (src/ddp/net.py, trainer.py:40):
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import threading
 import weakref
@@ -115,6 +116,14 @@ class FlatState:
         self.grad_mult = None
         self.norm_ws = None
         self.clip_pending = False
+        self._grad_acc = None
+
+    @property
+    def grad_acc(self) -> torch.Tensor:
+        """The gradient-accumulation buffer (ResNet.accumulate): the layout of `grads`, allocated on first use."""
+        if self._grad_acc is None:
+            self._grad_acc = torch.zeros_like(self.grads)
+        return self._grad_acc
 
     def refresh_bf16(self):
         ops.cast_f32_bf16(self.params, self.params_bf16)
@@ -153,6 +162,7 @@ class Executor:
         self.generation = 0
         self._bwd_gen = 0  # generation whose forward a backward has consumed (one backward per forward)
         self._dlogits = None
+        self._accum_mode = ops.ACCUM_OFF  # dtc_rn18_bind leaves the executor there
         call("dtc_rn18_bind", self.handle, self.ws_ptr, ptr(flat.params), ptr(flat.grads), ptr(flat.params_bf16),
              ptr(flat.bufs), ptr(flat.nbt), stream_ptr())
 
@@ -194,6 +204,14 @@ class Executor:
                               "would accumulate gradients in torch; the native kernels write them): run "
                               "the forward again")
         self._bwd_gen = gen
+
+    def set_grad_accum(self, mode: int) -> None:
+        """The accumulation mode of the next backwards (dtc_rn18_set_grad_accum, sticky), on the model's
+        `flat.grad_acc`; the library is called only when the mode changes."""
+        if mode != self._accum_mode:
+            call("dtc_rn18_set_grad_accum", self.handle, None if mode == ops.ACCUM_OFF else ptr(self.flat.grad_acc),
+                 int(mode))
+            self._accum_mode = mode
 
     def backward(self, dlogits: torch.Tensor, grad_scale: float, comm) -> None:
         call("dtc_rn18_backward", self.handle, ptr(dlogits), float(grad_scale), comm.handle if comm else None,
@@ -280,7 +298,9 @@ class _NetFn(torch.autograd.Function):
         if model._pre_backward is not None:
             model._pre_backward()
         exe.consume(ctx.gen)
-        exe.backward(dlogits.contiguous().float(), model._grad_scale, model._comm)
+        grad_scale, comm = model._begin_backward(exe)
+        exe.backward(dlogits.contiguous().float(), grad_scale, comm)
+        model._end_backward()
         model._ensure_grads()
         return None, None, None, None
 
@@ -410,10 +430,12 @@ class NativeLoss(torch.Tensor):
             if model._pre_backward is not None:
                 model._pre_backward()
             exe.consume(node.gen)
+            grad_scale, comm = model._begin_backward(exe)
             if isinstance(labels, _Soft):
-                exe.xent_soft_backward(logits, labels, lse, gscale, model._grad_scale, model._comm)
+                exe.xent_soft_backward(logits, labels, lse, gscale, grad_scale, comm)
             else:
-                exe.xent_backward(logits, labels, lse, gscale, model._grad_scale, model._comm)
+                exe.xent_backward(logits, labels, lse, gscale, grad_scale, comm)
+            model._end_backward()
             model._ensure_grads()
         else:  # DataParallel's gathered logits: xent backward, then the replicas' backward + reduce-add
             from .parallel import _DPFn
@@ -427,6 +449,16 @@ class NativeLoss(torch.Tensor):
         if not retain_graph:
             self._dtc_fast = None
         return None
+
+    # loss * c, c * loss, loss / c (e.g. the `loss / N` of a hand-written accumulation loop): the autograd form, so
+    # the product back-propagates (the value held here has no history of its own)
+    def __mul__(self, other):
+        return self._dtc_graph * other
+
+    __rmul__ = __mul__
+
+    def __truediv__(self, other):
+        return self._dtc_graph / other
 
     def item(self):
         """The loss value from the pinned host copy enqueued right after the loss kernel: waits
@@ -720,6 +752,12 @@ class ResNet(nn.Module):
         self._comm = None
         self._grad_scale = 1.0
         self._pre_backward = None  # set by DistributedDataParallel: runs before every native backward
+        # gradient accumulation: the micro-batches per optimizer step (divides the executor's grad_scale, so a
+        # window's gradient is the mean over its micro-batches), the nesting depth of accumulate() and whether a
+        # window is open (flat.grad_acc holds the sum of the backwards run inside accumulate() so far)
+        self.grad_accum_steps = 1
+        self._accum_depth = 0
+        self._accum_open = False
         self._bucket_cap_mb = float(bucket_cap_mb)
         self._capture = False
         self._sync_bn = False  # SyncBatchNorm.convert_sync_batchnorm marks the module
@@ -850,6 +888,55 @@ class ResNet(nn.Module):
         """Keep backward intermediates for per-layer parity tests (new executors only)."""
         self._capture = on
         self._executors.clear()
+
+    # ------------------------------------------------------------------ gradient accumulation
+    @contextlib.contextmanager
+    def accumulate(self):
+        """Accumulate gradients over micro-batches: the standard N x (forward, backward), one optimizer.step()
+        loop. The native kernels write gradients, so the sum is kept in ``flat.grad_acc``. A backward inside
+        this context adds its gradients there (the first of a window stores them) and all-reduces nothing --
+        under DistributedDataParallel this is ``no_sync()``. The first backward OUTSIDE the context closes the
+        window: its gradients plus the accumulated sum land in ``.grad`` / ``flat.grads`` ahead of each bucket's
+        all-reduce, so the collective (and then GradScaler's finiteness check, clipping and the optimizer) sees
+        the whole window. With no window open a backward is exactly the plain one.
+
+            model.grad_accum_steps = N                    # gradients become the mean over the N micro-batches
+            for i, (x, y) in enumerate(micro_batches):
+                with model.accumulate() if i < N - 1 else contextlib.nullcontext():
+                    criterion(model(x), y).backward()
+            optimizer.step()
+
+        ``grad_accum_steps`` divides the gradient scale of every backward, so the loss needs no ``/ N`` (and
+        ``NativeLoss.backward`` keeps its direct path); with ``grad_accum_steps = 1`` a ``(loss / N).backward()``
+        through autograd gives the same mean. ``.grad`` between the backwards of a window shows the last
+        micro-batch's gradients, not the running sum."""
+        self._accum_depth += 1
+        try:
+            yield self
+        finally:
+            self._accum_depth -= 1
+
+    def reset_accumulation(self) -> None:
+        """Drop an open accumulation window: the next backward outside accumulate() is a plain one."""
+        self._accum_open = False
+
+    def _begin_backward(self, exe: Executor):
+        """(grad_scale, comm) of the native backward about to run on `exe`, whose accumulation mode is set
+        from the window's state: STORE / ADD without a communicator inside accumulate(), FINISH for the backward
+        that closes a window, OFF otherwise."""
+        steps = self.grad_accum_steps
+        if not isinstance(steps, int) or steps < 1:
+            raise ValueError(f"grad_accum_steps must be an integer >= 1, not {steps!r}")
+        comm = self._comm
+        if self._accum_depth > 0:
+            mode, comm = (ops.ACCUM_ADD if self._accum_open else ops.ACCUM_STORE), None
+        else:
+            mode = ops.ACCUM_FINISH if self._accum_open else ops.ACCUM_OFF
+        exe.set_grad_accum(mode)
+        return self._grad_scale / steps, comm
+
+    def _end_backward(self) -> None:
+        self._accum_open = self._accum_depth > 0
 
     # ------------------------------------------------------------------ forward
     def forward(self, x: torch.Tensor) -> torch.Tensor:

@@ -626,6 +626,21 @@ def ema_update(ranges, state, decay, warmup=False, found_inf=None):
          stream_ptr())
 
 
+ACCUM_OFF, ACCUM_STORE, ACCUM_ADD, ACCUM_FINISH = 0, 1, 2, 3  # include/dtc.h DTC_ACCUM_*
+
+
+def grad_accum_flat(acc, g, mode):
+    """One gradient-accumulation launch over two contiguous fp32 tensors of one size (include/dtc.h:
+    dtc_grad_accum_flat): ACCUM_STORE acc = g, ACCUM_ADD acc = acc + g, ACCUM_FINISH g = g + acc -- one rounded fp32
+    add per element, the other operand untouched."""
+    require_cuda(acc, g)
+    if acc.dtype != torch.float32 or g.dtype != torch.float32:
+        raise NativeError("grad_accum_flat: acc and g must be fp32 tensors")
+    if acc.numel() != g.numel() or not (acc.is_contiguous() and g.is_contiguous()):
+        raise NativeError("grad_accum_flat: acc and g must be contiguous tensors of one size")
+    call("dtc_grad_accum_flat", ptr(acc), ptr(g), g.numel(), int(mode), stream_ptr())
+
+
 def cast_f32_bf16(src, dst):
     call("dtc_cast_f32_bf16", ptr(src), ptr(dst), src.numel(), stream_ptr())
 

@@ -14,7 +14,10 @@ on a ``dist.init_process_group('nccl', 'tcp://127.0.0.1:3456', world, rank)`` gr
   all-reduced on the communicator's side stream right after backward produced it, so it
   overlaps the remaining backward kernels; gradients are pre-divided by the world size in the
   kernels that write them (DDP's mean);
-* ``find_unused_parameters`` is accepted and ignored (ResNet-18 has no unused parameters).
+* ``find_unused_parameters`` is accepted and ignored (ResNet-18 has no unused parameters);
+* ``no_sync()`` is the module's ``accumulate()``: backwards inside it add their gradients into the module's
+  accumulation buffer and all-reduce nothing, the first backward outside it adds the sum back bucket by bucket
+  ahead of each bucket's all-reduce -- one set of collectives per window of micro-batches.
 """
 from __future__ import annotations
 
@@ -324,6 +327,13 @@ class DistributedDataParallel(nn.Module):
             self.comm.broadcast_(flat.bufs, 0)  # C2: rank-0 BN running statistics
         return self.module(*inputs, **kwargs)
 
+    def no_sync(self):
+        """torch's ``DistributedDataParallel.no_sync()``: a context in which backwards accumulate gradients
+        locally without all-reducing them (``ResNet.accumulate``); the first backward after it all-reduces the
+        accumulated gradients. Set ``module.grad_accum_steps`` to the window's length for the mean over its
+        micro-batches. SyncBatchNorm's statistics are still all-reduced on every micro-step, as torch's."""
+        return self.module.accumulate()
+
     @property
     def buckets(self):
         return self.module.buckets()
@@ -423,6 +433,15 @@ class _Replica:
         return t
 
 
+def _refuse_accumulation(model) -> None:
+    """DataParallel's reduce-add writes the module's gradients after the replicas' backwards; gradient
+    accumulation is not stacked on it."""
+    if model._accum_depth > 0 or model._accum_open or model.grad_accum_steps != 1:
+        raise NativeError("DataParallel does not support gradient accumulation (ResNet.accumulate() / "
+                          "grad_accum_steps != 1): use the bare module or DistributedDataParallel, or call "
+                          "reset_accumulation() and set grad_accum_steps = 1")
+
+
 class _DPFn(torch.autograd.Function):
     """scatter -> replicate -> parallel_apply -> gather (forward) and its reverse (backward:
     gather's backward scatters dlogits, replicate's backward reduce-adds the replicas' gradients
@@ -478,8 +497,10 @@ class _DPFn(torch.autograd.Function):
         model = dp.module
         dev0 = dp.devices[0]
         dl = dlogits.contiguous().float()
+        _refuse_accumulation(model)
         for exe, gen in ctx.runs:
             exe.consume(gen)
+            exe.set_grad_accum(0)  # (a mode left on the module's own executor by an abandoned window)
         for i, (exe, gen) in enumerate(ctx.runs):
             dev = dp.devices[i]
             d = dl[ctx.offs[i]:ctx.offs[i] + ctx.sizes[i]]
@@ -547,6 +568,7 @@ class DataParallel(nn.Module):
     def forward(self, x, *args, **kwargs):
         if args or kwargs:
             raise NotImplementedError("the native ResNet takes one input tensor")
+        _refuse_accumulation(self.module)
         if len(self.device_ids) == 1:
             return self.module(x)
         require_cuda(x)

@@ -82,6 +82,11 @@ def load_config(argv=None, mode: str = "ddp"):
     p.add_argument("--model-ema-warmup", action="store_true", default=False,
                    help="--model-ema: decay_t = min(decay, (1 + t) / (10 + t)) over the updates t")
     p.add_argument("--model-ema-steps", type=int, default=1, help="--model-ema: update on every N-th global step")
+    # not in the reference: the global batch of the large-batch recipes above on few GPUs
+    p.add_argument("--accum-steps", type=int, default=1,
+                   help="gradient accumulation: one optimizer step per N loader iterations, on the mean gradient of "
+                        "their N micro-batches (ddp: one all-reduce per N backwards, DDP.no_sync()). The last "
+                        "iteration of an epoch closes a shorter window, still divided by N (single and ddp only)")
     # synthetic-data size knobs (not in the reference: CIFAR-100 cannot be downloaded here)
     p.add_argument("--synthetic-train", type=int, default=50000)
     p.add_argument("--synthetic-test", type=int, default=10000)
@@ -105,6 +110,10 @@ def load_config(argv=None, mode: str = "ddp"):
         p.error("--mixup-alpha / --cutmix-alpha need --device-data (the host loader does not mix)")
     if not 0.0 <= h.model_ema_decay < 1.0 or h.model_ema_steps < 1:
         p.error("--model-ema-decay must be in [0, 1) and --model-ema-steps >= 1")
+    if h.accum_steps < 1:
+        p.error("--accum-steps must be >= 1")
+    if mode == "dp" and h.accum_steps > 1:
+        p.error("--accum-steps > 1 is not available under DataParallel (single and ddp only)")
     return h
 
 
@@ -195,6 +204,11 @@ class Trainer:
             self.test_loader = D.get_tst_loader(batch_size=hparams.batch_size, num_workers=1, pin_memory=True,
                                                 distributed=distributed, n=hparams.synthetic_test)
         self.global_step = 0
+        # optimizer steps taken (--accum-steps N: one per window of N loader iterations; N = 1: == global_step)
+        self.optimizer_step = 0
+        self.accum_steps = int(getattr(hparams, "accum_steps", 1))
+        if self.accum_steps > 1:
+            self._module_for_eval().grad_accum_steps = self.accum_steps
         self.global_top1_acc = 0.0
         self.eval_step = hparams.eval_step
         self.version = None
@@ -277,12 +291,32 @@ class Trainer:
             self.lr_scheduler.step()
         return self.version
 
+    def _backward(self, loss, closing: bool) -> None:
+        """loss.backward(); inside a --accum-steps window (not `closing`) under the model's accumulate() /
+        DDP's no_sync(): the gradients are added to the window's sum and nothing is all-reduced."""
+        if closing:
+            loss.backward()
+        else:
+            with (self.model.no_sync() if self.distributed else self.model.accumulate()):
+                loss.backward()
+
     def _train_epoch(self, epoch: int) -> dict:
+        """One epoch of the reference's step. --accum-steps N > 1: backwards 1..N-1 of a window of N loader
+        iterations accumulate; the N-th closes the window and is followed by the unscale_ / clip / step / EMA /
+        scaler.update sequence, which therefore runs -- and counts -- once per optimizer step. The epoch's last
+        iteration (also an early end through --max-steps) closes a shorter window; its gradient is still the sum
+        divided by N (PyTorch Lightning's accumulate_grad_batches does the same). Logging, --eval-step and the
+        per-iteration barrier keep counting loader iterations."""
         train_loss = AverageMeter()
         self.model.train()
+        n_acc = self.accum_steps
+        n_iter = len(self.train_loader) if n_acc > 1 else 0  # (read only to find a window's early end)
+        if n_acc > 1 and self.hparams.max_steps:
+            n_iter = min(n_iter, self.hparams.max_steps)
         for step, (img, label) in enumerate(self.train_loader):
             if self.hparams.max_steps and step >= self.hparams.max_steps:
                 break
+            closing = n_acc == 1 or (step + 1) % n_acc == 0 or step + 1 == n_iter
             img = img.to(self.device, non_blocking=True)
             label = label.to(self.device, non_blocking=True)
             self.optimizer.zero_grad()
@@ -292,25 +326,29 @@ class Trainer:
                     loss = self.criterion(logit, label)
                 if self.distributed:
                     barrier()  # dist.barrier() on the native communicator            # trainer.py:156
-                self.scaler.scale(loss).backward()
-                if self.hparams.clip_grad_norm > 0:  # torch's documented order: unscale_, clip, step
-                    self.scaler.unscale_(self.optimizer)
-                    clip_grad_norm_(self.model.parameters(), self.hparams.clip_grad_norm, scaler=self.scaler)
-                self.scaler.step(self.optimizer)
-                self._ema_update(self.scaler.found_inf)  # before update(), which clears found_inf
-                self.scaler.update()
+                self._backward(self.scaler.scale(loss), closing)
+                if closing:
+                    if self.hparams.clip_grad_norm > 0:  # torch's documented order: unscale_, clip, step
+                        self.scaler.unscale_(self.optimizer)
+                        clip_grad_norm_(self.model.parameters(), self.hparams.clip_grad_norm, scaler=self.scaler)
+                    self.scaler.step(self.optimizer)
+                    self._ema_update(self.scaler.found_inf)  # before update(), which clears found_inf
+                    self.scaler.update()
             else:
                 logit = self.model(img)
                 loss = self.criterion(logit, label)
                 if self.distributed:
                     barrier()                                                             # trainer.py:163
-                loss.backward()
-                if self.hparams.clip_grad_norm > 0:
-                    clip_grad_norm_(self.model.parameters(), self.hparams.clip_grad_norm)
-                self.optimizer.step()
-                self._ema_update(None)
+                self._backward(loss, closing)
+                if closing:
+                    if self.hparams.clip_grad_norm > 0:
+                        clip_grad_norm_(self.model.parameters(), self.hparams.clip_grad_norm)
+                    self.optimizer.step()
+                    self._ema_update(None)
             train_loss.update(loss.item())
             self.global_step += 1
+            if closing:
+                self.optimizer_step += 1
             if self.rank == 0 and self.global_step % self.eval_step == 0:
                 tag = "DDP" if self.distributed else ("DP" if self.data_parallel else "Single")
                 logging.info(f"[{tag} Version {self.version} Epoch {epoch}] "
@@ -351,10 +389,10 @@ class Trainer:
         return out
 
     def _ema_update(self, found_inf) -> None:
-        """--model-ema: one update right after the optimizer step, on every --model-ema-steps-th global step (the
-        step in progress is global_step + 1). A GradScaler-skipped step updates nothing: the kernel reads
-        `found_inf` on the device."""
-        if self.ema is not None and (self.global_step + 1) % self.hparams.model_ema_steps == 0:
+        """--model-ema: one update right after the optimizer step, on every --model-ema-steps-th optimizer step (the
+        step in progress is optimizer_step + 1; without --accum-steps that is global_step + 1). A GradScaler-skipped
+        step updates nothing: the kernel reads `found_inf` on the device."""
+        if self.ema is not None and (self.optimizer_step + 1) % self.hparams.model_ema_steps == 0:
             self.ema.update(found_inf=found_inf)
 
     def validate(self, epoch: int) -> Tuple[float, float]:

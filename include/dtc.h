@@ -341,6 +341,20 @@ typedef struct { float* ema; const float* src; uint16_t* ema_bf16; int64_t n; } 
 int dtc_ema_state_words(void);
 int dtc_ema_update(const dtc_ema_range* ranges, int nranges, void* state, double decay, int warmup,
                    const int* found_inf, void* stream);
+/* grad_accum: gradient accumulation over one fp32 range (torch's `.grad +=` over the micro-batches of one optimizer
+ * step, DistributedDataParallel.no_sync()). The backward kernels write their gradients, so the running sum of a
+ * window lives in a second buffer `acc`; per element
+ *   DTC_ACCUM_STORE (1)   acc = g         (the first micro-batch of a window)         8 bytes of HBM traffic
+ *   DTC_ACCUM_ADD (2)     acc = acc + g   (every further one inside the window)      12
+ *   DTC_ACCUM_FINISH (3)  g = g + acc     (the micro-batch that closes the window)   12
+ * Each result is exactly one IEEE fp32 add (round to nearest even, no FMA, nothing reassociated): the window's sum is
+ * bit-defined, g_N + ((g_1 + g_2) + ... + g_N-1) for the micro-batches 1..N in order, and an inf or NaN of any
+ * micro-batch reaches the final g, so dtc_amp_check_finite over g after FINISH still decides a skipped step. The operand that is not the destination stays bit-unchanged. One launch, 16-byte vector
+ * loads and stores, no atomics, no host synchronisation; every element is written by exactly one thread, so the
+ * result is bit-identical from run to run. Requires (else DTC_EINVAL, before any device call): n a positive multiple
+ * of 4; acc and g non-NULL and 16-byte aligned; mode in 1..3; [acc, acc + n) and [g, g + n) not overlapping. */
+enum { DTC_ACCUM_OFF = 0, DTC_ACCUM_STORE = 1, DTC_ACCUM_ADD = 2, DTC_ACCUM_FINISH = 3 };
+int dtc_grad_accum_flat(float* acc, float* g, int64_t n, int mode, void* stream);
 int dtc_cast_f32_bf16(const float* src, uint16_t* dst, int64_t n, void* stream);
 int dtc_amp_check_finite(const float* g, int64_t n, int* found_inf, void* stream);
 /* GradScaler.scale(loss): out = x * (*scale) with the scale device-resident (no host sync) */
@@ -500,6 +514,22 @@ int dtc_rn18_backward(dtc_net* net, const float* dlogits, float grad_scale, dtc_
  * communicator of its own, not the one passed to dtc_rn18_backward. Disables graph replay.
  * comm == NULL: per-rank statistics (the reference's BatchNorm2d). */
 int dtc_rn18_set_sync_bn(dtc_net* net, dtc_comm* comm);
+/* Gradient accumulation inside the backward (dtc_grad_accum_flat's modes; host only, no device call). Sticky: `mode`
+ * applies to every later dtc_rn18_backward, dtc_rn18_xent_backward and dtc_rn18_xent_soft_backward, in both
+ * precisions, until the next call; dtc_rn18_bind resets it to DTC_ACCUM_OFF. `acc`: caller-owned device memory of
+ * dtc_rn18_flat_numel floats in the gradient buffer's layout, 16-byte aligned, not overlapping the bound gradients
+ * (DTC_EINVAL otherwise); NULL only with DTC_ACCUM_OFF. The work is done per gradient bucket, at the point of the
+ * backward where the bucket's gradients are complete, on the stream that holds both of its producers (the
+ * weight-gradient stream when weight gradients are pending, else the compute stream), so it overlaps the rest of
+ * the backward:
+ *   STORE / ADD  acc = g / acc = acc + g over the bucket's range. The backward must be given comm == NULL
+ *                (DTC_EINVAL before any launch otherwise): nothing is all-reduced -- DDP's no_sync().
+ *   FINISH       g = g + acc over the bucket's range immediately before the bucket's all-reduce (comm != NULL), which
+ *                therefore reduces the accumulated gradient; without a communicator the add alone.
+ *   OFF          the backward as without this call: same launches, streams and results.
+ * A backward whose mode is not OFF always runs eagerly (as with SyncBN); it neither captures nor drops graphs, so
+ * alternating modes from step to step causes no re-capture. The accumulate launches take no profiling slot. */
+int dtc_rn18_set_grad_accum(dtc_net* net, float* acc, int mode);
 /* CrossEntropyLoss backward fused with the network backward (the reference's
  * `scaler.scale(loss).backward()`, ddp/trainer.py:157, when the loss is nn.CrossEntropyLoss of the
  * network's logits, trainer.py:40,155): dlogits = (softmax(logits) - onehot(labels)) * (*gscale) / N
