@@ -136,6 +136,8 @@ _SIGS = {
     "dtc_ema_state_words": (i32, []),
     "dtc_ema_update": (i32, [PEmaRange, i32, vp, f64, i32, vp, vp]),
     "dtc_grad_accum_flat": (i32, [vp, vp, i64, i32, vp]),
+    "dtc_grad_compress_bf16": (i32, [vp, vp, vp, i64, vp]),
+    "dtc_grad_decompress_bf16": (i32, [vp, vp, i64, vp]),
     "dtc_cast_f32_bf16": (i32, [vp, vp, i64, vp]),
     "dtc_amp_scale": (i32, [vp, vp, vp, i64, vp]),
     "dtc_amp_check_finite": (i32, [vp, i64, vp, vp]),
@@ -199,6 +201,7 @@ _SIGS = {
     "dtc_rn18_eval_batch_weights": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp]),
     "dtc_rn18_set_sync_bn": (i32, [vp, vp]),
     "dtc_rn18_set_grad_accum": (i32, [vp, vp, i32]),
+    "dtc_rn18_set_grad_compress": (i32, [vp, vp, i32]),
     "dtc_rn18_dlogits_buffer": (i32, [vp, C.POINTER(sz)]),
 }
 

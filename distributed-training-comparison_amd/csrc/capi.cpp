@@ -530,6 +530,12 @@ int dtc_ema_update(const dtc_ema_range* ranges, int nranges, void* state, double
 int dtc_grad_accum_flat(float* acc, float* g, int64_t n, int mode, void* stream) {
   return grad_accum(acc, g, n, mode, S(stream));
 }
+int dtc_grad_compress_bf16(const float* g, const float* acc, uint16_t* c, int64_t n, void* stream) {
+  return grad_compress_bf16(g, acc, c, n, S(stream));
+}
+int dtc_grad_decompress_bf16(const uint16_t* c, float* g, int64_t n, void* stream) {
+  return grad_decompress_bf16(c, g, n, S(stream));
+}
 int dtc_cast_f32_bf16(const float* src, uint16_t* dst, int64_t n, void* stream) {
   return cast_f32_bf16(src, dst, n, S(stream));
 }

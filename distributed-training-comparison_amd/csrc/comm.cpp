@@ -116,7 +116,7 @@ static int group_issue(ThreadGroup* g) {  // called with g->mu held by the last 
 static int group_collective(Comm* c, int kind, void* buf, size_t count, int dtype, int root, hipStream_t after,
                             hipStream_t waiter) {
   ThreadGroup* g = c->grp;
-  DTC_CHECK_ARG(kind != GK_ALLREDUCE || dtype == 0 || dtype == 2 || dtype == 3, "thread group: SUM of fp32 / int64 / fp64 only");
+  DTC_CHECK_ARG(kind != GK_ALLREDUCE || (dtype >= 0 && dtype <= 3), "thread group: SUM of fp32 / bf16 / int64 / fp64 only");
   DTC_HIP(hipEventRecord(c->ready, after));
   hipEvent_t res = nullptr;
   {
@@ -264,12 +264,13 @@ void comm_log_clear(Comm* c) {
 }
 
 // the loopback collective: buf *= factor (fp32 / fp64; int64 buffers -- BN statistics -- by the integer
-// factor) on `st`
+// factor; bf16 words: widened, multiplied in fp32 and rounded once) on `st`
 static int loopback_reduce(Comm* c, void* buf, size_t count, int dtype, hipStream_t st, bool async) {
-  DTC_CHECK_ARG(dtype == 0 || dtype == 2 || dtype == 3, "loopback communicator: fp32 / int64 / fp64 buffers only");
+  DTC_CHECK_ARG(dtype >= 0 && dtype <= 3, "loopback communicator: fp32 / bf16 / int64 / fp64 buffers only");
   DTC_CHECK_ARG(dtype != 2 || c->factor == (float)(int64_t)c->factor, "loopback communicator: int64 needs an integer factor");
   c->log.push_back(CommLogEntry{(uint64_t)(uintptr_t)buf, (uint64_t)count, async ? 1 : 0});
   if (dtype == 2) return scale_i64(reinterpret_cast<int64_t*>(buf), (int64_t)count, (int64_t)c->factor, st);
+  if (dtype == 1) return scale_bf16(reinterpret_cast<u16*>(buf), (int64_t)count, c->factor, st);
   return dtype == 0 ? scale_f32(reinterpret_cast<float*>(buf), (int64_t)count, c->factor, st)
                     : scale_f64(reinterpret_cast<double*>(buf), (int64_t)count, (double)c->factor, st);
 }
@@ -374,13 +375,14 @@ int comm_broadcast(Comm* c, void* buf, size_t count, int dtype, int root, hipStr
   return 0;
 }
 
-int comm_allreduce_async(Comm* c, void* buf, size_t count, hipStream_t compute, hipEvent_t t0, hipEvent_t t1) {
-  DTC_CHECK_ARG(c && buf, "comm_allreduce_async: bad args");
+int comm_allreduce_async(Comm* c, void* buf, size_t count, int dtype, hipStream_t compute, hipEvent_t t0,
+                         hipEvent_t t1) {
+  DTC_CHECK_ARG(c && buf && (dtype == 0 || dtype == 1), "comm_allreduce_async: bad args (fp32 / bf16 buckets)");
   if (count == 0) return 0;
   if (c->grp) {  // the bucket's producers on `compute`, the result awaited by the side stream
     c->log.push_back(CommLogEntry{(uint64_t)(uintptr_t)buf, (uint64_t)count, 1});
     if (t0) DTC_HIP(hipEventRecord(t0, compute));
-    DTC_TRY(group_collective(c, GK_ALLREDUCE, buf, count, 0, 0, compute, c->side));
+    DTC_TRY(group_collective(c, GK_ALLREDUCE, buf, count, dtype, 0, compute, c->side));
     if (t1) DTC_HIP(hipEventRecord(t1, c->side));
     c->pending = true;
     return 0;
@@ -390,24 +392,24 @@ int comm_allreduce_async(Comm* c, void* buf, size_t count, hipStream_t compute, 
   DTC_HIP(hipEventRecord(ev, compute));
   DTC_HIP(hipStreamWaitEvent(c->side, ev, 0));
   if (t0) DTC_HIP(hipEventRecord(t0, c->side));  // (after the wait: when the collective can start)
-  if (c->loopback) DTC_TRY(loopback_reduce(c, buf, count, 0, c->side, true));
-  else DTC_NCCL(ncclAllReduce(buf, buf, count, ncclFloat32, ncclSum, c->nccl, c->side));
+  if (c->loopback) DTC_TRY(loopback_reduce(c, buf, count, dtype, c->side, true));
+  else DTC_NCCL(ncclAllReduce(buf, buf, count, to_nccl(dtype), ncclSum, c->nccl, c->side));
   if (t1) DTC_HIP(hipEventRecord(t1, c->side));
   c->pending = true;
   return 0;
 }
 
-int comm_allreduce_on(Comm* c, void* buf, size_t count, hipStream_t st, hipEvent_t t0, hipEvent_t t1) {
-  DTC_CHECK_ARG(c && buf, "comm_allreduce_on: bad args");
+int comm_allreduce_on(Comm* c, void* buf, size_t count, int dtype, hipStream_t st, hipEvent_t t0, hipEvent_t t1) {
+  DTC_CHECK_ARG(c && buf && (dtype == 0 || dtype == 1), "comm_allreduce_on: bad args (fp32 / bf16 buckets)");
   if (count == 0) return 0;
   if (t0) DTC_HIP(hipEventRecord(t0, st));
   if (c->grp) {
     c->log.push_back(CommLogEntry{(uint64_t)(uintptr_t)buf, (uint64_t)count, 1});
-    DTC_TRY(group_collective(c, GK_ALLREDUCE, buf, count, 0, 0, st, st));
+    DTC_TRY(group_collective(c, GK_ALLREDUCE, buf, count, dtype, 0, st, st));
   } else if (c->loopback) {
-    DTC_TRY(loopback_reduce(c, buf, count, 0, st, true));
+    DTC_TRY(loopback_reduce(c, buf, count, dtype, st, true));
   } else {
-    DTC_NCCL(ncclAllReduce(buf, buf, count, ncclFloat32, ncclSum, c->nccl, st));
+    DTC_NCCL(ncclAllReduce(buf, buf, count, to_nccl(dtype), ncclSum, c->nccl, st));
   }
   if (t1) DTC_HIP(hipEventRecord(t1, st));
   return 0;
@@ -423,6 +425,7 @@ int comm_join(Comm* c, hipStream_t compute) {
 }
 
 bool comm_pending(const Comm* c) { return c != nullptr && c->pending; }
+hipStream_t comm_side_stream(const Comm* c) { return c ? c->side : nullptr; }
 int comm_world(const Comm* c) { return c ? c->world : 1; }
 int comm_rank(const Comm* c) { return c ? c->rank : 0; }
 

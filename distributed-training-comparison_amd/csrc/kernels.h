@@ -433,6 +433,15 @@ int ema_update(const EmaRange* ranges, int nranges, void* state, double decay, i
 #define DTC_ACCUM_UNROLL 4
 #define DTC_ACCUM_MAX_BLOCKS 1024
 int grad_accum(float* acc, float* g, int64_t n, int mode, hipStream_t st);
+// bf16 gradient compression (compress.hip) over one range: c = bf16_rne(acc ? g + acc : g) (one rounded fp32 add,
+// then one rounding) and g = widen(c) (exact). fp32 pointers 16-byte aligned, c 8-byte aligned, n a multiple of 4.
+// A workgroup of DTC_COMPRESS_THREADS takes chunks of DTC_COMPRESS_THREADS * DTC_COMPRESS_UNROLL rows of 8 elements
+// (decompress: twice as many rows of 4); the grid is capped at DTC_COMPRESS_MAX_BLOCKS. One launch each.
+#define DTC_COMPRESS_THREADS 256
+#define DTC_COMPRESS_UNROLL 4
+#define DTC_COMPRESS_MAX_BLOCKS 1024
+int grad_compress_bf16(const float* g, const float* acc, u16* c, int64_t n, hipStream_t st);
+int grad_decompress_bf16(const u16* c, float* g, int64_t n, hipStream_t st);
 int cast_f32_bf16(const float* src, u16* dst, int64_t n, hipStream_t st);
 // zero an 8-byte aligned range (a kernel node, unlike hipMemsetAsync's fill dispatch)
 int zero_bytes(void* p, size_t bytes, hipStream_t st);
@@ -440,10 +449,12 @@ int zero_bytes(void* p, size_t bytes, hipStream_t st);
 int copy_and_zero(const void* src, void* dst, size_t bytes, void* zp, size_t zbytes, hipStream_t st);
 // x[i] *= f (loopback test communicator)
 int scale_f32(float* x, int64_t n, float f, hipStream_t st);
+// bf16 words in place: x = bf16_rne(widen(x) * f), one fp32 multiply and one rounding (the loopback's bf16 collective)
+int scale_bf16(u16* x, int64_t n, float f, hipStream_t st);
 int scale_f64(double* x, int64_t n, double f, hipStream_t st);
 int scale_i64(int64_t* x, int64_t n, int64_t f, hipStream_t st);
 // thread-group communicator: every rank's buffer <- the rank-ordered sum of all (fp32 dtype 0 / int64 2 /
-// fp64 3)
+// fp64 3; bf16 dtype 1: the words widened, added in fp32 in rank order and rounded once)
 #define DTC_GROUP_MAX 8
 struct GroupPtrs { void* p[DTC_GROUP_MAX]; };
 int group_sum(const GroupPtrs& g, int w, int64_t n, int dtype, hipStream_t st);

@@ -173,6 +173,11 @@ struct Net {
   // caller-owned buffer in the gradient buffer's layout; applied per bucket at the plan's bucket points
   int accum_mode = 0;
   float* accum = nullptr;
+  // Gradient compression (dtc_rn18_set_grad_compress): the mode of the next backwards (DTC_COMPRESS_*) and the
+  // caller-owned bf16 staging buffer in the gradient buffer's element layout; a backward with a communicator
+  // all-reduces each bucket there and widens it back into the gradients behind the collective
+  int compress_mode = 0;
+  u16* compress = nullptr;
   // layers
   std::vector<ParamEntry> params;
   int64_t flat_numel = 0;

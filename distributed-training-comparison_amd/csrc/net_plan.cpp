@@ -384,6 +384,8 @@ int dtc_rn18_bind(dtc_net* net, void* workspace, float* params, float* grads, ui
   n.mem.nbt = num_batches_tracked;
   n.accum_mode = DTC_ACCUM_OFF;  // the accumulation buffer was checked against the previous gradients
   n.accum = nullptr;
+  n.compress_mode = DTC_COMPRESS_OFF;  // (likewise the staging buffer)
+  n.compress = nullptr;
   n.prof.ts = n.at<u64>(n.plan.PROF_TS);
   n.prof.acc = n.at<u64>(n.plan.PROF_ACC);
   drop_graphs(n);  // captured launches hold the previous pointers
@@ -441,6 +443,27 @@ int dtc_rn18_set_grad_accum(dtc_net* net, float* acc, int mode) {
   }
   n.accum = acc;
   n.accum_mode = mode;
+  return 0;
+}
+
+int dtc_rn18_set_grad_compress(dtc_net* net, uint16_t* staging, int mode) {
+  DTC_CHECK_ARG(net != nullptr, "dtc_rn18_set_grad_compress: null net");
+  DTC_CHECK_ARG(mode == DTC_COMPRESS_OFF || mode == DTC_COMPRESS_BF16,
+                "dtc_rn18_set_grad_compress: mode = %d is neither DTC_COMPRESS_OFF (0) nor DTC_COMPRESS_BF16 (1)", mode);
+  Net& n = net->n;
+  if (mode != DTC_COMPRESS_OFF) {
+    DTC_CHECK_ARG(staging != nullptr, "dtc_rn18_set_grad_compress: mode %d needs a staging buffer (staging is NULL)",
+                  mode);
+    DTC_CHECK_ARG(n.mem.g != nullptr, "dtc_rn18_set_grad_compress: call after dtc_rn18_bind");
+  }
+  if (staging != nullptr) {
+    DTC_CHECK_ARG(((uintptr_t)staging & 15) == 0, "dtc_rn18_set_grad_compress: staging must be 16-byte aligned");
+    const uintptr_t s0 = (uintptr_t)staging, g0 = (uintptr_t)n.mem.g, numel = (uintptr_t)n.flat_numel;
+    DTC_CHECK_ARG(n.mem.g == nullptr || s0 + numel * 2 <= g0 || g0 + numel * 4 <= s0,
+                  "dtc_rn18_set_grad_compress: staging overlaps the bound gradient buffer");
+  }
+  n.compress = staging;
+  n.compress_mode = mode;
   return 0;
 }
 

@@ -80,6 +80,9 @@ static bool graphs_on(Net& n, bool bwd, bool comm = false) {
   // an accumulating backward (dtc_rn18_set_grad_accum) runs eagerly and leaves the captured graphs alone: the
   // mode alternates from step to step, and the next plain backward replays what was captured before
   if (bwd && n.accum_mode != DTC_ACCUM_OFF) return false;
+  // likewise a backward with gradient compression armed (dtc_rn18_set_grad_compress): its bucket points compress,
+  // reduce the staging buffer and decompress, none of which a captured segment holds
+  if (bwd && n.compress_mode != DTC_COMPRESS_OFF) return false;
   if (g == 4 && (!bwd || !(comm && option_get(OPT_COMM_ON_SIDE) == 0))) return false;
   if (n.graph.epoch != option_epoch()) {  // options are baked into captured launches
     drop_graphs(n);
@@ -540,8 +543,11 @@ static bool bucket_fires(const Net& n, int after_block) {
   return false;
 }
 // Bucket i's all-reduce, bracketed by the timed step's events: on `stream` itself (on_stream: its producers
-// are already ordered before it there) or on the communicator's own stream, forked from `stream`
-static int issue_bucket(Net& n, Comm* comm, int i, hipStream_t stream, bool on_stream) {
+// are already ordered before it there) or on the communicator's own stream, forked from `stream`. `compressed`
+// (gradient compression, the caller has filled the bucket's staging range): the collective reduces the bf16
+// staging words, and the decompress into the fp32 gradients is enqueued directly behind it on the stream the
+// collective runs on -- outside the timing events, and ahead of the end-of-backward join of that stream.
+static int issue_bucket(Net& n, Comm* comm, int i, hipStream_t stream, bool on_stream, bool compressed = false) {
   hipEvent_t t0 = nullptr, t1 = nullptr;
   if (n.ct.cur && i < (int)n.ct.cur->b0.size()) {
     t0 = n.ct.cur->b0[i];
@@ -550,7 +556,13 @@ static int issue_bucket(Net& n, Comm* comm, int i, hipStream_t stream, bool on_s
   }
   float* g = n.mem.g + n.plan.bucket_off[i];
   const size_t len = (size_t)n.plan.bucket_len[i];
-  return on_stream ? comm_allreduce_on(comm, g, len, stream, t0, t1) : comm_allreduce_async(comm, g, len, stream, t0, t1);
+  if (!compressed)
+    return on_stream ? comm_allreduce_on(comm, g, len, 0, stream, t0, t1)
+                     : comm_allreduce_async(comm, g, len, 0, stream, t0, t1);
+  u16* c = n.compress + n.plan.bucket_off[i];
+  DTC_TRY(on_stream ? comm_allreduce_on(comm, c, len, 1, stream, t0, t1)
+                    : comm_allreduce_async(comm, c, len, 1, stream, t0, t1));
+  return grad_decompress_bf16(c, g, (int64_t)len, on_stream ? stream : comm_side_stream(comm));
 }
 // Bucket point after block `after_block` (-1: after the stem). Eager: all-reduce the buckets that
 // are complete now. Capturing: close the current graph segment there and open the next one; the
@@ -579,13 +591,22 @@ static int maybe_bucket(Net& n, int after_block, const BwdCtx& cx, hipStream_t s
     // collective does. STORE / ADD keep the sum in n.accum and reduce nothing (the entry points refuse a
     // communicator); FINISH adds the sum onto the gradients ahead of the buckets' collectives below, which are
     // ordered after `prod`.
-    if (accum != DTC_ACCUM_OFF) {
+    // Gradient compression (dtc_rn18_set_grad_compress; only with a communicator): one compress launch over the
+    // same range into the bf16 staging buffer, on `prod` too. With FINISH it is the fused form, staging =
+    // bf16(g + acc), in place of the FINISH launch: g + acc is not written to g, the decompress behind each
+    // bucket's collective (issue_bucket) overwrites g anyway.
+    const bool compress = cx.comm && n.compress_mode == DTC_COMPRESS_BF16;
+    if (accum != DTC_ACCUM_OFF || compress) {
       int64_t lo = n.plan.bucket_off[ids[0]], hi = lo;
       for (int i : ids) {
         lo = std::min(lo, n.plan.bucket_off[i]);
         hi = std::max(hi, n.plan.bucket_off[i] + n.plan.bucket_len[i]);
       }
-      DTC_TRY(grad_accum(n.accum + lo, n.mem.g + lo, hi - lo, accum, prod));
+      if (compress)
+        DTC_TRY(grad_compress_bf16(n.mem.g + lo, accum == DTC_ACCUM_FINISH ? n.accum + lo : nullptr, n.compress + lo,
+                                   hi - lo, prod));
+      else
+        DTC_TRY(grad_accum(n.accum + lo, n.mem.g + lo, hi - lo, accum, prod));
       if (!cx.comm) return 0;
     }
     // option comm_on_side: the collective on the weight-gradient stream itself (it holds both producers
@@ -599,7 +620,7 @@ static int maybe_bucket(Net& n, int after_block, const BwdCtx& cx, hipStream_t s
     // two cross-stream hand-offs, ~15 us each (bench --sim-world 2 buckets_us / comm_exposed_us, round 5)
     const bool inline_tail = after_block == -1 && prod == st && option_get(OPT_COMM_TAIL_INLINE) != 0 &&
                              !comm_pending(cx.comm);
-    for (int i : ids) DTC_TRY(issue_bucket(n, cx.comm, i, prod, on_side || inline_tail));
+    for (int i : ids) DTC_TRY(issue_bucket(n, cx.comm, i, prod, on_side || inline_tail, compress));
     return 0;
   }
   DTC_TRY(join_side(n, st));  // a graph segment ends here: every stream forked in it joins back

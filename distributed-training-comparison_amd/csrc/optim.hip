@@ -298,6 +298,20 @@ int scale_f32(float* x, int64_t n, float f, hipStream_t st) {
   return 0;
 }
 
+// bf16 words: x = bf16_rne(widen(x) * f), one fp32 multiply (__fmul_rn) and one rounding per element
+__global__ void scale_bf16_kernel(u16* __restrict__ x, int64_t n, float f) {
+  for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    x[i] = f2bf(__fmul_rn(bf2f(x[i]), f));
+}
+
+int scale_bf16(u16* x, int64_t n, float f, hipStream_t st) {
+  DTC_CHECK_ARG(x && n > 0, "scale_bf16: bad args");
+  const int blocks = (int)std::min<int64_t>(2048, (n + 255) / 256);
+  DTC_KLAUNCH(scale_bf16_kernel, dim3(blocks), dim3(256), 0, st, x, n, f);
+  DTC_LAUNCH_CHECK();
+  return 0;
+}
+
 int scale_f64(double* x, int64_t n, double f, hipStream_t st) {
   DTC_CHECK_ARG(x && n > 0, "scale_f64: bad args");
   const int blocks = (int)std::min<int64_t>(2048, (n + 255) / 256);
@@ -357,10 +371,22 @@ __global__ void group_sum_kernel(GroupPtrs g, int w, int64_t n) {
   }
 }
 
+// bf16 buffers: every rank's word <- bf16_rne(((widen(c_0) + widen(c_1)) + ...) + widen(c_{w-1})), fp32 adds in
+// rank order (__fadd_rn), rounded once; read before written per element, as above
+__global__ void group_sum_bf16_kernel(GroupPtrs g, int w, int64_t n) {
+  for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    float s = bf2f(((const u16*)g.p[0])[i]);
+    for (int r = 1; r < w; ++r) s = __fadd_rn(s, bf2f(((const u16*)g.p[r])[i]));
+    const u16 o = f2bf(s);
+    for (int r = 0; r < w; ++r) ((u16*)g.p[r])[i] = o;
+  }
+}
+
 int group_sum(const GroupPtrs& g, int w, int64_t n, int dtype, hipStream_t st) {
-  DTC_CHECK_ARG(w >= 1 && w <= DTC_GROUP_MAX && n > 0 && (dtype == 0 || dtype == 2 || dtype == 3), "group_sum: bad args");
+  DTC_CHECK_ARG(w >= 1 && w <= DTC_GROUP_MAX && n > 0 && dtype >= 0 && dtype <= 3, "group_sum: bad args");
   const int blocks = (int)std::min<int64_t>(2048, (n + 255) / 256);
   if (dtype == 0) DTC_KLAUNCH(group_sum_kernel<float>, dim3(blocks), dim3(256), 0, st, g, w, n);
+  else if (dtype == 1) DTC_KLAUNCH(group_sum_bf16_kernel, dim3(blocks), dim3(256), 0, st, g, w, n);
   else if (dtype == 2) DTC_KLAUNCH(group_sum_kernel<int64_t>, dim3(blocks), dim3(256), 0, st, g, w, n);
   else DTC_KLAUNCH(group_sum_kernel<double>, dim3(blocks), dim3(256), 0, st, g, w, n);
   DTC_LAUNCH_CHECK();

@@ -46,6 +46,7 @@ def set_autocast_enabled(enabled: bool) -> None:
 
 
 PRECISIONS = ("bf16", "fp32")
+GRAD_COMPRESSIONS = (None, "bf16")  # ResNet.grad_compression
 
 
 # ----------------------------------------------------------------------------- layout
@@ -117,6 +118,15 @@ class FlatState:
         self.norm_ws = None
         self.clip_pending = False
         self._grad_acc = None
+        self._grad_c16 = None
+
+    @property
+    def grad_c16(self) -> torch.Tensor:
+        """The bf16 staging buffer of gradient compression (ResNet.grad_compression): `grads`' element layout in
+        bf16, allocated on first use. The bucket all-reduces of a compressed backward run on it."""
+        if self._grad_c16 is None:
+            self._grad_c16 = torch.zeros(self.grads.numel(), dtype=torch.bfloat16, device=self.device)
+        return self._grad_c16
 
     @property
     def grad_acc(self) -> torch.Tensor:
@@ -163,6 +173,7 @@ class Executor:
         self._bwd_gen = 0  # generation whose forward a backward has consumed (one backward per forward)
         self._dlogits = None
         self._accum_mode = ops.ACCUM_OFF  # dtc_rn18_bind leaves the executor there
+        self._compress_mode = ops.COMPRESS_OFF  # (likewise)
         call("dtc_rn18_bind", self.handle, self.ws_ptr, ptr(flat.params), ptr(flat.grads), ptr(flat.params_bf16),
              ptr(flat.bufs), ptr(flat.nbt), stream_ptr())
 
@@ -212,6 +223,14 @@ class Executor:
             call("dtc_rn18_set_grad_accum", self.handle, None if mode == ops.ACCUM_OFF else ptr(self.flat.grad_acc),
                  int(mode))
             self._accum_mode = mode
+
+    def set_grad_compress(self, mode: int) -> None:
+        """The gradient-compression mode of the next backwards (dtc_rn18_set_grad_compress, sticky), staged in the
+        model's `flat.grad_c16`; the library is called only when the mode changes."""
+        if mode != self._compress_mode:
+            call("dtc_rn18_set_grad_compress", self.handle,
+                 None if mode == ops.COMPRESS_OFF else ptr(self.flat.grad_c16), int(mode))
+            self._compress_mode = mode
 
     def backward(self, dlogits: torch.Tensor, grad_scale: float, comm) -> None:
         call("dtc_rn18_backward", self.handle, ptr(dlogits), float(grad_scale), comm.handle if comm else None,
@@ -756,6 +775,10 @@ class ResNet(nn.Module):
         # window's gradient is the mean over its micro-batches), the nesting depth of accumulate() and whether a
         # window is open (flat.grad_acc holds the sum of the backwards run inside accumulate() so far)
         self.grad_accum_steps = 1
+        # gradient compression of the bucket all-reduces: None, or "bf16" (torch's bf16_compress_hook; set by
+        # DistributedDataParallel.register_comm_hook / gradient_compression=). Only a backward that all-reduces
+        # compresses anything; the gradients the optimizer reads stay fp32.
+        self.grad_compression = None
         self._accum_depth = 0
         self._accum_open = False
         self._bucket_cap_mb = float(bucket_cap_mb)
@@ -923,7 +946,9 @@ class ResNet(nn.Module):
     def _begin_backward(self, exe: Executor):
         """(grad_scale, comm) of the native backward about to run on `exe`, whose accumulation mode is set
         from the window's state: STORE / ADD without a communicator inside accumulate(), FINISH for the backward
-        that closes a window, OFF otherwise."""
+        that closes a window, OFF otherwise; its compression mode from `grad_compression`."""
+        if self.grad_compression not in GRAD_COMPRESSIONS:
+            raise ValueError(f"grad_compression must be one of {GRAD_COMPRESSIONS}, not {self.grad_compression!r}")
         steps = self.grad_accum_steps
         if not isinstance(steps, int) or steps < 1:
             raise ValueError(f"grad_accum_steps must be an integer >= 1, not {steps!r}")
@@ -933,6 +958,7 @@ class ResNet(nn.Module):
         else:
             mode = ops.ACCUM_FINISH if self._accum_open else ops.ACCUM_OFF
         exe.set_grad_accum(mode)
+        exe.set_grad_compress(ops.COMPRESS_BF16 if self.grad_compression == "bf16" else ops.COMPRESS_OFF)
         return self._grad_scale / steps, comm
 
     def _end_backward(self) -> None:

@@ -641,6 +641,37 @@ def grad_accum_flat(acc, g, mode):
     call("dtc_grad_accum_flat", ptr(acc), ptr(g), g.numel(), int(mode), stream_ptr())
 
 
+COMPRESS_OFF, COMPRESS_BF16 = 0, 1  # include/dtc.h DTC_COMPRESS_*
+
+
+def _bf16_words(c, name):
+    if c.dtype not in (torch.bfloat16, torch.uint16, torch.int16) or not c.is_contiguous():
+        raise NativeError(f"{name}: c must be a contiguous tensor of 16-bit words (bfloat16, uint16 or int16)")
+
+
+def grad_compress_bf16(g, c, acc=None):
+    """c = bf16(g), or bf16(g + acc) with `acc` (one rounded fp32 add, then one round-to-nearest-even; include/dtc.h:
+    dtc_grad_compress_bf16). g, acc: contiguous fp32 tensors; c: 16-bit words of the same element count."""
+    require_cuda(g, c)
+    _bf16_words(c, "grad_compress_bf16")
+    if g.dtype != torch.float32 or not g.is_contiguous() or c.numel() != g.numel():
+        raise NativeError("grad_compress_bf16: g must be a contiguous fp32 tensor of c's element count")
+    if acc is not None:
+        require_cuda(acc)
+        if acc.dtype != torch.float32 or not acc.is_contiguous() or acc.numel() != g.numel():
+            raise NativeError("grad_compress_bf16: acc must be a contiguous fp32 tensor of g's size")
+    call("dtc_grad_compress_bf16", ptr(g), None if acc is None else ptr(acc), ptr(c), g.numel(), stream_ptr())
+
+
+def grad_decompress_bf16(c, g):
+    """g = widen(c): the bf16 words shifted into the upper half of fp32, exact (dtc_grad_decompress_bf16)."""
+    require_cuda(g, c)
+    _bf16_words(c, "grad_decompress_bf16")
+    if g.dtype != torch.float32 or not g.is_contiguous() or c.numel() != g.numel():
+        raise NativeError("grad_decompress_bf16: g must be a contiguous fp32 tensor of c's element count")
+    call("dtc_grad_decompress_bf16", ptr(c), ptr(g), g.numel(), stream_ptr())
+
+
 def cast_f32_bf16(src, dst):
     call("dtc_cast_f32_bf16", ptr(src), ptr(dst), src.numel(), stream_ptr())
 

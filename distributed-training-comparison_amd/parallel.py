@@ -17,7 +17,10 @@ on a ``dist.init_process_group('nccl', 'tcp://127.0.0.1:3456', world, rank)`` gr
 * ``find_unused_parameters`` is accepted and ignored (ResNet-18 has no unused parameters);
 * ``no_sync()`` is the module's ``accumulate()``: backwards inside it add their gradients into the module's
   accumulation buffer and all-reduce nothing, the first backward outside it adds the sum back bucket by bucket
-  ahead of each bucket's all-reduce -- one set of collectives per window of micro-batches.
+  ahead of each bucket's all-reduce -- one set of collectives per window of micro-batches;
+* ``register_comm_hook(state, bf16_compress_hook)`` / ``gradient_compression="bf16"``: each bucket is rounded to
+  bf16 into a staging buffer, all-reduced there at half the bytes and widened back into the fp32 gradients behind
+  its collective (torch's ``default_hooks.bf16_compress_hook``); ``allreduce_hook`` is the plain fp32 all-reduce.
 """
 from __future__ import annotations
 
@@ -32,6 +35,42 @@ from ._native import NativeError, call, lib, ptr, require_cuda, stream_ptr
 
 DTYPE_F32, DTYPE_BF16, DTYPE_I64, DTYPE_F64 = 0, 1, 2, 3
 _DTYPES = {torch.float32: DTYPE_F32, torch.bfloat16: DTYPE_BF16, torch.int64: DTYPE_I64, torch.float64: DTYPE_F64}
+
+
+def bf16_compress_hook(state=None, bucket=None):
+    """Sentinel for ``DistributedDataParallel.register_comm_hook``: all-reduce the gradient buckets in bf16 (the
+    counterpart of torch's ``ddp_comm_hooks.default_hooks.bf16_compress_hook``, which is accepted too). The native
+    Reducer does the work; this function is never called."""
+    raise NativeError("bf16_compress_hook is a marker for register_comm_hook, not a callable hook")
+
+
+def allreduce_hook(state=None, bucket=None):
+    """Sentinel for ``DistributedDataParallel.register_comm_hook``: the plain fp32 bucket all-reduce (torch's
+    ``default_hooks.allreduce_hook``, accepted too). Never called."""
+    raise NativeError("allreduce_hook is a marker for register_comm_hook, not a callable hook")
+
+
+def resolve_comm_hook(hook):
+    """The module's ``grad_compression`` for a communication hook: "bf16" for ``bf16_compress_hook``, None for
+    ``allreduce_hook`` -- this module's sentinels or, by identity, the functions of the same names in
+    ``torch.distributed.algorithms.ddp_comm_hooks.default_hooks``. Any other hook is refused: the native Reducer
+    runs no Python between a bucket's gradients and its collective."""
+    if hook is bf16_compress_hook:
+        return "bf16"
+    if hook is allreduce_hook:
+        return None
+    try:
+        from torch.distributed.algorithms.ddp_comm_hooks import default_hooks as torch_hooks
+    except ImportError:  # a torch built without distributed support
+        torch_hooks = None
+    if torch_hooks is not None:
+        if hook is torch_hooks.bf16_compress_hook:
+            return "bf16"
+        if hook is torch_hooks.allreduce_hook:
+            return None
+    raise NotImplementedError(f"communication hook {hook!r} is not supported: the native Reducer implements "
+                              "bf16_compress_hook and allreduce_hook (dtc.parallel's, or torch's default_hooks of "
+                              "the same names)")
 
 
 class Comm:
@@ -216,8 +255,10 @@ class DistributedDataParallel(nn.Module):
 
     def __init__(self, module, device_ids=None, output_device=None, dim=0, broadcast_buffers=True,
                  process_group=None, bucket_cap_mb=25, find_unused_parameters=False, comm=None, sync_comm=None,
-                 **_ignored):
+                 gradient_compression=None, **_ignored):
         super().__init__()
+        if gradient_compression not in (None, "bf16"):
+            raise ValueError(f"gradient_compression must be None or 'bf16', not {gradient_compression!r}")
         if comm is None and not dist.is_initialized():
             raise NativeError("DistributedDataParallel requires torch.distributed.init_process_group")
         self.module = module
@@ -245,6 +286,7 @@ class DistributedDataParallel(nn.Module):
             # a one-rank all-reduce is the identity: no side-stream fork/join inside the backward
             module._comm = self.comm if self.world_size > 1 else None
             module._grad_scale = 1.0 / self.world_size
+            module.grad_compression = gradient_compression
             # SyncBatchNorm: a communicator of its own (BN-sum all-reduces run on the compute
             # stream while the Reducer's bucket all-reduces run on its side stream)
             self.sync_comm = None
@@ -333,6 +375,13 @@ class DistributedDataParallel(nn.Module):
         accumulated gradients. Set ``module.grad_accum_steps`` to the window's length for the mean over its
         micro-batches. SyncBatchNorm's statistics are still all-reduced on every micro-step, as torch's."""
         return self.module.accumulate()
+
+    def register_comm_hook(self, state, hook) -> None:
+        """torch's ``DistributedDataParallel.register_comm_hook(state, hook)`` for the two hooks the native Reducer
+        implements (``resolve_comm_hook``): ``bf16_compress_hook`` turns bf16 compression of the bucket all-reduces
+        on (``module.grad_compression = "bf16"``), ``allreduce_hook`` turns it off. `state` (a process group in
+        torch) is ignored: the buckets are reduced on this wrapper's communicator."""
+        self.module.grad_compression = resolve_comm_hook(hook)
 
     @property
     def buckets(self):
@@ -433,6 +482,13 @@ class _Replica:
         return t
 
 
+def _refuse_compression(model) -> None:
+    """DataParallel's reduce-add is not the Reducer: there are no bucket all-reduces to compress."""
+    if model.grad_compression is not None:
+        raise NativeError(f"DataParallel does not support gradient compression (grad_compression = "
+                          f"{model.grad_compression!r}): use DistributedDataParallel, or set grad_compression = None")
+
+
 def _refuse_accumulation(model) -> None:
     """DataParallel's reduce-add writes the module's gradients after the replicas' backwards; gradient
     accumulation is not stacked on it."""
@@ -498,9 +554,11 @@ class _DPFn(torch.autograd.Function):
         dev0 = dp.devices[0]
         dl = dlogits.contiguous().float()
         _refuse_accumulation(model)
+        _refuse_compression(model)
         for exe, gen in ctx.runs:
             exe.consume(gen)
             exe.set_grad_accum(0)  # (a mode left on the module's own executor by an abandoned window)
+            exe.set_grad_compress(0)
         for i, (exe, gen) in enumerate(ctx.runs):
             dev = dp.devices[i]
             d = dl[ctx.offs[i]:ctx.offs[i] + ctx.sizes[i]]
@@ -569,6 +627,7 @@ class DataParallel(nn.Module):
         if args or kwargs:
             raise NotImplementedError("the native ResNet takes one input tensor")
         _refuse_accumulation(self.module)
+        _refuse_compression(self.module)
         if len(self.device_ids) == 1:
             return self.module(x)
         require_cuda(x)

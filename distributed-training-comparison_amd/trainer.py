@@ -24,7 +24,7 @@ from .amp import GradScaler, autocast
 from .ema import ModelEma
 from .nn import CrossEntropyLoss, ResNet18, SyncBatchNorm
 from .optim import LARS, SGD, Adam, AdamW, clip_grad_norm_
-from .parallel import DDP, DataParallel, barrier
+from .parallel import DDP, DataParallel, barrier, bf16_compress_hook
 
 
 def load_config(argv=None, mode: str = "ddp"):
@@ -44,6 +44,10 @@ def load_config(argv=None, mode: str = "ddp"):
         p.add_argument("--dist-url", default="tcp://127.0.0.1:3456", type=str)
         p.add_argument("--sync-bn", action="store_true", default=False,
                        help="SyncBatchNorm.convert_sync_batchnorm (README.md:40; off in the reference)")
+        # not in the reference: torch's ddp.register_comm_hook(None, default_hooks.bf16_compress_hook)
+        p.add_argument("--grad-compress", choices=("none", "bf16"), default="none",
+                       help="bf16: all-reduce the gradient buckets in bf16 (half the bytes per step); the optimizer "
+                            "still reads fp32 gradients")
     p.add_argument("--epoch", type=int, default=200 if mode == "single" else 100)
     p.add_argument("--batch-size", type=int, default=128)
     p.add_argument("--model", type=str, default="resnet18")
@@ -184,6 +188,8 @@ class Trainer:
             self.model = DataParallel(self.model, device_ids=getattr(hparams, "device_ids", None))  # dp/trainer.py:27
         if distributed:
             self.model = DDP(self.model, device_ids=[rank], find_unused_parameters=True)   # ddp/trainer.py:31
+            if getattr(hparams, "grad_compress", "none") == "bf16":
+                self.model.register_comm_hook(None, bf16_compress_hook)
             hparams.batch_size = int(hparams.batch_size / ngpus_per_node)                  # ddp/trainer.py:34
         self.scaler = scaler
         self.optimizer, self.lr_scheduler = self.configure_optimizers()

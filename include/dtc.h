@@ -355,6 +355,19 @@ int dtc_ema_update(const dtc_ema_range* ranges, int nranges, void* state, double
  * of 4; acc and g non-NULL and 16-byte aligned; mode in 1..3; [acc, acc + n) and [g, g + n) not overlapping. */
 enum { DTC_ACCUM_OFF = 0, DTC_ACCUM_STORE = 1, DTC_ACCUM_ADD = 2, DTC_ACCUM_FINISH = 3 };
 int dtc_grad_accum_flat(float* acc, float* g, int64_t n, int mode, void* stream);
+/* bf16 gradient compression for the bucketed all-reduce (torch's default_hooks.bf16_compress_hook), one launch each:
+ *   compress    c[i] = bf16_rne(acc ? g[i] + acc[i] : g[i])   4 (+ 4) bytes read, 2 written per element
+ *   decompress  g[i] = widen(c[i])  (bits << 16: exact; NaN payloads, inf, -0 and subnormals preserved)   2 read, 4 written
+ * The rounding is dtc_cast_f32_bf16's, round to nearest even: a NaN stays a NaN, a finite value at or above the bf16
+ * overflow threshold becomes +-inf. With acc != NULL the sum is exactly one IEEE fp32 add (no FMA, nothing
+ * reassociated) followed by the one rounding, so the result is bit-identical to dtc_grad_accum_flat(DTC_ACCUM_FINISH)
+ * followed by the plain compress, at 10 instead of 18 bytes per element. compress never writes g or acc, decompress
+ * never writes c. 16-byte fp32 loads and stores; compress stores 16 bytes of bf16 from c's first 16-byte boundary on,
+ * with an 8-byte store for the 4 elements in front of it and for a last 4 left over; decompress loads 8 bytes of bf16
+ * per 16-byte store; no atomics; every element is written by exactly one thread. Requires (else DTC_EINVAL, before any device call): n a positive multiple of 4; g, c non-NULL;
+ * g and acc 16-byte aligned, c 8-byte aligned; [c, c + n) overlapping neither [g, g + n) nor [acc, acc + n). */
+int dtc_grad_compress_bf16(const float* g, const float* acc, uint16_t* c, int64_t n, void* stream);
+int dtc_grad_decompress_bf16(const uint16_t* c, float* g, int64_t n, void* stream);
 int dtc_cast_f32_bf16(const float* src, uint16_t* dst, int64_t n, void* stream);
 int dtc_amp_check_finite(const float* g, int64_t n, int* found_inf, void* stream);
 /* GradScaler.scale(loss): out = x * (*scale) with the scale device-resident (no host sync) */
@@ -421,7 +434,8 @@ int dtc_barrier(dtc_comm* comm, void* stream);
  * reports `world` ranks. With factor == world it is `world` ranks holding identical data. Lets a
  * one-GPU test prove that every gradient bucket is reduced exactly once and only after its producers,
  * and that SyncBN's sums really go through the collective (a one-rank RCCL SUM is the identity and
- * proves neither). fp32 / int64 / fp64 buffers only (int64 x the integer factor). */
+ * proves neither). fp32 / bf16 / int64 / fp64 buffers (int64 x the integer factor; a bf16 word becomes
+ * bf16_rne(widen(word) * factor): one fp32 multiply, one round-to-nearest-even). */
 int dtc_comm_init_loopback(dtc_comm** out, int device, int world, float factor);
 int dtc_comm_log_size(dtc_comm* comm);
 int dtc_comm_log_entry(dtc_comm* comm, int idx, uint64_t* addr, uint64_t* count, int* is_async);
@@ -431,7 +445,8 @@ int dtc_comm_log_clear(dtc_comm* comm);
  * Collectives are matched by call order (as RCCL's): the calling thread blocks until every rank issued
  * the same collective (kind, count, dtype, root; a mismatch or a 120 s wait is an error for all ranks),
  * then the data really moves between the ranks' buffers on a group stream that waits for every rank's
- * producers -- SUM all-reduce as the rank-ordered fp32/int64/fp64 sum written into every buffer, broadcast as
+ * producers -- SUM all-reduce as the rank-ordered fp32/int64/fp64 sum written into every buffer (bf16 buffers: the
+ * words widened, added in fp32 in rank order without FMA and rounded once to nearest even), broadcast as
  * root -> all copies, barrier as a host rendezvous + stream drain -- and each rank's consumer stream
  * (the Reducer's side stream for buckets) waits for the result. Lets one GPU run W ranks with DISTINCT
  * data through the product Reducer, broadcasts and SyncBN (max 8 ranks). Every all-reduce is logged
@@ -530,6 +545,23 @@ int dtc_rn18_set_sync_bn(dtc_net* net, dtc_comm* comm);
  * A backward whose mode is not OFF always runs eagerly (as with SyncBN); it neither captures nor drops graphs, so
  * alternating modes from step to step causes no re-capture. The accumulate launches take no profiling slot. */
 int dtc_rn18_set_grad_accum(dtc_net* net, float* acc, int mode);
+/* bf16 gradient compression of the bucket all-reduces (host only, no device call). Sticky like
+ * dtc_rn18_set_grad_accum; dtc_rn18_bind resets it to DTC_COMPRESS_OFF. `staging`: caller-owned device memory of
+ * dtc_rn18_flat_numel bf16 words in the gradient buffer's element layout, 16-byte aligned, not overlapping the bound
+ * gradients; NULL only with DTC_COMPRESS_OFF. Gradients must be bound first; an unknown mode is DTC_EINVAL.
+ * DTC_COMPRESS_BF16 and a backward with comm != NULL: at each bucket point, on the stream that holds both producers,
+ * one dtc_grad_compress_bf16 launch over the contiguous range of the buckets complete there into staging (with
+ * DTC_ACCUM_FINISH the fused form with acc, in place of the FINISH launch), then each bucket's all-reduce on its
+ * staging range as bf16 -- half the bytes of the fp32 one; its placement (options comm_on_side, comm_tail_inline) is
+ * decided as without compression -- and one dtc_grad_decompress_bf16 per bucket into the gradients, enqueued directly
+ * behind that bucket's collective on the stream the collective runs on, so the end-of-backward join orders the compute
+ * stream after it: the finiteness check, clipping, LARS and the optimizers read ordinary fp32 gradients (a value that
+ * overflowed to inf in bf16 arrives as inf). With comm == NULL (no communicator; STORE / ADD micro-steps) nothing is
+ * compressed, staging is not touched and the gradients are bit-identical to DTC_COMPRESS_OFF. A backward whose mode
+ * is not OFF always runs eagerly; it neither captures nor drops graphs. dtc_rn18_comm_timing's events keep bracketing
+ * the collective alone; the new launches take no profiling slot. SyncBN's statistics are not compressed. */
+enum { DTC_COMPRESS_OFF = 0, DTC_COMPRESS_BF16 = 1 };
+int dtc_rn18_set_grad_compress(dtc_net* net, uint16_t* staging, int mode);
 /* CrossEntropyLoss backward fused with the network backward (the reference's
  * `scaler.scale(loss).backward()`, ddp/trainer.py:157, when the loss is nn.CrossEntropyLoss of the
  * network's logits, trainer.py:40,155): dlogits = (softmax(logits) - onehot(labels)) * (*gscale) / N
