@@ -10,10 +10,10 @@
 // (ACCUM_UNROLL per thread, ACCUM_THREADS apart); in a full chunk every thread issues all its 16-byte loads of
 // both operands before the first add, a ragged last chunk guards each row. The grid is sized to the range, capped
 // at ACCUM_MAX_BLOCKS (four workgroups per CU), and strides over the chunks. No atomics, vector stores only; every
-// element is written by exactly one thread, so the result is bit-identical from run to run.
-#include <algorithm>
+// element is written by exactly one thread, so the result is bit-identical from run to run. The kernel keeps its own
+// loop rather than flat.h's stream_chunks: on that, STORE measured 2% slower (profiles/flat_refactor_ab.json).
 #include "../../include/dtc.h"
-#include "common.h"
+#include "flat.h"
 #include "kernels.h"
 
 namespace dtc {
@@ -81,13 +81,12 @@ __global__ void __launch_bounds__(ACCUM_THREADS) grad_accum_kernel(float* __rest
 
 int grad_accum(float* acc, float* g, int64_t n, int mode, hipStream_t st) {
   DTC_CHECK_ARG(acc && g, "grad_accum: null pointer (acc or g)");
-  DTC_CHECK_ARG(n > 0 && (n % 4) == 0, "grad_accum: n = %lld must be a positive multiple of 4", (long long)n);
-  DTC_CHECK_ARG(((uintptr_t)acc & 15) == 0 && ((uintptr_t)g & 15) == 0, "grad_accum: acc and g must be 16-byte aligned");
+  DTC_CHECK_ARG(mult4(n), "grad_accum: n = %lld must be a positive multiple of 4", (long long)n);
+  DTC_CHECK_ARG(aligned(acc, 16) && aligned(g, 16), "grad_accum: acc and g must be 16-byte aligned");
   DTC_CHECK_ARG(mode >= DTC_ACCUM_STORE && mode <= DTC_ACCUM_FINISH, "grad_accum: mode = %d outside [1, 3]", mode);
-  const uintptr_t a0 = (uintptr_t)acc, g0 = (uintptr_t)g, bytes = (uintptr_t)n * 4;
-  DTC_CHECK_ARG(a0 + bytes <= g0 || g0 + bytes <= a0, "grad_accum: acc and g overlap");
+  DTC_CHECK_ARG(!ranges_overlap(acc, n * 4, g, n * 4), "grad_accum: acc and g overlap");
   const int64_t n4 = n / 4;
-  const dim3 grid((unsigned)std::min<int64_t>(ACCUM_MAX_BLOCKS, (n4 + ACCUM_CHUNK4 - 1) / ACCUM_CHUNK4));
+  const dim3 grid(flat_blocks(n4, ACCUM_CHUNK4, ACCUM_MAX_BLOCKS));
   if (mode == DTC_ACCUM_STORE)
     DTC_KLAUNCH(grad_accum_kernel<DTC_ACCUM_STORE>, grid, dim3(ACCUM_THREADS), 0, st, acc, g, n4);
   else if (mode == DTC_ACCUM_ADD)

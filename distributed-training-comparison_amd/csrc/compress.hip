@@ -11,20 +11,19 @@
 // elements). Compress stores 16 bytes of bf16 per thread: its body works in rows of 8 elements from the first
 // 16-byte boundary of `c`, two 16-byte fp32 loads against one 16-byte bf16 store per row. What is left in front of
 // that boundary (`head`) and behind the last whole row (`tail`) is 0 or 4 elements each, done with one 8-byte store
-// by one thread of workgroup 0. Decompress works in rows of 4 (an 8-byte load, a 16-byte store; see there). A
-// workgroup takes chunks of COMPRESS_CHUNK8 rows (COMPRESS_UNROLL per thread, COMPRESS_THREADS apart); in a full
-// chunk every thread issues all its loads before the first use, a ragged last chunk guards each row. The grid is
-// sized to the range, capped at COMPRESS_MAX_BLOCKS (four workgroups per CU), and strides over the chunks.
+// by one thread of workgroup 0. Decompress works in rows of 4 (an 8-byte load, a 16-byte store; see there). The
+// compress body is stream_chunks (flat.h), COMPRESS_UNROLL rows of 8 per thread; its workgroup-uniform base and
+// 32-bit row index keep the fused form's 16 float4 of loads within the register budget without scratch. Decompress
+// keeps its own copy of that loop: on stream_chunks it measured 2% slower (profiles/flat_refactor_ab.json). The
+// grids are sized to the range, capped at COMPRESS_MAX_BLOCKS (four workgroups per CU).
 // No atomics, vector stores only; every element is written by exactly one thread.
-#include <algorithm>
 #include "../../include/dtc.h"
-#include "common.h"
+#include "flat.h"
 #include "kernels.h"
 
 namespace dtc {
 
 constexpr int COMPRESS_THREADS = DTC_COMPRESS_THREADS, COMPRESS_UNROLL = DTC_COMPRESS_UNROLL;
-constexpr int COMPRESS_CHUNK8 = COMPRESS_THREADS * COMPRESS_UNROLL;  // rows of 8 elements per workgroup trip
 constexpr int COMPRESS_MAX_BLOCKS = DTC_COMPRESS_MAX_BLOCKS;
 // four workgroups of four waves per CU = four waves per SIMD: the register budget that keeps the whole capped grid
 // resident (the fused compress holds 16 float4 of loads per thread)
@@ -37,7 +36,7 @@ __device__ __forceinline__ uint2 compress4(const f32x4& g, const f32x4& a) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) s[e] = __fadd_rn(g[e], a[e]);
   }
-  return uint2{pack_bf2(s[0], s[1]), pack_bf2(s[2], s[3])};
+  return pack_bf16x4(s);
 }
 __device__ __forceinline__ f32x4 widen4(uint32_t lo, uint32_t hi) {
   return f32x4{bf_lo(lo), bf_hi(lo), bf_lo(hi), bf_hi(hi)};
@@ -61,60 +60,21 @@ __global__ void __launch_bounds__(COMPRESS_THREADS, COMPRESS_WAVES_PER_EU)
       *(uint2*)(c + r * 4) = compress4<ACC>(gv, av);
     }
   }
-  // per chunk a workgroup-uniform base (scalar registers) and a 32-bit row index per thread: one address register
-  // per load, so the fused form's 16 float4 of loads fit the register budget without scratch
-  const int64_t chunks = (n8 + COMPRESS_CHUNK8 - 1) / COMPRESS_CHUNK8;
-  for (int64_t ch = blockIdx.x; ch < chunks; ch += gridDim.x) {
-    const f32x4* __restrict__ gb = g4 + 2 * ch * COMPRESS_CHUNK8;
-    const f32x4* __restrict__ ab = a4 + 2 * ch * COMPRESS_CHUNK8;
-    uint4* __restrict__ cb = c8 + ch * COMPRESS_CHUNK8;
-    const uint32_t rows = (uint32_t)std::min<int64_t>(COMPRESS_CHUNK8, n8 - ch * COMPRESS_CHUNK8);
-    f32x4 gv[COMPRESS_UNROLL][2], av[COMPRESS_UNROLL][2];
-    if (rows == COMPRESS_CHUNK8) {  // uniform over the workgroup: a full chunk, no per-row guard
+  f32x4 gv[COMPRESS_UNROLL][2], av[COMPRESS_UNROLL][2];
+  stream_chunks<COMPRESS_THREADS, COMPRESS_UNROLL>(
+      n8,
+      [&](int k, int64_t base, uint32_t i) {
 #pragma unroll
-      for (int k = 0; k < COMPRESS_UNROLL; ++k) {
-        const uint32_t i = threadIdx.x + k * COMPRESS_THREADS;
-        gv[k][0] = gb[2 * i];
-        gv[k][1] = gb[2 * i + 1];
-      }
-      if (ACC) {
-#pragma unroll
-        for (int k = 0; k < COMPRESS_UNROLL; ++k) {
-          const uint32_t i = threadIdx.x + k * COMPRESS_THREADS;
-          av[k][0] = ab[2 * i];
-          av[k][1] = ab[2 * i + 1];
+        for (int h = 0; h < 2; ++h) {
+          gv[k][h] = (g4 + 2 * base)[2 * i + h];
+          if (ACC) av[k][h] = (a4 + 2 * base)[2 * i + h];
         }
-      }
-#pragma unroll
-      for (int k = 0; k < COMPRESS_UNROLL; ++k) {
+      },
+      [&](int k, int64_t base, uint32_t i) {
         const uint2 lo = compress4<ACC>(gv[k][0], ACC ? av[k][0] : gv[k][0]);
         const uint2 hi = compress4<ACC>(gv[k][1], ACC ? av[k][1] : gv[k][1]);
-        cb[threadIdx.x + k * COMPRESS_THREADS] = uint4{lo.x, lo.y, hi.x, hi.y};
-      }
-    } else {  // the ragged last chunk
-#pragma unroll
-      for (int k = 0; k < COMPRESS_UNROLL; ++k) {
-        const uint32_t i = threadIdx.x + k * COMPRESS_THREADS;
-        if (i < rows) {
-          gv[k][0] = gb[2 * i];
-          gv[k][1] = gb[2 * i + 1];
-          if (ACC) {
-            av[k][0] = ab[2 * i];
-            av[k][1] = ab[2 * i + 1];
-          }
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < COMPRESS_UNROLL; ++k) {
-        const uint32_t i = threadIdx.x + k * COMPRESS_THREADS;
-        if (i < rows) {
-          const uint2 lo = compress4<ACC>(gv[k][0], ACC ? av[k][0] : gv[k][0]);
-          const uint2 hi = compress4<ACC>(gv[k][1], ACC ? av[k][1] : gv[k][1]);
-          cb[i] = uint4{lo.x, lo.y, hi.x, hi.y};
-        }
-      }
-    }
-  }
+        (c8 + base)[i] = uint4{lo.x, lo.y, hi.x, hi.y};
+      });
 }
 
 // Widening has no 16-byte constraint on the bf16 side worth a head and a tail: a thread takes rows of 4 elements, one
@@ -161,21 +121,20 @@ struct CompressSplit {
 };
 static CompressSplit compress_split(const u16* c, int64_t n) {
   CompressSplit s;
-  s.head = ((uintptr_t)c & 15) != 0 ? 4 : 0;
+  s.head = aligned(c, 16) ? 0 : 4;
   s.n8 = (n - s.head) / 8;
   s.tail = (int)(n - s.head - s.n8 * 8);
-  s.grid = dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(COMPRESS_MAX_BLOCKS, (s.n8 + COMPRESS_CHUNK8 - 1) / COMPRESS_CHUNK8)));
+  s.grid = dim3(flat_blocks(s.n8, COMPRESS_THREADS * COMPRESS_UNROLL, COMPRESS_MAX_BLOCKS));
   return s;
 }
 
 static int compress_args_ok(const char* fn, const float* g, const float* acc, const u16* c, int64_t n) {
   DTC_CHECK_ARG(g && c, "%s: null pointer (g or c)", fn);
-  DTC_CHECK_ARG(n > 0 && (n % 4) == 0, "%s: n = %lld must be a positive multiple of 4", fn, (long long)n);
-  DTC_CHECK_ARG(((uintptr_t)g & 15) == 0 && ((uintptr_t)acc & 15) == 0, "%s: g and acc must be 16-byte aligned", fn);
-  DTC_CHECK_ARG(((uintptr_t)c & 7) == 0, "%s: c must be 8-byte aligned", fn);
-  const uintptr_t c0 = (uintptr_t)c, c1 = c0 + (uintptr_t)n * 2, fb = (uintptr_t)n * 4;
-  DTC_CHECK_ARG(c1 <= (uintptr_t)g || (uintptr_t)g + fb <= c0, "%s: c and g overlap", fn);
-  DTC_CHECK_ARG(!acc || c1 <= (uintptr_t)acc || (uintptr_t)acc + fb <= c0, "%s: c and acc overlap", fn);
+  DTC_CHECK_ARG(mult4(n), "%s: n = %lld must be a positive multiple of 4", fn, (long long)n);
+  DTC_CHECK_ARG(aligned(g, 16) && aligned(acc, 16), "%s: g and acc must be 16-byte aligned", fn);
+  DTC_CHECK_ARG(aligned(c, 8), "%s: c must be 8-byte aligned", fn);
+  DTC_CHECK_ARG(!ranges_overlap(c, n * 2, g, n * 4), "%s: c and g overlap", fn);
+  DTC_CHECK_ARG(!acc || !ranges_overlap(c, n * 2, acc, n * 4), "%s: c and acc overlap", fn);
   return 0;
 }
 
@@ -195,7 +154,7 @@ int grad_compress_bf16(const float* g, const float* acc, u16* c, int64_t n, hipS
 int grad_decompress_bf16(const u16* c, float* g, int64_t n, hipStream_t st) {
   DTC_TRY(compress_args_ok("grad_decompress_bf16", g, nullptr, c, n));
   const int64_t n4 = n / 4;
-  const dim3 grid((unsigned)std::min<int64_t>(COMPRESS_MAX_BLOCKS, (n4 + DECOMPRESS_CHUNK4 - 1) / DECOMPRESS_CHUNK4));
+  const dim3 grid(flat_blocks(n4, DECOMPRESS_CHUNK4, COMPRESS_MAX_BLOCKS));
   DTC_KLAUNCH(grad_decompress_kernel, grid, dim3(COMPRESS_THREADS), 0, st, c, g, n4);
   DTC_LAUNCH_CHECK();
   return 0;

@@ -11,7 +11,7 @@
 // launch: the range table travels by value and the blocks are dealt out in proportion to the lengths. HBM-bound:
 // 4 (ema read) + 4 (src) + 4 (ema write) + 2 (bf16) = 14 B per element. No atomics, no host synchronisation;
 // every element is written by exactly one thread, so the result is bit-identical from run to run.
-#include "common.h"
+#include "flat.h"
 #include "kernels.h"
 
 namespace dtc {
@@ -65,18 +65,8 @@ __global__ void __launch_bounds__(256) ema_update_kernel(const EmaTable tab, con
 #pragma unroll
     for (int k = 0; k < 4; ++k) ev[k] = fmaf(sv[k] - ev[k], w, ev[k]);
     *(f32x4*)(e + i * 4) = ev;
-    if (eb) {  // uniform over the block
-      uint2 o;
-      o.x = pack_bf2(ev[0], ev[1]);
-      o.y = pack_bf2(ev[2], ev[3]);
-      *(uint2*)(eb + i * 4) = o;
-    }
+    if (eb) store_bf16x4(eb + i * 4, ev);  // uniform over the block
   }
-}
-
-static bool overlap(const float* a, int64_t na, const float* b, int64_t nb) {
-  const uintptr_t a0 = (uintptr_t)a, a1 = a0 + (uintptr_t)na * 4, b0 = (uintptr_t)b, b1 = b0 + (uintptr_t)nb * 4;
-  return a0 < b1 && b0 < a1;
 }
 
 int ema_update(const EmaRange* ranges, int nranges, void* state, double decay, int warmup, const int* found_inf,
@@ -84,7 +74,7 @@ int ema_update(const EmaRange* ranges, int nranges, void* state, double decay, i
   DTC_CHECK_ARG(ranges && state, "ema_update: null pointer (ranges or state)");
   DTC_CHECK_ARG(nranges >= 1 && nranges <= DTC_EMA_MAX_RANGES, "ema_update: nranges = %d outside [1, %d]", nranges,
                 DTC_EMA_MAX_RANGES);
-  DTC_CHECK_ARG(((uintptr_t)state & 15) == 0, "ema_update: state must be 16-byte aligned");
+  DTC_CHECK_ARG(aligned(state, 16), "ema_update: state must be 16-byte aligned");
   DTC_CHECK_ARG(decay >= 0.0 && decay < 1.0, "ema_update: decay = %g must lie in [0, 1)", decay);
   EmaTable tab = {};
   tab.nranges = nranges;
@@ -92,26 +82,26 @@ int ema_update(const EmaRange* ranges, int nranges, void* state, double decay, i
   for (int r = 0; r < nranges; ++r) {
     const EmaRange& q = ranges[r];
     DTC_CHECK_ARG(q.ema && q.src, "ema_update: range %d: null pointer (ema or src)", r);
-    DTC_CHECK_ARG(q.n > 0 && (q.n % 4) == 0, "ema_update: range %d: n = %lld must be a positive multiple of 4", r,
+    DTC_CHECK_ARG(mult4(q.n), "ema_update: range %d: n = %lld must be a positive multiple of 4", r,
                   (long long)q.n);
-    DTC_CHECK_ARG(((uintptr_t)q.ema & 15) == 0 && ((uintptr_t)q.src & 15) == 0 && ((uintptr_t)q.ema_bf16 & 7) == 0,
+    DTC_CHECK_ARG(aligned(q.ema, 16) && aligned(q.src, 16) && aligned(q.ema_bf16, 8),
                   "ema_update: range %d: ema and src must be 16-byte aligned, ema_bf16 8-byte aligned", r);
-    DTC_CHECK_ARG(!overlap(q.ema, q.n, q.src, q.n), "ema_update: range %d: ema and src overlap", r);
+    DTC_CHECK_ARG(!ranges_overlap(q.ema, q.n * 4, q.src, q.n * 4), "ema_update: range %d: ema and src overlap", r);
     for (int o = 0; o < r; ++o)
-      DTC_CHECK_ARG(!overlap(q.ema, q.n, ranges[o].ema, ranges[o].n), "ema_update: the ema of ranges %d and %d overlap",
-                    o, r);
+      DTC_CHECK_ARG(!ranges_overlap(q.ema, q.n * 4, ranges[o].ema, ranges[o].n * 4),
+                    "ema_update: the ema of ranges %d and %d overlap", o, r);
     tab.ema[r] = q.ema;
     tab.src[r] = q.src;
     tab.bf[r] = q.ema_bf16;
     tab.n4[r] = q.n / 4;
     total4 += tab.n4[r];
-    want += (tab.n4[r] + 255) / 256;
+    want += flat_blocks(tab.n4[r], 256, INT32_MAX);
   }
   // blocks in proportion to the lengths, at least one per range and never more than a range has float4 rows of 256
   const int64_t budget = std::min<int64_t>(2048, want);
   tab.first[0] = 0;
   for (int r = 0; r < nranges; ++r) {
-    const int64_t full = (tab.n4[r] + 255) / 256;
+    const int64_t full = flat_blocks(tab.n4[r], 256, INT32_MAX);
     const int64_t share = (int64_t)((double)budget * (double)tab.n4[r] / (double)total4);
     tab.first[r + 1] = tab.first[r] + (int)std::max<int64_t>(1, std::min<int64_t>(full, share));
   }

@@ -13,15 +13,15 @@
 //     buf = mu * buf + d ;  u = nesterov ? d + mu * buf : buf ;  p -= lr * u ;  p_bf16 = bf16(p)
 // Three launches, no host synchronisation, no floating-point atomics:
 //   1. seg_sumsq_kernel: one workgroup per SEG_CHUNK-element chunk of one segment (the host-built work map), both
-//      sums of squares in double in grad_sumsq_kernel's fixed order -- per thread in index order, a butterfly over
-//      the wave, the waves in index order -- into the chunk's own slot;
+//      sums of squares in double in grad_sumsq_kernel's fixed order -- per thread in index order, the workgroup by
+//      the same block_sum_ordered (flat.h) -- into the chunk's own slot;
 //   2. seg_ratio_kernel: one wave per segment folds its slots in index order and writes norms and ratio;
 //   3. lars_update_kernel: one workgroup per chunk over the same map applies the update and the bf16 shadow.
 // Every result is bit-identical from run to run. Elements between the segments (the flat buffer's 64-element
 // alignment padding) are neither read nor written.
 #include <new>
 #include <vector>
-#include "common.h"
+#include "flat.h"
 #include "kernels.h"
 
 namespace dtc {
@@ -113,7 +113,7 @@ size_t segplan_device_bytes(const SegPlan* plan) { return plan ? plan->bytes : 0
 
 int segplan_bind(SegPlan* plan, void* dev, size_t bytes, hipStream_t st) {
   DTC_CHECK_ARG(plan && dev, "segplan_bind: null pointer");
-  DTC_CHECK_ARG(((uintptr_t)dev & 15) == 0, "segplan_bind: the device region must be 16-byte aligned");
+  DTC_CHECK_ARG(aligned(dev, 16), "segplan_bind: the device region must be 16-byte aligned");
   DTC_CHECK_ARG(bytes >= plan->bytes, "segplan_bind: %zu bytes given, the plan needs %zu", bytes, plan->bytes);
   plan->dev = nullptr;
   DTC_HIP(hipMemcpyAsync(dev, plan->segs.data(), plan->segs.size() * sizeof(SegDev), hipMemcpyHostToDevice, st));
@@ -124,15 +124,6 @@ int segplan_bind(SegPlan* plan, void* dev, size_t bytes, hipStream_t st) {
 }
 
 // ---------------------------------------------------------------- kernels
-__device__ __forceinline__ double sq4(double acc, const f32x4& a) {
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const double d = (double)a[k];
-    acc += d * d;
-  }
-  return acc;
-}
-
 // this workgroup's chunk: first element and length (the last chunk of a segment is the short one)
 struct ChunkSpan {
   int64_t base;
@@ -163,34 +154,19 @@ __global__ void __launch_bounds__(SEG_THREADS) seg_sumsq_kernel(const SegDev* __
     pv[k] = i < n4 ? p4[i] : zero;
     gv[k] = i < n4 ? g4[i] : zero;
   }
-  double sp = 0.0, sg = 0.0;
+  double s[2] = {0.0, 0.0};  // sum p^2, sum g^2
 #pragma unroll
   for (int k = 0; k < SEG_VEC; ++k) {
-    sp = sq4(sp, pv[k]);
-    sg = sq4(sg, gv[k]);
+    s[0] = sumsq4(s[0], pv[k]);
+    s[1] = sumsq4(s[1], gv[k]);
   }
   if (t < (c.len & 3)) {  // numel % 4 elements at the end of a segment
     const double a = (double)p[c.base + 4 * n4 + t], b = (double)g[c.base + 4 * n4 + t];
-    sp += a * a;
-    sg += b * b;
+    s[0] += a * a;
+    s[1] += b * b;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {  // a + b == b + a: every lane gets the same bits
-    sp += __shfl_xor(sp, o, 64);
-    sg += __shfl_xor(sg, o, 64);
-  }
-  __shared__ SegSums wsum[SEG_THREADS / 64];
-  if ((t & 63) == 0) wsum[t >> 6] = SegSums{sp, sg};
-  __syncthreads();
-  if (t == 0) {
-    SegSums s = wsum[0];
-#pragma unroll
-    for (int w = 1; w < SEG_THREADS / 64; ++w) {
-      s.p += wsum[w].p;
-      s.g += wsum[w].g;
-    }
-    slots[blockIdx.x] = s;
-  }
+  block_sum_ordered<SEG_THREADS>(s);
+  if (t == 0) slots[blockIdx.x] = SegSums{s[0], s[1]};
 }
 
 struct RatioArgs {
@@ -268,24 +244,15 @@ __global__ void __launch_bounds__(SEG_THREADS) lars_update_kernel(const SegDev* 
     f32x4 pv = *(const f32x4*)(pc + i * 4);
     const f32x4 gv = *(const f32x4*)(gc + i * 4);
     f32x4 mv = *(const f32x4*)(mc + i * 4);
-    const f32x4 d = (gv * is + pv * wds) * ratio;
-    mv = mv * mu + d;
-    const f32x4 u = NESTEROV ? d + mv * mu : mv;
-    pv = pv - u * lr;
+    momentum_step<NESTEROV>(pv, mv, (gv * is + pv * wds) * ratio, mu, lr);
     *(f32x4*)(pc + i * 4) = pv;
     *(f32x4*)(mc + i * 4) = mv;
-    uint2 w;
-    w.x = pack_bf2(pv[0], pv[1]);
-    w.y = pack_bf2(pv[2], pv[3]);
-    *(uint2*)(pbc + i * 4) = w;
+    store_bf16x4(pbc + i * 4, pv);
   }
   if (t < (c.len & 3)) {  // numel % 4 elements at the end of a segment
     const int i = 4 * n4 + t;
     float pv = pc[i], mv = mc[i];
-    const float d = (gc[i] * is + pv * wds) * ratio;
-    mv = mv * mu + d;
-    const float u = NESTEROV ? d + mv * mu : mv;
-    pv = pv - u * lr;
+    momentum_step<NESTEROV>(pv, mv, (gc[i] * is + pv * wds) * ratio, mu, lr);
     pc[i] = pv;
     mc[i] = mv;
     pbc[i] = f2bf(pv);
@@ -293,8 +260,6 @@ __global__ void __launch_bounds__(SEG_THREADS) lars_update_kernel(const SegDev* 
 }
 
 // ---------------------------------------------------------------- launchers
-static bool aligned16(const void* a) { return ((uintptr_t)a & 15) == 0; }
-
 static int launch_norms(const SegPlan* pl, const float* p, const float* g, const RatioArgs& ra, const float* gmul,
                         float* seg_out, hipStream_t st) {
   DTC_KLAUNCH(seg_sumsq_kernel, dim3((unsigned)pl->map.size()), dim3(SEG_THREADS), 0, st, pl->d_segs(), pl->d_map(), p,
@@ -306,7 +271,7 @@ static int launch_norms(const SegPlan* pl, const float* p, const float* g, const
 
 int seg_norms(SegPlan* plan, const float* p, const float* g, const float* gmul, float* seg_out, hipStream_t st) {
   DTC_CHECK_ARG(plan && p && g, "seg_norms: null pointer");
-  DTC_CHECK_ARG(aligned16(p) && aligned16(g), "seg_norms: p and g must be 16-byte aligned");
+  DTC_CHECK_ARG(aligned(p, 16) && aligned(g, 16), "seg_norms: p and g must be 16-byte aligned");
   DTC_CHECK_ARG(plan->dev, "seg_norms: the plan is not bound to device memory (dtc_segplan_bind)");
   launch_norms(plan, p, g, RatioArgs{1.0, 0.0, 1.0, 0.0, 0}, gmul, seg_out, st);  // ratio = ||p|| / (|mult| ||g||)
   DTC_LAUNCH_CHECK();
@@ -323,7 +288,7 @@ int lars_flat(SegPlan* plan, float* p, const float* g, float* mom, u16* p_bf16, 
   DTC_CHECK_ARG(!trust_clip || lr > 0.0, "lars_flat: trust_clip divides the ratio by lr = %g, which must be positive",
                 lr);
   DTC_CHECK_ARG(plan && p && g && mom && p_bf16, "lars_flat: null pointer");
-  DTC_CHECK_ARG(aligned16(p) && aligned16(g) && aligned16(mom) && ((uintptr_t)p_bf16 & 7) == 0,
+  DTC_CHECK_ARG(aligned(p, 16) && aligned(g, 16) && aligned(mom, 16) && aligned(p_bf16, 8),
                 "lars_flat: p, g and momentum_buf must be 16-byte aligned, p_bf16 8-byte aligned");
   DTC_CHECK_ARG(plan->dev, "lars_flat: the plan is not bound to device memory (dtc_segplan_bind)");
   launch_norms(plan, p, g, RatioArgs{lr, wd, trust_coef, eps, trust_clip}, inv_scale, seg_out, st);

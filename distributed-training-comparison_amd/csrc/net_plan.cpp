@@ -2,6 +2,7 @@
 // and capture registries, slab sizing), the DDP buckets, and the entry points that create, bind and query an
 // executor. Nothing here launches a kernel.
 #include <algorithm>
+#include "flat.h"
 #include "net.h"
 
 namespace dtc {
@@ -436,9 +437,8 @@ int dtc_rn18_set_grad_accum(dtc_net* net, float* acc, int mode) {
     DTC_CHECK_ARG(n.mem.g != nullptr, "dtc_rn18_set_grad_accum: call after dtc_rn18_bind");
   }
   if (acc != nullptr) {
-    DTC_CHECK_ARG(((uintptr_t)acc & 15) == 0, "dtc_rn18_set_grad_accum: acc must be 16-byte aligned");
-    const uintptr_t a0 = (uintptr_t)acc, g0 = (uintptr_t)n.mem.g, bytes = (uintptr_t)n.flat_numel * 4;
-    DTC_CHECK_ARG(n.mem.g == nullptr || a0 + bytes <= g0 || g0 + bytes <= a0,
+    DTC_CHECK_ARG(aligned(acc, 16), "dtc_rn18_set_grad_accum: acc must be 16-byte aligned");
+    DTC_CHECK_ARG(n.mem.g == nullptr || !ranges_overlap(acc, n.flat_numel * 4, n.mem.g, n.flat_numel * 4),
                   "dtc_rn18_set_grad_accum: acc overlaps the bound gradient buffer");
   }
   n.accum = acc;
@@ -457,9 +457,8 @@ int dtc_rn18_set_grad_compress(dtc_net* net, uint16_t* staging, int mode) {
     DTC_CHECK_ARG(n.mem.g != nullptr, "dtc_rn18_set_grad_compress: call after dtc_rn18_bind");
   }
   if (staging != nullptr) {
-    DTC_CHECK_ARG(((uintptr_t)staging & 15) == 0, "dtc_rn18_set_grad_compress: staging must be 16-byte aligned");
-    const uintptr_t s0 = (uintptr_t)staging, g0 = (uintptr_t)n.mem.g, numel = (uintptr_t)n.flat_numel;
-    DTC_CHECK_ARG(n.mem.g == nullptr || s0 + numel * 2 <= g0 || g0 + numel * 4 <= s0,
+    DTC_CHECK_ARG(aligned(staging, 16), "dtc_rn18_set_grad_compress: staging must be 16-byte aligned");
+    DTC_CHECK_ARG(n.mem.g == nullptr || !ranges_overlap(staging, n.flat_numel * 2, n.mem.g, n.flat_numel * 4),
                   "dtc_rn18_set_grad_compress: staging overlaps the bound gradient buffer");
   }
   n.compress = staging;

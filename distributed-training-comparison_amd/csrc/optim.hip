@@ -8,12 +8,10 @@
 // GradScaler semantics (torch._amp_update_scale_): a step whose gradients hold inf/NaN is
 // skipped entirely; scale *= backoff on overflow, *= growth after `interval` clean steps.
 // The step also refreshes the bf16 shadow of every parameter (the GEMM operand layout).
-#include "common.h"
+#include "flat.h"
 #include "kernels.h"
 
 namespace dtc {
-
-static bool aligned16(const void* a) { return ((uintptr_t)a & 15) == 0; }
 
 __global__ void __launch_bounds__(256) sgd_nesterov_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                           float* __restrict__ m, u16* __restrict__ pb, int64_t n4,
@@ -26,26 +24,20 @@ __global__ void __launch_bounds__(256) sgd_nesterov_kernel(float* __restrict__ p
     f32x4 pv = *(const f32x4*)(p + i * 4);
     const f32x4 gv = *(const f32x4*)(g + i * 4);
     f32x4 mv = *(const f32x4*)(m + i * 4);
-    f32x4 d = gv * is + pv * wd;
-    mv = mv * mu + d;
-    d = d + mv * mu;
-    pv = pv - d * lr;
+    momentum_step<true>(pv, mv, gv * is + pv * wd, mu, lr);
     *(f32x4*)(p + i * 4) = pv;
     *(f32x4*)(m + i * 4) = mv;
-    uint2 w;
-    w.x = pack_bf2(pv[0], pv[1]);
-    w.y = pack_bf2(pv[2], pv[3]);
-    *(uint2*)(pb + i * 4) = w;
+    store_bf16x4(pb + i * 4, pv);
   }
 }
 
 int sgd_nesterov(float* p, const float* g, float* mom, u16* p_bf16, int64_t n, float lr, float wd, float mu,
                  const float* inv_scale, const int* found_inf, hipStream_t st) {
-  DTC_CHECK_ARG(p && g && mom && p_bf16 && n > 0 && (n % 4) == 0, "sgd_nesterov: bad args (n=%lld)", (long long)n);
-  DTC_CHECK_ARG(aligned16(p) && aligned16(g) && aligned16(mom) && ((uintptr_t)p_bf16 & 7) == 0,
+  DTC_CHECK_ARG(p && g && mom && p_bf16 && mult4(n), "sgd_nesterov: bad args (n=%lld)", (long long)n);
+  DTC_CHECK_ARG(aligned(p, 16) && aligned(g, 16) && aligned(mom, 16) && aligned(p_bf16, 8),
                 "sgd_nesterov: p, g and momentum must be 16-byte aligned, p_bf16 8-byte aligned");
   const int64_t n4 = n / 4;
-  const int blocks = (int)std::min<int64_t>(2048, (n4 + 255) / 256);
+  const int blocks = flat_blocks(n4, 256, 2048);
   DTC_KLAUNCH(sgd_nesterov_kernel, dim3(blocks), dim3(256), 0, st, p, g, mom, p_bf16, n4, lr, wd, mu, inv_scale,
                      found_inf);
   DTC_LAUNCH_CHECK();
@@ -119,10 +111,7 @@ __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, const 
     *(f32x4*)(p + i * 4) = pv;
     *(f32x4*)(m + i * 4) = mv;
     *(f32x4*)(v + i * 4) = vv;
-    uint2 w;
-    w.x = pack_bf2(pv[0], pv[1]);
-    w.y = pack_bf2(pv[2], pv[3]);
-    *(uint2*)(pb + i * 4) = w;
+    store_bf16x4(pb + i * 4, pv);
   }
 }
 
@@ -130,16 +119,16 @@ int adam_flat(float* p, const float* g, float* m, float* v, u16* p_bf16, int64_t
               double beta1, double beta2, double eps, double wd, int decoupled, const float* inv_scale,
               const int* found_inf, hipStream_t st) {
   DTC_CHECK_ARG(p && g && m && v && p_bf16 && state, "adam_flat: null pointer");
-  DTC_CHECK_ARG(n > 0 && (n % 4) == 0, "adam_flat: n = %lld must be a positive multiple of 4", (long long)n);
-  DTC_CHECK_ARG(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && ((uintptr_t)p_bf16 & 7) == 0 &&
-                    ((uintptr_t)state & 15) == 0,
+  DTC_CHECK_ARG(mult4(n), "adam_flat: n = %lld must be a positive multiple of 4", (long long)n);
+  DTC_CHECK_ARG(aligned(p, 16) && aligned(g, 16) && aligned(m, 16) && aligned(v, 16) && aligned(p_bf16, 8) &&
+                    aligned(state, 16),
                 "adam_flat: p, g, m, v and state must be 16-byte aligned, p_bf16 8-byte aligned");
   DTC_CHECK_ARG(eps > 0.0, "adam_flat: eps = %g must be positive", eps);
   DTC_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0,
                 "adam_flat: betas (%g, %g) must lie in [0, 1)", beta1, beta2);
   DTC_CHECK_ARG(lr >= 0.0 && wd >= 0.0, "adam_flat: lr = %g and weight_decay = %g must not be negative", lr, wd);
   const int64_t n4 = n / 4;
-  const int blocks = (int)std::min<int64_t>(2048, (n4 + 255) / 256);
+  const int blocks = flat_blocks(n4, 256, 2048);
   DTC_KLAUNCH(adam_tick_kernel, dim3(1), dim3(1), 0, st, (AdamState*)state, lr, beta1, beta2, found_inf);
   const float omb1 = (float)(1.0 - beta1), b2 = (float)beta2, omb2 = (float)(1.0 - beta2);
   const float decay = (float)(1.0 - lr * wd);
@@ -158,47 +147,27 @@ int adam_flat(float* p, const float* g, float* m, float* v, u16* p_bf16, int64_t
 // folded in: total_norm = inv_scale * sqrt(sum g^2), grad_mult = inv_scale * min(1, max_norm / (total_norm
 // + 1e-6)). The optimizer kernels take grad_mult where they would take inv_scale, so the clip costs one
 // read pass and no write pass. Squares are accumulated in double (loss-scaled gradients overflow and
-// underflow fp32 squares) and in a fixed order -- per thread in index order, a butterfly over the wave, the
-// block's waves in index order, one workspace slot per block, the slots in index order -- with no
+// underflow fp32 squares) and in a fixed order -- per thread in index order, the workgroup by
+// block_sum_ordered (flat.h), one workspace slot per block, the slots in index order -- with no
 // floating-point atomics: the result is bit-identical from run to run.
 constexpr int GN_THREADS = 1024;  // one workgroup per CU fills it (16 waves), and keeps the slot count small
 constexpr int GN_MAX_BLOCKS = 256;
-static int grad_norm_blocks(int64_t n) {
-  return (int)std::max<int64_t>(1, std::min<int64_t>(GN_MAX_BLOCKS, (n / 4 + GN_THREADS - 1) / GN_THREADS));
-}
+static int grad_norm_blocks(int64_t n) { return flat_blocks(n / 4, GN_THREADS, GN_MAX_BLOCKS); }
 size_t grad_norm_workspace_bytes(int64_t n) { return n > 0 ? (size_t)grad_norm_blocks(n) * sizeof(double) : 0; }
-
-__device__ __forceinline__ double sumsq4(double acc, const f32x4& a) {
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const double d = (double)a[k];
-    acc += d * d;
-  }
-  return acc;
-}
 
 __global__ void __launch_bounds__(GN_THREADS) grad_sumsq_kernel(const float* __restrict__ g, int64_t n4,
                                                                 double* __restrict__ slots) {
   const int64_t stride = (int64_t)gridDim.x * GN_THREADS;
   const f32x4* __restrict__ g4 = (const f32x4*)g;
-  double acc = 0.0;
+  double acc[1] = {0.0};
   int64_t i = blockIdx.x * (int64_t)GN_THREADS + threadIdx.x;
   for (; i + 3 * stride < n4; i += 4 * stride) {  // four loads in flight per thread per trip
     const f32x4 a = g4[i], b = g4[i + stride], c = g4[i + 2 * stride], d = g4[i + 3 * stride];
-    acc = sumsq4(sumsq4(sumsq4(sumsq4(acc, a), b), c), d);
+    acc[0] = sumsq4(sumsq4(sumsq4(sumsq4(acc[0], a), b), c), d);
   }
-  for (; i < n4; i += stride) acc = sumsq4(acc, g4[i]);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);  // a + b == b + a: every lane gets the same bits
-  __shared__ double wsum[GN_THREADS / 64];
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double s = wsum[0];
-#pragma unroll
-    for (int w = 1; w < GN_THREADS / 64; ++w) s += wsum[w];
-    slots[blockIdx.x] = s;
-  }
+  for (; i < n4; i += stride) acc[0] = sumsq4(acc[0], g4[i]);
+  block_sum_ordered<GN_THREADS>(acc);
+  if (threadIdx.x == 0) slots[blockIdx.x] = acc[0];
 }
 
 __global__ void __launch_bounds__(64) grad_norm_finalize_kernel(const double* __restrict__ slots, int nslots,
@@ -224,8 +193,8 @@ __global__ void __launch_bounds__(64) grad_norm_finalize_kernel(const double* __
 int grad_norm_clip(const float* g, int64_t n, const float* inv_scale, double max_norm, void* workspace,
                    float* total_norm, float* grad_mult, hipStream_t st) {
   DTC_CHECK_ARG(g && workspace && total_norm && grad_mult, "grad_norm_clip: null pointer");
-  DTC_CHECK_ARG(n > 0 && (n % 4) == 0, "grad_norm_clip: n = %lld must be a positive multiple of 4", (long long)n);
-  DTC_CHECK_ARG(aligned16(g) && ((uintptr_t)workspace & 7) == 0,
+  DTC_CHECK_ARG(mult4(n), "grad_norm_clip: n = %lld must be a positive multiple of 4", (long long)n);
+  DTC_CHECK_ARG(aligned(g, 16) && aligned(workspace, 8),
                 "grad_norm_clip: g must be 16-byte aligned, the workspace 8-byte aligned");
   DTC_CHECK_ARG(max_norm > 0.0, "grad_norm_clip: max_norm = %g must be positive", max_norm);
   const int blocks = grad_norm_blocks(n);
@@ -236,31 +205,26 @@ int grad_norm_clip(const float* g, int64_t n, const float* inv_scale, double max
   return 0;
 }
 
-__global__ void cast_f32_bf16_kernel(const float* __restrict__ s, u16* __restrict__ d, int64_t n) {
-  for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) d[i] = f2bf(s[i]);
-}
-
+// ---------------------------------------------------------------- element-wise operations (flat_map_kernel, flat.h)
+struct CastBf16 {
+  const float* s;
+  u16* d;
+  __device__ void operator()(int64_t i) const { d[i] = f2bf(s[i]); }
+};
 int cast_f32_bf16(const float* src, u16* dst, int64_t n, hipStream_t st) {
   DTC_CHECK_ARG(src && dst && n > 0, "cast_f32_bf16: bad args");
-  const int blocks = (int)std::min<int64_t>(2048, (n + 255) / 256);
-  DTC_KLAUNCH(cast_f32_bf16_kernel, dim3(blocks), dim3(256), 0, st, src, dst, n);
-  DTC_LAUNCH_CHECK();
-  return 0;
+  return launch_map(n, 2048, st, CastBf16{src, dst});
 }
 
-__global__ void zero_kernel(uint2* __restrict__ p, int64_t n) {
-  for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) p[i] = uint2{0u, 0u};
-}
-
+struct Zero8 {
+  uint2* p;
+  __device__ void operator()(int64_t i) const { p[i] = uint2{0u, 0u}; }
+};
 // A kernel, not hipMemsetAsync: inside a captured graph a memset node is a separate (fill) dispatch
 int zero_bytes(void* p, size_t bytes, hipStream_t st) {
-  DTC_CHECK_ARG(p && bytes % 8 == 0 && ((uintptr_t)p & 7) == 0, "zero_bytes: 8-byte aligned ranges only");
+  DTC_CHECK_ARG(p && bytes % 8 == 0 && aligned(p, 8), "zero_bytes: 8-byte aligned ranges only");
   if (bytes == 0) return 0;
-  const int64_t n = (int64_t)(bytes / 8);
-  const int blocks = (int)std::min<int64_t>(1024, (n + 255) / 256);
-  DTC_KLAUNCH(zero_kernel, dim3(blocks), dim3(256), 0, st, (uint2*)p, n);
-  DTC_LAUNCH_CHECK();
-  return 0;
+  return launch_map((int64_t)(bytes / 8), 1024, st, Zero8{(uint2*)p});
 }
 
 // The executor's forward prologue: the caller's input copied into the executor's own buffer (the
@@ -273,124 +237,101 @@ __global__ void copy_zero_kernel(const uint4* __restrict__ src, uint4* __restric
 }
 
 int copy_and_zero(const void* src, void* dst, size_t bytes, void* zp, size_t zbytes, hipStream_t st) {
-  DTC_CHECK_ARG(src && dst && zp && bytes % 16 == 0 && zbytes % 8 == 0 && ((uintptr_t)src & 15) == 0 &&
-                    ((uintptr_t)dst & 15) == 0 && ((uintptr_t)zp & 7) == 0,
+  DTC_CHECK_ARG(src && dst && zp && bytes % 16 == 0 && zbytes % 8 == 0 && aligned(src, 16) && aligned(dst, 16) &&
+                    aligned(zp, 8),
                 "copy_and_zero: 16-byte aligned copy, 8-byte aligned zero range");
   const int64_t n16 = (int64_t)(bytes / 16), n8 = (int64_t)(zbytes / 8);
-  const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(1024, (std::max(n16, n8) + 255) / 256));
-  DTC_KLAUNCH(copy_zero_kernel, dim3(blocks), dim3(256), 0, st, (const uint4*)src, (uint4*)dst, n16, (uint2*)zp,
-                     n8);
+  DTC_KLAUNCH(copy_zero_kernel, dim3(flat_blocks(std::max(n16, n8), 256, 1024)), dim3(256), 0, st, (const uint4*)src,
+              (uint4*)dst, n16, (uint2*)zp, n8);
   DTC_LAUNCH_CHECK();
   return 0;
 }
-
 
 template <typename T>
-__global__ void scale_kernel(T* __restrict__ x, int64_t n, T f) {
-  for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) x[i] *= f;
-}
-
+struct Scale {
+  T* x;
+  T f;
+  __device__ void operator()(int64_t i) const { x[i] *= f; }
+};
+// bf16 words: x = bf16_rne(widen(x) * f), one fp32 multiply (__fmul_rn) and one rounding per element
+struct ScaleBf16 {
+  u16* x;
+  float f;
+  __device__ void operator()(int64_t i) const { x[i] = f2bf(__fmul_rn(bf2f(x[i]), f)); }
+};
 int scale_f32(float* x, int64_t n, float f, hipStream_t st) {
   DTC_CHECK_ARG(x && n > 0, "scale_f32: bad args");
-  const int blocks = (int)std::min<int64_t>(2048, (n + 255) / 256);
-  DTC_KLAUNCH(scale_kernel<float>, dim3(blocks), dim3(256), 0, st, x, n, f);
-  DTC_LAUNCH_CHECK();
-  return 0;
+  return launch_map(n, 2048, st, Scale<float>{x, f});
 }
-
-// bf16 words: x = bf16_rne(widen(x) * f), one fp32 multiply (__fmul_rn) and one rounding per element
-__global__ void scale_bf16_kernel(u16* __restrict__ x, int64_t n, float f) {
-  for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
-    x[i] = f2bf(__fmul_rn(bf2f(x[i]), f));
-}
-
 int scale_bf16(u16* x, int64_t n, float f, hipStream_t st) {
   DTC_CHECK_ARG(x && n > 0, "scale_bf16: bad args");
-  const int blocks = (int)std::min<int64_t>(2048, (n + 255) / 256);
-  DTC_KLAUNCH(scale_bf16_kernel, dim3(blocks), dim3(256), 0, st, x, n, f);
-  DTC_LAUNCH_CHECK();
-  return 0;
+  return launch_map(n, 2048, st, ScaleBf16{x, f});
 }
-
 int scale_f64(double* x, int64_t n, double f, hipStream_t st) {
   DTC_CHECK_ARG(x && n > 0, "scale_f64: bad args");
-  const int blocks = (int)std::min<int64_t>(2048, (n + 255) / 256);
-  DTC_KLAUNCH(scale_kernel<double>, dim3(blocks), dim3(256), 0, st, x, n, f);
-  DTC_LAUNCH_CHECK();
-  return 0;
+  return launch_map(n, 2048, st, Scale<double>{x, f});
 }
-
 int scale_i64(int64_t* x, int64_t n, int64_t f, hipStream_t st) {
   DTC_CHECK_ARG(x && n > 0, "scale_i64: bad args");
-  const int blocks = (int)std::min<int64_t>(2048, (n + 255) / 256);
-  DTC_KLAUNCH(scale_kernel<int64_t>, dim3(blocks), dim3(256), 0, st, x, n, f);
-  DTC_LAUNCH_CHECK();
-  return 0;
+  return launch_map(n, 2048, st, Scale<int64_t>{x, f});
 }
 
-__global__ void amp_scale_kernel(const float* __restrict__ x, const float* __restrict__ scale, float* __restrict__ out,
-                                 int64_t n) {
-  const float s = *scale;
-  for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) out[i] = x[i] * s;
-}
-
+struct AmpScale {
+  const float *x, *scale;
+  float* out;
+  __device__ void operator()(int64_t i) const { out[i] = x[i] * *scale; }
+};
 int amp_scale(const float* x, const float* scale, float* out, int64_t n, hipStream_t st) {
   DTC_CHECK_ARG(x && scale && out && n > 0, "amp_scale: bad args");
-  const int blocks = (int)std::min<int64_t>(1024, (n + 255) / 256);
-  DTC_KLAUNCH(amp_scale_kernel, dim3(blocks), dim3(256), 0, st, x, scale, out, n);
-  DTC_LAUNCH_CHECK();
-  return 0;
+  return launch_map(n, 1024, st, AmpScale{x, scale, out});
 }
 
-__global__ void add_f32_kernel(float* __restrict__ d, const float* __restrict__ s, int64_t n4) {
-  for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
-    f32x4 a = ((f32x4*)d)[i];
-    a += ((const f32x4*)s)[i];
-    ((f32x4*)d)[i] = a;
+struct AddF32 {
+  f32x4* d;
+  const f32x4* s;
+  __device__ void operator()(int64_t i) const {
+    f32x4 a = d[i];
+    a += s[i];
+    d[i] = a;
   }
-}
-
+};
 int add_f32(float* dst, const float* src, int64_t n, hipStream_t st) {
-  DTC_CHECK_ARG(dst && src && n > 0 && n % 4 == 0 && ((uintptr_t)dst & 15) == 0 && ((uintptr_t)src & 15) == 0,
+  DTC_CHECK_ARG(dst && src && mult4(n) && aligned(dst, 16) && aligned(src, 16),
                 "add_f32: bad args (n %% 4 and 16-byte alignment required)");
-  const int blocks = (int)std::min<int64_t>(2048, (n / 4 + 255) / 256);
-  DTC_KLAUNCH(add_f32_kernel, dim3(blocks), dim3(256), 0, st, dst, src, n / 4);
-  DTC_LAUNCH_CHECK();
-  return 0;
+  return launch_map(n / 4, 2048, st, AddF32{(f32x4*)dst, (const f32x4*)src});
 }
 
 // In-process thread-group communicator (comm.cpp): out_r[i] = sum_q in_q[i] for every rank r, the
 // ranks' buffers summed in rank order (fixed; for two ranks the fp32 sum itself), read before written
 // per element so the all-reduce is in place in every rank's buffer.
 template <typename T>
-__global__ void group_sum_kernel(GroupPtrs g, int w, int64_t n) {
-  for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+struct GroupSum {
+  GroupPtrs g;
+  int w;
+  __device__ void operator()(int64_t i) const {
     T s = ((const T*)g.p[0])[i];
     for (int r = 1; r < w; ++r) s += ((const T*)g.p[r])[i];
     for (int r = 0; r < w; ++r) ((T*)g.p[r])[i] = s;
   }
-}
-
+};
 // bf16 buffers: every rank's word <- bf16_rne(((widen(c_0) + widen(c_1)) + ...) + widen(c_{w-1})), fp32 adds in
 // rank order (__fadd_rn), rounded once; read before written per element, as above
-__global__ void group_sum_bf16_kernel(GroupPtrs g, int w, int64_t n) {
-  for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+struct GroupSumBf16 {
+  GroupPtrs g;
+  int w;
+  __device__ void operator()(int64_t i) const {
     float s = bf2f(((const u16*)g.p[0])[i]);
     for (int r = 1; r < w; ++r) s = __fadd_rn(s, bf2f(((const u16*)g.p[r])[i]));
     const u16 o = f2bf(s);
     for (int r = 0; r < w; ++r) ((u16*)g.p[r])[i] = o;
   }
-}
-
+};
 int group_sum(const GroupPtrs& g, int w, int64_t n, int dtype, hipStream_t st) {
   DTC_CHECK_ARG(w >= 1 && w <= DTC_GROUP_MAX && n > 0 && dtype >= 0 && dtype <= 3, "group_sum: bad args");
-  const int blocks = (int)std::min<int64_t>(2048, (n + 255) / 256);
-  if (dtype == 0) DTC_KLAUNCH(group_sum_kernel<float>, dim3(blocks), dim3(256), 0, st, g, w, n);
-  else if (dtype == 1) DTC_KLAUNCH(group_sum_bf16_kernel, dim3(blocks), dim3(256), 0, st, g, w, n);
-  else if (dtype == 2) DTC_KLAUNCH(group_sum_kernel<int64_t>, dim3(blocks), dim3(256), 0, st, g, w, n);
-  else DTC_KLAUNCH(group_sum_kernel<double>, dim3(blocks), dim3(256), 0, st, g, w, n);
-  DTC_LAUNCH_CHECK();
-  return 0;
+  if (dtype == 0) return launch_map(n, 2048, st, GroupSum<float>{g, w});
+  if (dtype == 1) return launch_map(n, 2048, st, GroupSumBf16{g, w});
+  if (dtype == 2) return launch_map(n, 2048, st, GroupSum<int64_t>{g, w});
+  return launch_map(n, 2048, st, GroupSum<double>{g, w});
 }
 
 __global__ void amp_check_finite_kernel(const float* __restrict__ g, int64_t n, int* __restrict__ found) {
@@ -423,14 +364,10 @@ __global__ void amp_check_finite4_kernel(const float* __restrict__ g, int64_t n,
 
 int amp_check_finite(const float* g, int64_t n, int* found_inf, hipStream_t st) {
   DTC_CHECK_ARG(g && found_inf && n > 0, "amp_check_finite: bad args");
-  if (((uintptr_t)g & 15) == 0) {
-    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(1024, (n / 4 + 255) / 256));
-    DTC_KLAUNCH(amp_check_finite4_kernel, dim3(blocks), dim3(256), 0, st, g, n, found_inf);
-    DTC_LAUNCH_CHECK();
-    return 0;
-  }
-  const int blocks = (int)std::min<int64_t>(2048, (n + 255) / 256);
-  DTC_KLAUNCH(amp_check_finite_kernel, dim3(blocks), dim3(256), 0, st, g, n, found_inf);
+  if (aligned(g, 16))
+    DTC_KLAUNCH(amp_check_finite4_kernel, dim3(flat_blocks(n / 4, 256, 1024)), dim3(256), 0, st, g, n, found_inf);
+  else
+    DTC_KLAUNCH(amp_check_finite_kernel, dim3(flat_blocks(n, 256, 2048)), dim3(256), 0, st, g, n, found_inf);
   DTC_LAUNCH_CHECK();
   return 0;
 }
