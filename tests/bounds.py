@@ -43,6 +43,13 @@ bound of C + 1 terms, doubled as CONV_FACTOR is); bound tol(ref, d). fp32 execut
 Head dW / db (fp32 outputs, no bf16 term): scale * sum_n dl[n][j] * feat[n][c] over N images in any order, then
 the multiply by scale: 2 * (N + 1) * U * scale * (|dl|.T @ |feat|), and 2 * (N + 1) * U * scale * sum_n |dl|.
 
+Conv WGRAD (exact bf16 operands, fp32 accumulation, fp32 output, no bf16 term): dw[k,r,s,c] = scale * sum over
+the M = N*P*Q output pixels of dy[n,p,q,k] * x[n, p*st-pad+r, q*st-pad+s, c] (padding taps contribute exact zeros),
+the products exact in fp32, summed in any order (MFMA k-steps, split-K slabs, the reduce launch), then the multiply
+by scale: the length-M dot-product bound plus one rounding, (M + 1) * U * |scale| * S with S the same weight
+gradient of the absolute operands, doubled for the reasons CONV_FACTOR gives: 2 * (M + 1) * U * |scale| * S. The
+bound grows with M and has no teeth at large batches; it is meant for the small shapes that use it.
+
 SGD (Nesterov), all fp32: m' = mu*m + (g*is + wd*p), p' = p - lr*((g*is + wd*p) + mu*m'). With
 Tm = mu|m| + |g|*is + wd|p| every intermediate of the first chain is at most Tm in magnitude and the chain holds at
 most four roundings (g*is, wd*p, their sum, mu*m + that; fewer with FMA contraction): tol_m = 4 * U * Tm. With
@@ -122,6 +129,12 @@ def dgrad_tol(ref, dy, w, in_hw, stride, pad, res=None, dsc=None, wsc=None):
         S = S + O.conv2d_dgrad(np.abs(dsc), np.abs(wsc), in_hw, stride, 0)
         L += K
     return conv_tol(ref, S, L)
+
+
+def wgrad_tol(x, dy, R, S, stride, pad, scale=1.0):
+    """Bound on |dw - scale * O.conv2d_wgrad(x, dy, ...)| for the fp32 weight gradient [K,R,S,C]; M = N*P*Q."""
+    M = int(np.prod(np.shape(dy)[:3]))
+    return 2 * (M + 1) * U * abs(scale) * O.conv2d_wgrad(np.abs(x), np.abs(dy), R, S, stride, pad)
 
 
 # ----------------------------------------------------------------------------- batch norm

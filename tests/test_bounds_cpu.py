@@ -358,6 +358,51 @@ def test_head_bounds_hold_for_fp32_emulation_and_reject_planted_defects():
     print("head bounds, worst clean |err|/tol: " + ", ".join(f"{k} {v:.3f}" for k, v in worst.items()))
 
 
+def _wgrad_emu(x, dy, R, stride, pad, scale, order, drop=None):
+    """fp32 weight gradient, the output pixels summed one at a time in `order` (a permutation of the N*P*Q
+    pixels), then the multiply by scale; drop = (pixel, r, s): that pixel contributes nothing to tap (r, s)."""
+    cols = O._im2col(x, R, R, stride, pad).astype(np.float32)
+    Kn, Cn = dy.shape[3], x.shape[3]
+    cols = cols.reshape(-1, R, R, Cn)
+    d = dy.reshape(-1, Kn).astype(np.float32)
+    dw = np.zeros((Kn, R, R, Cn), np.float32)
+    for m in order:
+        t = cols[m].copy()
+        if drop is not None and drop[0] == m:
+            t[drop[1], drop[2]] = 0
+        dw = dw + d[m][:, None, None, None] * t[None]  # exact fp32 products (bf16 operands), one rounded add each
+    return dw * np.float32(scale)
+
+
+@pytest.mark.parametrize("R", [3, 1])
+def test_wgrad_bound_holds_for_shuffled_fp32_sum_and_rejects_a_dropped_tap(R):
+    """wgrad_tol at (3,7,7,64,64) stride 2 (an odd map: M = 3*4*4 = 48 output pixels, the last row's and column's
+    r = 2 / s = 2 taps are padding): the float64 reference re-summed in fp32 in a shuffled pixel order stays inside
+    the bound; one pixel's contribution dropped from one tap lands outside it."""
+    Nn, Hh, Ww, Cn, Kn = 3, 7, 7, 64, 64
+    pad, scale = (1 if R == 3 else 0), 0.5
+    g = np.random.default_rng(17)
+    x, dy = _rand_bf16((Nn, Hh, Ww, Cn), g), _rand_bf16((Nn, 4, 4, Kn), g)
+    ref = scale * O.conv2d_wgrad(x, dy, R, R, 2, pad)
+    tl = B.wgrad_tol(x, dy, R, R, 2, pad, scale)
+    assert tl.shape == ref.shape == (Kn, R, R, Cn) and (tl > 0).all()
+    order = g.permutation(Nn * 16)
+    clean = _wgrad_emu(x, dy, R, 2, pad, scale, order)
+    assert clean.dtype == np.float32
+    r = B.assert_within(clean, ref, tl, f"wgrad {R}x{R}")
+    print(f"wgrad {R}x{R} (3,7,7,64,64) stride 2: shuffled fp32 sum worst |err|/tol {r:.3f}, rel_err {rel_err(clean, ref):.2e}")
+    assert r < 1.0 and rel_err(clean, ref) < 1e-5
+    # an interior pixel of the middle image, its centre tap (in range for both filter sizes)
+    tap = (R // 2, R // 2)
+    m = _wgrad_emu(x, dy, R, 2, pad, scale, order, drop=(16 + 1 * 4 + 2,) + tap)
+    other = np.ones((R, R), bool)
+    other[tap] = False
+    assert np.array_equal(m[:, other], clean[:, other]) and not np.array_equal(m, clean)
+    _outside(m, ref, tl, f"wgrad {R}x{R} / one pixel dropped from one tap")
+    # the bound scales with |scale| and is symmetric in its sign
+    np.testing.assert_array_equal(B.wgrad_tol(x, dy, R, R, 2, pad, -2.0), 4 * tl)
+
+
 def _sgd_emu(p, g, m, lr, wd, mu, is_, once=False):
     """Unfused fp32 step (every product and sum rounded; the kernel may contract to FMAs), the decay term first.
     once: the look-ahead adds m' instead of mu * m' (momentum applied once)."""

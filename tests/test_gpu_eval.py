@@ -186,6 +186,42 @@ def test_eval_batch_partial(dtc, cuda, net, prec, n_valid):
         assert _record(rec) == _record(want) and _record(rec)[1] == n_valid
 
 
+@pytest.mark.parametrize("prec", ["bf16", "fp32"])
+def test_eval_batch_odd_extents(dtc, cuda, net, prec):
+    """eval_batch at 18x21 (every stride-2 block sees an odd map: even/odd, odd/odd, odd/even), batch 3, the full
+    batch (n_valid 3) and a short one (2), as test_eval_batch_partial: the valid rows bit-equal to the eval-mode
+    forward's, the padding rows finite, the record that of the valid rows; the weights untouched."""
+    import torch
+
+    model = net[0]
+    nb, h, w = 3, 18, 21
+    g = torch.Generator().manual_seed(23)
+    x = torch.randn(nb, 3, h, w, generator=g).to(cuda)
+    y = torch.randint(0, 100, (nb,), generator=g).to(cuda)
+    exe = model.executor(nb, h, w, prec)
+    ref = torch.empty(nb, 100, dtype=torch.float32, device=cuda)
+    exe.forward(x, ref, False)
+    torch.cuda.synchronize()
+    assert np.isfinite(ref.cpu().numpy()).all()
+    before = _state(model)
+    for n_valid in (3, 2):
+        want = dtc.ops.eval_metrics(ref[:n_valid].contiguous(), y[:n_valid].contiguous(), topk=5)
+        for poison in (False, True):
+            xin = x.clone()
+            if poison:
+                xin[n_valid:] = float("nan")
+            lg = torch.full((nb, 100), float("nan"), dtype=torch.float32, device=cuda)
+            rec = torch.zeros(4, dtype=torch.int32, device=cuda)
+            exe.eval_batch(xin, y, n_valid, 5, rec, logits=lg)
+            torch.cuda.synchronize()
+            assert np.array_equal(_bits(lg[:n_valid]), _bits(ref[:n_valid])), (prec, n_valid, poison)
+            assert np.isfinite(lg.cpu().numpy()).all()
+            assert np.isfinite(_loss_of(rec))
+            assert _record(rec) == _record(want) and _record(rec)[1] == n_valid
+    for a, b in zip(before, _state(model)):
+        assert np.array_equal(a, b)
+
+
 def test_backward_after_eval_batch_is_refused(dtc, cuda, net):
     import torch
 

@@ -9,7 +9,7 @@ import torch
 
 from oracle import resnet as R
 from tests.conftest import rel_err
-from tests.test_gpu_resnet import _np, _setup, _split_state, _teacher_forced
+from tests.test_gpu_resnet import ODD_SIZES, _hw, _np, _setup, _split_state, _teacher_forced
 
 pytestmark = pytest.mark.gpu
 
@@ -43,12 +43,29 @@ def test_fp32_per_layer_teacher_forced_non_square(dtc, cuda):
     assert len(errs) > 90
 
 
+@pytest.mark.parametrize("batch,hw,seed", ODD_SIZES, ids=["18x21", "28x28", "15x17"])
+def test_fp32_per_layer_teacher_forced_odd_extents(dtc, cuda, batch, hw, seed):
+    """Sizes whose stride-2 blocks see odd maps (tests/test_gpu_resnet.py::ODD_SIZES), every layer, fp32."""
+    errs = _teacher_forced(dtc, cuda, batch, hw=hw, seed=seed, precision="fp32")
+    assert len(errs) > 90
+
+
 def test_fp32_end_to_end_matches_oracle(dtc, cuda):
     """Free-running fp32 forward + backward vs the fp32 oracle (no rounding points anywhere): unlike
     bf16, fp32 stays close end to end -- logits and loss to 1e-5, every activation to 1e-4, every
     parameter gradient to 1e-3 (measured drift is fp32 summation order only), running statistics
     to 1e-5."""
-    model, sd, x, y = _setup(dtc, cuda, 8, seed=4)
+    _fp32_end_to_end(dtc, cuda, 8, 32)
+
+
+def test_fp32_end_to_end_matches_oracle_odd_extents(dtc, cuda):
+    """The same free-running step, with the same bounds, at 18x21 batch 3: every stride-2 block sees an odd map
+    (even/odd, odd/odd, odd/even)."""
+    _fp32_end_to_end(dtc, cuda, 3, (18, 21))
+
+
+def _fp32_end_to_end(dtc, cuda, batch, hw):
+    model, sd, x, y = _setup(dtc, cuda, batch, seed=4, hw=hw)
     model.precision = "fp32"
     crit = dtc.CrossEntropyLoss()
     logits = model(torch.from_numpy(x).to(cuda))
@@ -59,7 +76,7 @@ def test_fp32_end_to_end_matches_oracle(dtc, cuda):
     ref = R.forward_backward(params, bufs, x, y, bf16_mode=False, train=True, want_acts=True)
     assert rel_err(_np(logits), ref["logits"]) < 1e-5
     assert abs(float(loss) - ref["loss"]) < 1e-5 * max(1.0, abs(ref["loss"]))
-    acts = model.executor(8, 32, 32, "fp32").activations()
+    acts = model.executor(batch, *_hw(hw), "fp32").activations()
     for k, v in ref["acts"].items():
         e = rel_err(_np(acts[k]).reshape(v.shape), v)
         assert e < 1e-4, (k, e)

@@ -263,6 +263,11 @@ def _stem_ops(shape, seed):
 CASES = [
     ("igemm-1x5x7", {}, lambda: _conv_ops((1, 5, 7, 64, 64, 3, 1), 1)),
     ("igemm-ragged-splitk-s2", {}, lambda: _conv_ops((3, 4, 4, 256, 512, 3, 2), 1)),
+    # odd extents (tests/test_gpu_odd_extents.py): stride 2 at P = (H + 1) / 2, where tap r = 2 of the last output
+    # row is padding, and the stride-1 conv of the 7x7 map behind it (49 pixels per image: no halo tile fits)
+    ("igemm-odd-3x7x7-s2", {}, lambda: _conv_ops((3, 7, 7, 256, 512, 3, 2), 61)),
+    ("igemm-odd-2x9x11-s2", {}, lambda: _conv_ops((2, 9, 11, 128, 256, 3, 2), 62)),
+    ("igemm-odd-3x7x7-s1", {}, lambda: _conv_ops((3, 7, 7, 256, 256, 3, 1), 63)),
     ("halo-5x8x8-auto", {"halo_split": 0}, lambda: _conv_ops((5, 8, 8, 256, 256, 3, 1), 21, "fd")),
     ("halo-5x8x8-split2", {"halo_split": 2}, lambda: _conv_ops((5, 8, 8, 256, 256, 3, 1), 21, "fd")),
     ("halo-9x4x4-auto", {"halo_split": 0}, lambda: _conv_ops((9, 4, 4, 512, 256, 3, 1), 21, "fd")),

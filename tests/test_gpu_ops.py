@@ -150,6 +150,7 @@ def test_conv_wgrad(dtc, cuda, case):
     ref = 0.5 * O.conv2d_wgrad(x, dy, R, R, st, pad)
     # fp32 accumulation of exact bf16 products: only summation-order differences remain
     assert rel_err(dw.cpu().numpy(), ref) < 1e-5
+    _within(f"conv_wgrad {case}", ("dw", dw.cpu().numpy(), ref, B.wgrad_tol(x, dy, R, R, st, pad, 0.5)))
 
 
 @pytest.mark.parametrize("case", S2_CASES + S2_GEN_CASES)

@@ -10,7 +10,21 @@ End-to-end checks compare free-running forward/backward. Two CORRECT bf16 implem
 apart with depth: the oracle run twice with fp32 vs fp64 conv accumulation differs by 1.8% at
 layer4 and 0.6% on logits (batch 2), and by 21% on the concatenated parameter gradient (batch 2
 and 8 alike; the stem/layer1 weight gradients of a freshly initialised BN network are dominated
-by amplified rounding noise). The free-running bounds below are set from those measurements.
+by amplified rounding noise). The free-running bounds below were set from those measurements.
+
+A second oracle-vs-oracle measurement, and the one that stands where the two differ (it is the larger, and the one
+taken at every size the free-running tests run): two bf16 oracle runs (fp64 accumulation both) whose parameters
+differ by a one-ulp perturbation (_perturb_ulp), worst of three perturbation seeds, the oracle alone on the CPU:
+
+    size, batch     logits   worst activation  gradient  linear.weight grad  running stats  loss
+    32x32, 2        7.9e-3   2.6e-2            0.27      8.3e-3              5.7e-3         4.6e-4
+    32x32, 8        8.8e-3   2.4e-2            0.25      7.8e-3              2.6e-3         3.4e-4
+    18x21, 3        1.1e-2   2.6e-2            0.26      1.1e-2              6.2e-3         8.7e-4
+    28x28, 4        8.7e-3   2.4e-2            0.25      8.4e-3              3.7e-3         1.0e-3
+
+Against these the bounds (logits 3e-2, loss 1e-2, activations 5e-2, gradient 0.35, linear.weight 2e-2, running
+statistics 2e-2) keep margins of 2.7x, 10x, 1.9x, 1.3x, 1.8x and 3.2x at the worst size; the gradient's 1.3x is the
+narrowest (not the 1.67x the 21% figure suggests). The odd sizes drift as the 32x32 ones do, so they share the bounds.
 """
 import numpy as np
 import pytest
@@ -428,6 +442,30 @@ def test_per_layer_teacher_forced_non_square(dtc, cuda):
     assert len(errs) > 90
 
 
+# Odd extents: every other size here (32, 224, 8, 24x40) hands an even map to each stride-2 block, which is what
+# the stride-2 tiled kernels (parity-class / sub-pixel dgrad, column-split halo forward and wgrad, the fused
+# shortcut launches, the compact shortcut residual) require; these three send stride-2 layers down the generic
+# implicit-GEMM code at P = (H + 1) / 2 instead (tests/test_gpu_odd_extents.py runs the same shapes per kernel).
+ODD_SIZES = [
+    (3, (18, 21), 51),  # maps 18x21, 9x11, 5x6, 3x3: the stride-2 inputs are even/odd, odd/odd, odd/even
+    (4, 28, 52),        # maps 28, 14, 7, 4: layers 2.0 / 3.0 even (fused projection blocks), layer 4.0 odd
+    (3, (15, 17), 53),  # the image itself odd: odd stem extents, layer1 off conv_c64; maps 15x17, 8x9, 4x5, 2x3
+]
+
+
+@pytest.mark.parametrize("batch,hw,seed", ODD_SIZES, ids=["18x21", "28x28", "15x17"])
+def test_per_layer_teacher_forced_odd_extents(dtc, cuda, batch, hw, seed):
+    errs = _teacher_forced(dtc, cuda, batch, hw=hw, seed=seed)
+    assert len(errs) > 90
+
+
+def test_per_layer_teacher_forced_odd_extents_bn_state_and_eval(dtc, cuda):
+    """18x21 once more from a drawn BN state (tests/test_gpu_bn_affine.py's seed; checked on the CPU with the oracle:
+    no dead activation at this size either), then the eval-mode forward on the statistics that step wrote."""
+    errs = _teacher_forced(dtc, cuda, 3, hw=(18, 21), seed=51, bn_state_seed=7, eval_after=True)
+    assert len(errs) > 130
+
+
 # BASELINE config 2 at its own size (B=256, 32x32): the launches bench.py times -- conv_c64's
 # multi-tile persistent walk, the batched wgrad_halo split plan on layer1, the halo layer2 tiles, split-K
 # layer3/4 fwd/dgrad/wgrad, the stride-2 parity classes -- against the oracle. Split by stage so each
@@ -518,8 +556,22 @@ def test_config5_b512_224_step_properties(dtc, cuda):
 @pytest.mark.parametrize("batch", [2, 8])
 def test_end_to_end_drift_bounded(dtc, cuda, batch):
     """Free-running forward/backward vs the oracle. Bounds: logits/loss 3e-2 / 1e-2, every
-    activation 5e-2, concatenated gradient 0.35 (oracle-vs-oracle: 1.8%, 0.6%, 21%)."""
-    model, sd, x, y = _setup(dtc, cuda, batch)
+    activation 5e-2, concatenated gradient 0.35 (the oracle-vs-oracle figures behind them, and the margins: the
+    module docstring)."""
+    _end_to_end_drift(dtc, cuda, batch, 32)
+
+
+@pytest.mark.parametrize("batch,hw", [(3, (18, 21)), (4, 28)], ids=["18x21", "28x28"])
+def test_end_to_end_drift_bounded_odd_extents(dtc, cuda, batch, hw):
+    """The same free-running comparison, with the same bounds, at sizes whose stride-2 blocks see odd maps (28x28:
+    two fused projection blocks and the unfused layer4.0 in one backward). The bounds need no widening there: the
+    oracle against itself under a one-ulp perturbation drifts at 18x21 and 28x28 as it does at 32x32 (the table in
+    the module docstring)."""
+    _end_to_end_drift(dtc, cuda, batch, hw)
+
+
+def _end_to_end_drift(dtc, cuda, batch, hw):
+    model, sd, x, y = _setup(dtc, cuda, batch, hw=hw)
     crit = dtc.CrossEntropyLoss()
     logits = model(torch.from_numpy(x).to(cuda))
     loss = crit(logits, torch.from_numpy(y).to(cuda))
@@ -529,7 +581,7 @@ def test_end_to_end_drift_bounded(dtc, cuda, batch):
     ref = R.forward_backward(params, bufs, x, y, bf16_mode=True, train=True, want_acts=True)
     assert rel_err(_np(logits), ref["logits"]) < 3e-2
     assert abs(float(loss) - ref["loss"]) < 1e-2 * max(1.0, abs(ref["loss"]))
-    acts = model.executor(batch, 32, 32).activations()
+    acts = model.executor(batch, *_hw(hw)).activations()
     worst = max(rel_err(_np(acts[k]).reshape(v.shape), v) for k, v in ref["acts"].items())
     assert worst < 5e-2
     g_exe = np.concatenate([_np(p.grad).ravel() for _, p in model.named_parameters()])
@@ -938,6 +990,56 @@ def test_fused_shortcut_dgrad_and_wgrad_match_separate(dtc, cuda, batch):
                 elif pe.name.startswith("layer3.1.bn2"):
                     assert rel_err(b, a) < 1e-2, (graphs, rep, pe.name, rel_err(b, a))
                 assert np.isfinite(b).all()
+
+
+@pytest.mark.parametrize("batch,hw", [(8, 28), (3, (18, 21))], ids=["28x28", "18x21"])
+def test_shortcut_options_at_odd_extents(dtc, cuda, batch, hw):
+    """The projection-block options where some (28x28: layer4.0, a 7x7 input) or all (18x21) stride-2 blocks see an
+    odd map and must fall back per block, graphs on and off:
+    * sc_compact 1 vs 0: bit-identical (test_shortcut_compact_dx_matches_full);
+    * graph capture + replay vs eager launches: bit-identical;
+    * dgrad_scf / wgrad_s2 on vs off, as test_fused_shortcut_dgrad_and_wgrad_match_separate: wgrad_s2 within 1e-5
+      on every parameter; dgrad_scf bit-identical on layer4 and linear, layer3.1.bn2 within 1e-2, everything finite.
+    At 18x21 no block can fuse or compact, so every pair must be bit-identical."""
+    lib = dtc._native.lib
+    lay = dtc.nn.Layout(100, 25.0)
+    none_fuses = hw != 28
+
+    def run(opts, graphs):
+        prev = {k: lib.dtc_get_option(k) for k in opts}
+        try:
+            for k, v in opts.items():
+                lib.dtc_set_option(k, v)
+            return _grads_repeated(dtc, cuda, graphs, batch=batch, hw=hw)
+        finally:
+            for k, v in prev.items():
+                lib.dtc_set_option(k, v)
+
+    default = {}
+    for graphs in (1, 0):
+        default[graphs] = run({}, graphs)
+        full = run({b"sc_compact": 0}, graphs)
+        base = run({b"dgrad_scf": 0, b"wgrad_s2": 0}, graphs)
+        ws2 = run({b"dgrad_scf": 0, b"wgrad_s2": 1}, graphs)
+        dsf = run({b"dgrad_scf": 1, b"wgrad_s2": 0}, graphs)
+        for rep in range(2):
+            assert np.isfinite(default[graphs][rep]).all()
+            _assert_same_grads(dtc, default[graphs][rep], full[rep], f"sc_compact rep {rep} graphs {graphs}")
+            if none_fuses:
+                for what, g in (("wgrad_s2", ws2), ("dgrad_scf", dsf), ("default", default[graphs])):
+                    _assert_same_grads(dtc, base[rep], g[rep], f"{what} vs separate, rep {rep} graphs {graphs}")
+                continue
+            for pe in lay.params:
+                a = base[rep][pe.offset:pe.offset + pe.numel]
+                assert rel_err(ws2[rep][pe.offset:pe.offset + pe.numel], a) < 1e-5, (graphs, rep, pe.name)
+                b = dsf[rep][pe.offset:pe.offset + pe.numel]
+                if pe.name.startswith(("layer4", "linear")):
+                    assert np.array_equal(a, b), (graphs, rep, pe.name)
+                elif pe.name.startswith("layer3.1.bn2"):
+                    assert rel_err(b, a) < 1e-2, (graphs, rep, pe.name, rel_err(b, a))
+                assert np.isfinite(b).all()
+    for rep in range(2):
+        _assert_same_grads(dtc, default[1][rep], default[0][rep], f"graph replay vs eager, rep {rep}")
 
 
 @pytest.mark.parametrize("batch,hw", [(8, 32), (256, 32), (8, 8)])
