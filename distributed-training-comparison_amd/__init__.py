@@ -18,7 +18,7 @@ from .nn import (BasicBlock, CrossEntropyLoss, EvalResult, MixedTarget, ResNet, 
                  SyncBatchNorm)
 from . import ema, optim  # noqa: F401
 from .ema import ModelEma  # noqa: F401
-from .optim import LARS, SGD, Adam, AdamW, clip_grad_norm_  # noqa: F401
+from .optim import LARS, SAM, SGD, Adam, AdamW, clip_grad_norm_  # noqa: F401
 from .parallel import DDP, Comm, DataParallel, DistributedDataParallel, barrier  # noqa: F401
 from . import parallel  # noqa: F401
 from . import trainer  # noqa: F401

@@ -74,6 +74,16 @@ class EmaRange(C.Structure):
 PEmaRange = C.POINTER(EmaRange)
 
 
+class SamKeep(C.Structure):
+    """dtc_sam_keep: one small range dtc_sam_perturb copies aside and dtc_sam_restore copies back."""
+
+    _fields_ = [("live", C.c_void_p), ("saved", C.c_void_p), ("bytes", C.c_int64)]
+
+
+PSamKeep = C.POINTER(SamKeep)
+SAM_MAX_KEEP = 4  # include/dtc.h DTC_SAM_MAX_KEEP
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "dtc_abi_version": (i32, []),
@@ -138,6 +148,10 @@ _SIGS = {
     "dtc_grad_accum_flat": (i32, [vp, vp, i64, i32, vp]),
     "dtc_grad_compress_bf16": (i32, [vp, vp, vp, i64, vp]),
     "dtc_grad_decompress_bf16": (i32, [vp, vp, i64, vp]),
+    "dtc_sam_state_words": (i32, []),
+    "dtc_sam_workspace_bytes": (sz, [i64]),
+    "dtc_sam_perturb": (i32, [vp, vp, vp, vp, i64, f64, f64, i32, vp, PSamKeep, i32, vp, vp, vp]),
+    "dtc_sam_restore": (i32, [vp, vp, vp, i64, PSamKeep, i32, vp, vp, vp]),
     "dtc_cast_f32_bf16": (i32, [vp, vp, i64, vp]),
     "dtc_amp_scale": (i32, [vp, vp, vp, i64, vp]),
     "dtc_amp_check_finite": (i32, [vp, i64, vp, vp]),

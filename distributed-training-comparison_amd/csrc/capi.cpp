@@ -536,6 +536,21 @@ int dtc_grad_compress_bf16(const float* g, const float* acc, uint16_t* c, int64_
 int dtc_grad_decompress_bf16(const uint16_t* c, float* g, int64_t n, void* stream) {
   return grad_decompress_bf16(c, g, n, S(stream));
 }
+static_assert(sizeof(dtc_sam_keep) == sizeof(SamKeep) && offsetof(dtc_sam_keep, saved) == offsetof(SamKeep, saved) &&
+                  offsetof(dtc_sam_keep, bytes) == offsetof(SamKeep, bytes),
+              "dtc_sam_keep is SamKeep");
+int dtc_sam_state_words(void) { return DTC_SAM_STATE_WORDS; }
+size_t dtc_sam_workspace_bytes(int64_t n) { return sam_workspace_bytes(n); }
+int dtc_sam_perturb(float* p, const float* g, float* p_saved, uint16_t* pb, int64_t n, double rho, double eps,
+                    int adaptive, const float* gmul, const dtc_sam_keep* keep, int nkeep, void* state, void* workspace,
+                    void* stream) {
+  return sam_perturb(p, g, p_saved, pb, n, rho, eps, adaptive, gmul, (const SamKeep*)keep, nkeep, state, workspace,
+                     S(stream));
+}
+int dtc_sam_restore(float* p, const float* p_saved, uint16_t* pb, int64_t n, const dtc_sam_keep* keep, int nkeep,
+                    const void* state, int* found_inf, void* stream) {
+  return sam_restore(p, p_saved, pb, n, (const SamKeep*)keep, nkeep, state, found_inf, S(stream));
+}
 int dtc_cast_f32_bf16(const float* src, uint16_t* dst, int64_t n, void* stream) {
   return cast_f32_bf16(src, dst, n, S(stream));
 }

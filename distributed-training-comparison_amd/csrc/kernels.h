@@ -442,6 +442,27 @@ int grad_accum(float* acc, float* g, int64_t n, int mode, hipStream_t st);
 #define DTC_COMPRESS_MAX_BLOCKS 1024
 int grad_compress_bf16(const float* g, const float* acc, u16* c, int64_t n, hipStream_t st);
 int grad_decompress_bf16(const u16* c, float* g, int64_t n, hipStream_t st);
+// SAM / ASAM (sam.hip) over the whole flat buffer. perturb: p_saved = p, p += coef * g (adaptive: * p * p) with
+// coef = rho * m / (|m| * ||t|| + eps), t = g or p * g, m = *gmul, p_bf16 = bf16(p); a non-finite norm moves nothing
+// and marks `state` (DTC_SAM_STATE_WORDS 32-bit words, 16-byte aligned: fp32 coef, fp32 norm, int32 skipped) --
+// three launches (norm pass into sam_workspace_bytes(n) of slots, finalize, update). restore: p = p_saved, p_bf16 =
+// bf16(p), *found_inf = 1 if the perturb was skipped -- one launch. Up to the ABI's DTC_SAM_MAX_KEEP small ranges
+// are copied aside by the perturb and back by the restore as 8-byte words, inside those launches. The update and
+// restore kernels take chunks of DTC_SAM_THREADS * DTC_SAM_UNROLL float4 rows on a grid capped at DTC_SAM_MAX_BLOCKS.
+#define DTC_SAM_STATE_WORDS 4
+#define DTC_SAM_THREADS 256
+#define DTC_SAM_UNROLL 4
+#define DTC_SAM_MAX_BLOCKS 1024
+struct SamKeep {  // layout of the ABI's dtc_sam_keep
+  void* live;
+  void* saved;
+  int64_t bytes;
+};
+size_t sam_workspace_bytes(int64_t n);
+int sam_perturb(float* p, const float* g, float* p_saved, u16* p_bf16, int64_t n, double rho, double eps, int adaptive,
+                const float* gmul, const SamKeep* keep, int nkeep, void* state, void* workspace, hipStream_t st);
+int sam_restore(float* p, const float* p_saved, u16* p_bf16, int64_t n, const SamKeep* keep, int nkeep,
+                const void* state, int* found_inf, hipStream_t st);
 int cast_f32_bf16(const float* src, u16* dst, int64_t n, hipStream_t st);
 // zero an 8-byte aligned range (a kernel node, unlike hipMemsetAsync's fill dispatch)
 int zero_bytes(void* p, size_t bytes, hipStream_t st);

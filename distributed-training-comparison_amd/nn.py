@@ -781,6 +781,7 @@ class ResNet(nn.Module):
         self.grad_compression = None
         self._accum_depth = 0
         self._accum_open = False
+        self._local_depth = 0  # nesting depth of local_grads()
         self._bucket_cap_mb = float(bucket_cap_mb)
         self._capture = False
         self._sync_bn = False  # SyncBatchNorm.convert_sync_batchnorm marks the module
@@ -943,17 +944,41 @@ class ResNet(nn.Module):
         """Drop an open accumulation window: the next backward outside accumulate() is a plain one."""
         self._accum_open = False
 
+    @contextlib.contextmanager
+    def local_grads(self):
+        """Backwards inside this context write this rank's own gradients and nothing else: no communicator
+        (nothing is all-reduced or compressed, whatever wrapper the model is in) and accumulation mode OFF. It is
+        SAM's first backward (optim.SAM): under DistributedDataParallel every rank then perturbs along its own
+        un-reduced gradient. Refused while an accumulation window is open or with ``grad_accum_steps != 1`` -- the
+        local gradient would be neither the window's nor a whole step's. Outside the context nothing changes."""
+        self._check_local_grads()
+        self._local_depth += 1
+        try:
+            yield self
+        finally:
+            self._local_depth -= 1
+
+    def _check_local_grads(self) -> None:
+        if self._accum_open or self._accum_depth > 0:
+            raise NativeError("local_grads(): a gradient-accumulation window is open (accumulate() / no_sync())")
+        if self.grad_accum_steps != 1:
+            raise NativeError(f"local_grads() needs grad_accum_steps == 1, not {self.grad_accum_steps!r}")
+
     def _begin_backward(self, exe: Executor):
         """(grad_scale, comm) of the native backward about to run on `exe`, whose accumulation mode is set
         from the window's state: STORE / ADD without a communicator inside accumulate(), FINISH for the backward
-        that closes a window, OFF otherwise; its compression mode from `grad_compression`."""
+        that closes a window, OFF otherwise; its compression mode from `grad_compression`. Inside local_grads():
+        OFF and no communicator."""
         if self.grad_compression not in GRAD_COMPRESSIONS:
             raise ValueError(f"grad_compression must be one of {GRAD_COMPRESSIONS}, not {self.grad_compression!r}")
         steps = self.grad_accum_steps
         if not isinstance(steps, int) or steps < 1:
             raise ValueError(f"grad_accum_steps must be an integer >= 1, not {steps!r}")
         comm = self._comm
-        if self._accum_depth > 0:
+        if self._local_depth > 0:
+            self._check_local_grads()  # (an accumulate() entered inside the context)
+            mode, comm = ops.ACCUM_OFF, None
+        elif self._accum_depth > 0:
             mode, comm = (ops.ACCUM_ADD if self._accum_open else ops.ACCUM_STORE), None
         else:
             mode = ops.ACCUM_FINISH if self._accum_open else ops.ACCUM_OFF

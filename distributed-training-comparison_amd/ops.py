@@ -11,7 +11,8 @@ import ctypes as C
 
 import torch
 
-from ._native import SEG_ADAPT, ConvDesc, EmaRange, NativeError, Seg, call, lib, ptr, require_cuda, stream_ptr
+from ._native import (SAM_MAX_KEEP, SEG_ADAPT, ConvDesc, EmaRange, NativeError, SamKeep, Seg, call, lib, ptr,
+                      require_cuda, stream_ptr)
 
 
 
@@ -670,6 +671,65 @@ def grad_decompress_bf16(c, g):
     if g.dtype != torch.float32 or not g.is_contiguous() or c.numel() != g.numel():
         raise NativeError("grad_decompress_bf16: g must be a contiguous fp32 tensor of c's element count")
     call("dtc_grad_decompress_bf16", ptr(c), ptr(g), g.numel(), stream_ptr())
+
+
+def sam_state(device):
+    """The device record of one SAM optimizer (include/dtc.h: dtc_sam_perturb), int32 [4]: word 0 the fp32 coef,
+    word 1 the fp32 gradient norm of the last perturb, word 2 `skipped` (1: the norm was not finite and nothing
+    moved). Every perturb writes it whole."""
+    return torch.zeros(lib.dtc_sam_state_words(), dtype=torch.int32, device=device)
+
+
+def sam_workspace(n, device):
+    return torch.empty(max(1, lib.dtc_sam_workspace_bytes(int(n)) // 8), dtype=torch.float64, device=device)
+
+
+def _sam_keep(keep, who):
+    """The dtc_sam_keep table of (live, saved) tensor pairs: contiguous, one size in bytes, a multiple of 8."""
+    keep = list(keep or ())
+    if len(keep) > SAM_MAX_KEEP:
+        raise NativeError(f"{who}: at most {SAM_MAX_KEEP} keep ranges, got {len(keep)}")
+    table = (SamKeep * max(1, len(keep)))()
+    for k, (live, saved) in enumerate(keep):
+        require_cuda(live, saved)
+        nbytes = live.numel() * live.element_size()
+        if not (live.is_contiguous() and saved.is_contiguous()) or saved.numel() * saved.element_size() != nbytes:
+            raise NativeError(f"{who}: keep {k}: live and saved must be contiguous tensors of one size in bytes")
+        table[k] = SamKeep(ptr(live), ptr(saved), nbytes)
+    return table, len(keep)
+
+
+def _sam_check(who, p, p_saved, pb, g=None):
+    require_cuda(p, p_saved, pb, g)
+    fp32 = [t for t in (p, p_saved, g) if t is not None]
+    if any(t.dtype != torch.float32 for t in fp32) or pb.dtype != torch.bfloat16:
+        raise NativeError(f"{who}: p, g and p_saved must be fp32 tensors, p_bf16 a bf16 tensor")
+    if any(t.numel() != p.numel() or not t.is_contiguous() for t in fp32 + [pb]):
+        raise NativeError(f"{who}: p, g, p_saved and p_bf16 must be contiguous tensors of one size")
+
+
+def sam_perturb(p, g, p_saved, pb, state, rho, adaptive=False, eps=1e-12, gmul=None, keep=None, workspace=None):
+    """The SAM / ASAM ascent step over flat fp32 buffers (include/dtc.h: dtc_sam_perturb): p_saved = p, then
+    p += coef * g (adaptive: * p * p) with coef = rho * m / (|m| * ||g|| + eps) (adaptive: ||p * g||), m = *gmul, and
+    the bf16 shadow `pb` refreshed; a non-finite norm moves nothing and sets state's `skipped`. `keep`: up to 4
+    (live, saved) pairs of small tensors copied live -> saved in the same launches. `state` from sam_state()."""
+    _sam_check("sam_perturb", p, p_saved, pb, g)
+    if workspace is None:
+        workspace = sam_workspace(p.numel(), p.device)
+    require_cuda(state, gmul, workspace)
+    table, nkeep = _sam_keep(keep, "sam_perturb")
+    call("dtc_sam_perturb", ptr(p), ptr(g), ptr(p_saved), ptr(pb), p.numel(), float(rho), float(eps),
+         int(bool(adaptive)), ptr(gmul), table, nkeep, ptr(state), ptr(workspace), stream_ptr())
+
+
+def sam_restore(p, p_saved, pb, state, keep=None, found_inf=None):
+    """The way back (dtc_sam_restore), one launch: p = p_saved bit for bit, pb = bf16(p), every keep pair copied
+    saved -> live, and *found_inf = 1 (an int32 device word, never cleared here) if the perturb was skipped."""
+    _sam_check("sam_restore", p, p_saved, pb)
+    require_cuda(state, found_inf)
+    table, nkeep = _sam_keep(keep, "sam_restore")
+    call("dtc_sam_restore", ptr(p), ptr(p_saved), ptr(pb), p.numel(), table, nkeep, ptr(state), ptr(found_inf),
+         stream_ptr())
 
 
 def cast_f32_bf16(src, dst):

@@ -1,4 +1,4 @@
-"""optim.SGD / Adam / AdamW mirrors and LARS running fused flat-buffer kernels, and clip_grad_norm_.
+"""optim.SGD / Adam / AdamW mirrors, LARS and the SAM wrapper running fused flat-buffer kernels, and clip_grad_norm_.
 
 Reference: ``optim.SGD(self.model.parameters(), lr, weight_decay, momentum=0.9, nesterov=True)``
 (src/ddp/trainer.py:92-98) stepped through ``GradScaler.step`` (trainer.py:158); the reference's README
@@ -187,6 +187,102 @@ class LARS(_FlatOptimizer):
         if self._plan is None:
             raise NativeError("LARS.layer_norms: no step has run yet")
         return self._norms, self._plan.names
+
+
+class SAM(Optimizer):
+    """Sharpness-aware minimisation (Foret et al. 2021; ``adaptive=True``: ASAM, Kwon et al. 2021, typical rho 0.5
+    to 2.0) around one of the fused optimizers above. One optimizer step is two passes over the same batch:
+
+        loss = criterion(model(x), y)                 # at w: the loss worth logging
+        with model.local_grads():                     # this rank's own gradient: not reduced, not accumulated
+            loss.backward()
+        optimizer.first_step(scaler)                  # w <- w + e(w): three launches (include/dtc.h dtc_sam_perturb)
+        criterion(model(x), y).backward()             # the gradient at w + e, all-reduced as ever
+        optimizer.step()                              # w restored bit for bit (one launch), then the base's step
+
+    (under AMP the two backwards run on ``scaler.scale(loss)`` and the last line is ``scaler.step(optimizer)``).
+    ``param_groups`` IS the base optimizer's list, so LR schedulers built on either drive the same ``lr``; ``_flat``,
+    ``attach``, ``_find_flat`` and ``zero_grad`` are the base's, so ``GradScaler.unscale_ / step`` and
+    ``clip_grad_norm_`` take the wrapper unchanged. The BatchNorm running statistics and batch counts the second
+    forward updates again are put back by the restore: one SAM step moves them as one plain step does.
+
+    A first gradient that is not finite moves nothing. With a scaler the restore raises its ``found_inf`` word on
+    the device, so the step is skipped and ``update()`` backs the scale off; without one the step is the plain step
+    at the unperturbed weights. ``rho = 0`` is legal: the perturbation is then zero."""
+
+    def __init__(self, base_optimizer, rho=0.05, adaptive=False, eps=1e-12):
+        if not isinstance(base_optimizer, _FlatOptimizer):
+            raise TypeError("SAM wraps one of this package's fused optimizers (SGD, Adam, AdamW, LARS), not "
+                            f"{type(base_optimizer).__name__}")
+        if not 0.0 <= rho:
+            raise ValueError(f"Invalid rho value: {rho}")
+        if not 0.0 < eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        self.base = base_optimizer
+        self.rho, self.adaptive, self.eps = float(rho), bool(adaptive), float(eps)
+        super().__init__(base_optimizer.param_groups[0]["params"], dict(base_optimizer.defaults))
+        self.param_groups = base_optimizer.param_groups  # shared, not copied: one lr for schedulers to drive
+        self._perturbed = False
+        self._saved = None  # (flat, p_saved, bufs_saved, nbt_saved), allocated by the first first_step()
+        self._state = self._ws = None
+
+    @property
+    def _flat(self):
+        return self.base._flat
+
+    def attach(self, model):
+        self.base.attach(model)
+
+    def _find_flat(self):
+        return self.base._find_flat()
+
+    def zero_grad(self, set_to_none: bool = True):
+        return self.base.zero_grad(set_to_none)
+
+    def _keep(self, flat):
+        _, _, bufs_saved, nbt_saved = self._saved
+        return [(flat.bufs, bufs_saved), (flat.nbt, nbt_saved)]
+
+    @property
+    def grad_norm(self) -> torch.Tensor:
+        """The L2 norm of the last first_step()'s gradient (unscaled; ASAM: of p * g) as a 0-dim fp32 view of the
+        device record: no synchronisation, overwritten by the next first_step() (clone to keep)."""
+        if self._state is None:
+            raise NativeError("SAM.grad_norm: no first_step() has run yet")
+        return self._state.view(torch.float32)[1]
+
+    @torch.no_grad()
+    def first_step(self, scaler=None):
+        """After the first backward: save the weights and the BatchNorm running state, move to w + e(w)."""
+        if self._perturbed:
+            raise NativeError("SAM.first_step: the weights are already perturbed (step() must follow first_step())")
+        if self.base._flat is None:
+            self.base.attach(self.base._find_flat())
+        flat = self.base._flat
+        if self._saved is None or self._saved[0] is not flat:
+            self._saved = (flat, torch.empty_like(flat.params), torch.empty_like(flat.bufs),
+                           torch.empty_like(flat.nbt))
+            self._state = ops.sam_state(flat.device)
+            self._ws = ops.sam_workspace(flat.params.numel(), flat.device)
+        gmul = None
+        if scaler is not None and scaler.is_enabled():
+            scaler._lazy_init(flat.device)
+            gmul = scaler._inv_scale
+        ops.sam_perturb(flat.params, flat.grads, self._saved[1], flat.params_bf16, self._state, self.rho,
+                        self.adaptive, self.eps, gmul, self._keep(flat), self._ws)
+        self._perturbed = True
+
+    @torch.no_grad()
+    def step(self, closure=None, inv_scale=None, found_inf=None):
+        if closure is not None:
+            raise NotImplementedError("closures are not used: run the two passes and first_step() explicitly")
+        if not self._perturbed:
+            raise NativeError("SAM.step: no first_step() since the last step (the two-pass loop: backward inside "
+                              "model.local_grads(), first_step(), a second forward / backward, step())")
+        flat = self.base._flat
+        ops.sam_restore(flat.params, self._saved[1], flat.params_bf16, self._state, self._keep(flat), found_inf)
+        self._perturbed = False
+        return self.base.step(inv_scale=inv_scale, found_inf=found_inf)
 
 
 def clip_grad_norm_(parameters, max_norm, norm_type=2.0, scaler=None) -> torch.Tensor:

@@ -23,7 +23,7 @@ from . import data as D
 from .amp import GradScaler, autocast
 from .ema import ModelEma
 from .nn import CrossEntropyLoss, ResNet18, SyncBatchNorm
-from .optim import LARS, SGD, Adam, AdamW, clip_grad_norm_
+from .optim import LARS, SAM, SGD, Adam, AdamW, clip_grad_norm_
 from .parallel import DDP, DataParallel, barrier, bf16_compress_hook
 
 
@@ -91,6 +91,13 @@ def load_config(argv=None, mode: str = "ddp"):
                    help="gradient accumulation: one optimizer step per N loader iterations, on the mean gradient of "
                         "their N micro-batches (ddp: one all-reduce per N backwards, DDP.no_sync()). The last "
                         "iteration of an epoch closes a shorter window, still divided by N (single and ddp only)")
+    # not in the reference: sharpness-aware minimisation (Foret et al. 2021) around whichever --optimizer
+    p.add_argument("--sam-rho", type=float, default=0.0,
+                   help="SAM: every optimizer step takes its gradient at the worst point of the rho-ball around the "
+                        "weights, found along this rank's own gradient (two forward / backward passes per step; "
+                        "0 = off; typical 0.05; single and ddp only, not with --accum-steps > 1)")
+    p.add_argument("--sam-adaptive", action="store_true", default=False,
+                   help="--sam-rho: ASAM (Kwon et al. 2021), the ball scaled per weight by |w|; typical rho 0.5 to 2.0")
     # synthetic-data size knobs (not in the reference: CIFAR-100 cannot be downloaded here)
     p.add_argument("--synthetic-train", type=int, default=50000)
     p.add_argument("--synthetic-test", type=int, default=10000)
@@ -118,6 +125,12 @@ def load_config(argv=None, mode: str = "ddp"):
         p.error("--accum-steps must be >= 1")
     if mode == "dp" and h.accum_steps > 1:
         p.error("--accum-steps > 1 is not available under DataParallel (single and ddp only)")
+    if not h.sam_rho >= 0.0:
+        p.error("--sam-rho must be >= 0")
+    if h.sam_rho > 0 and h.accum_steps > 1:
+        p.error("--sam-rho is not available with --accum-steps > 1 (its first backward is a whole step's gradient)")
+    if h.sam_rho > 0 and mode == "dp":
+        p.error("--sam-rho is not available under DataParallel (single and ddp only)")
     return h
 
 
@@ -213,6 +226,7 @@ class Trainer:
         # optimizer steps taken (--accum-steps N: one per window of N loader iterations; N = 1: == global_step)
         self.optimizer_step = 0
         self.accum_steps = int(getattr(hparams, "accum_steps", 1))
+        self.sam = isinstance(self.optimizer, SAM)
         if self.accum_steps > 1:
             self._module_for_eval().grad_accum_steps = self.accum_steps
         self.global_top1_acc = 0.0
@@ -271,6 +285,8 @@ class Trainer:
         else:
             cls = {"adam": Adam, "adamw": AdamW}[h.optimizer]
             optimizer = cls(self.model.parameters(), lr=h.lr, weight_decay=h.weight_decay)
+        if getattr(h, "sam_rho", 0.0) > 0:  # shares param_groups with the base: the schedule drives the base's lr
+            optimizer = SAM(optimizer, rho=h.sam_rho, adaptive=getattr(h, "sam_adaptive", False))
         return optimizer, make_scheduler(optimizer, h)
 
     def save_checkpoint(self, epoch: int, val_acc: float, model) -> None:
@@ -306,6 +322,41 @@ class Trainer:
             with (self.model.no_sync() if self.distributed else self.model.accumulate()):
                 loss.backward()
 
+    def _loss(self, img, label):
+        if self.hparams.amp:
+            with autocast():
+                return self.criterion(self.model(img), label)
+        return self.criterion(self.model(img), label)
+
+    def _sam_step(self, img, label):
+        """One optimizer step with --sam-rho: the loss at w (returned: the one that is logged) and its backward
+        inside local_grads() -- this rank's own gradient, nothing all-reduced --, first_step() to w + e, then the
+        same (already mixed) batch and target again: loss at w + e, the per-step barrier (still one per optimizer
+        step), the all-reduced backward and the unscale_ / clip / step / EMA / update sequence of the plain step.
+        The optimizer's step() first restores w and the BatchNorm running state of the first forward."""
+        amp, scaler = self.hparams.amp, self.scaler
+        loss = self._loss(img, label)
+        with self._module_for_eval().local_grads():
+            (scaler.scale(loss) if amp else loss).backward()
+        self.optimizer.first_step(scaler if amp else None)
+        loss2 = self._loss(img, label)
+        if self.distributed:
+            barrier()
+        (scaler.scale(loss2) if amp else loss2).backward()
+        if amp:
+            if self.hparams.clip_grad_norm > 0:
+                scaler.unscale_(self.optimizer)
+                clip_grad_norm_(self.model.parameters(), self.hparams.clip_grad_norm, scaler=scaler)
+            scaler.step(self.optimizer)
+            self._ema_update(scaler.found_inf)
+            scaler.update()
+        else:
+            if self.hparams.clip_grad_norm > 0:
+                clip_grad_norm_(self.model.parameters(), self.hparams.clip_grad_norm)
+            self.optimizer.step()
+            self._ema_update(None)
+        return loss
+
     def _train_epoch(self, epoch: int) -> dict:
         """One epoch of the reference's step. --accum-steps N > 1: backwards 1..N-1 of a window of N loader
         iterations accumulate; the N-th closes the window and is followed by the unscale_ / clip / step / EMA /
@@ -326,7 +377,9 @@ class Trainer:
             img = img.to(self.device, non_blocking=True)
             label = label.to(self.device, non_blocking=True)
             self.optimizer.zero_grad()
-            if self.hparams.amp:
+            if self.sam:
+                loss = self._sam_step(img, label)
+            elif self.hparams.amp:
                 with autocast():
                     logit = self.model(img)
                     loss = self.criterion(logit, label)

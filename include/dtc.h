@@ -368,6 +368,40 @@ int dtc_grad_accum_flat(float* acc, float* g, int64_t n, int mode, void* stream)
  * g and acc 16-byte aligned, c 8-byte aligned; [c, c + n) overlapping neither [g, g + n) nor [acc, acc + n). */
 int dtc_grad_compress_bf16(const float* g, const float* acc, uint16_t* c, int64_t n, void* stream);
 int dtc_grad_decompress_bf16(const uint16_t* c, float* g, int64_t n, void* stream);
+/* sam: sharpness-aware minimisation (SAM, Foret et al. 2021) and its scale-adaptive form (ASAM, Kwon et al. 2021)
+ * over the whole flat buffers (n a positive multiple of 4; alignment padding holds zeros in p and g and so is not
+ * moved). dtc_sam_perturb, after the first backward, with m = *gmul (NULL: 1; GradScaler's 1 / scale):
+ *   t_i  = g_i (adaptive == 0)  |  p_i * g_i (adaptive != 0)
+ *   S    = sum t_i^2 in double, in dtc_grad_norm_clip's fixed order;  gn = |m| * sqrt(S)
+ *   ok   = isfinite(S) && isfinite(m);  coef = ok ? (float)(rho * m / (gn + eps)) : 0   (double, rounded once)
+ *   state = {float coef; float norm = (float)gn; int32 skipped = !ok; int32 reserved}
+ *   every element:  p_saved_i = p_i
+ *   ok:   p_i = p_i + coef * g_i  |  p_i + (coef * g_i) * (p_i * p_i), each operation one IEEE fp32 rounding (no
+ *         FMA); an element whose increment is zero keeps its bits;  p_bf16_i = bf16(p_i) (dtc_cast_f32_bf16's rounding)
+ *   !ok:  p and p_bf16 stay bit-unchanged (g is not multiplied in: 0 * NaN is NaN)
+ *   keep[k]: saved <- live, raw 8-byte words (BatchNorm running statistics and batch counts across the second forward)
+ * dtc_sam_restore, after the second backward and ahead of the optimizer step: p_i = p_saved_i and p_bf16_i =
+ * bf16(p_i) for every element -- a copy, never a subtraction, so the weights return bit for bit; keep[k]: live <-
+ * saved; and *found_inf = 1 if found_inf != NULL and state.skipped (the word is never cleared here): GradScaler then
+ * skips the step and backs the scale off, with no host synchronisation.
+ * `state`: dtc_sam_state_words() (= 4) 32-bit words of device memory, 16-byte aligned, written by every perturb.
+ * `workspace`: dtc_sam_workspace_bytes(n) bytes, 8-byte aligned, overwritten. Launches: perturb three (the norm pass,
+ * which does not read p unless adaptive and carries the keep copies; a one-workgroup finalize; the update), restore
+ * one. HBM traffic per element: norm 4 bytes (adaptive 8), update 18, restore 10. 16-byte loads and stores, no
+ * floating-point atomics, every element written by exactly one thread: bit-identical from run to run. Requires (else
+ * DTC_EINVAL, before any device call): non-NULL p, g, p_saved, p_bf16, state, workspace; n a positive multiple of 4;
+ * p, g, p_saved 16-byte and p_bf16 8-byte aligned; [p_saved, p_saved + n) overlapping neither p nor g; rho >= 0,
+ * eps > 0; 0 <= nkeep <= DTC_SAM_MAX_KEEP, every keep record with non-NULL 8-byte aligned live and saved, bytes a
+ * positive multiple of 8, and no range of the table overlapping another. */
+#define DTC_SAM_MAX_KEEP 4
+typedef struct { void* live; void* saved; int64_t bytes; } dtc_sam_keep;
+int dtc_sam_state_words(void);
+size_t dtc_sam_workspace_bytes(int64_t n);
+int dtc_sam_perturb(float* p, const float* g, float* p_saved, uint16_t* p_bf16, int64_t n, double rho, double eps,
+                    int adaptive, const float* gmul, const dtc_sam_keep* keep, int nkeep, void* state, void* workspace,
+                    void* stream);
+int dtc_sam_restore(float* p, const float* p_saved, uint16_t* p_bf16, int64_t n, const dtc_sam_keep* keep, int nkeep,
+                    const void* state, int* found_inf, void* stream);
 int dtc_cast_f32_bf16(const float* src, uint16_t* dst, int64_t n, void* stream);
 int dtc_amp_check_finite(const float* g, int64_t n, int* found_inf, void* stream);
 /* GradScaler.scale(loss): out = x * (*scale) with the scale device-resident (no host sync) */
