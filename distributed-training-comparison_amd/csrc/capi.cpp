@@ -208,7 +208,7 @@ int dtc_install_crash_handler(void) {
 
 size_t dtc_conv2d_workspace_size(const dtc_conv_desc* d, int pass) {
   if (!desc_ok(d) || pass < 0 || pass > 2) return 0;
-  const size_t slab = plan_conv(shape_of(d), pass).slab_bytes;
+  const size_t slab = conv_route(shape_of(d), pass).slab_bytes;
   // FWD / DGRAD split-K: + the arrival counters of the in-kernel reduction at the workspace's end (+ room to
   // align them to 256 B, so a workspace of exactly this size always holds both)
   return slab > 0 && pass != 2 ? slab + (size_t)DTC_TICKS * 4 + 256 : slab;
@@ -218,17 +218,14 @@ size_t dtc_conv2d_workspace_size(const dtc_conv_desc* d, int pass) {
 // the in-kernel reduction are zeroed on the call's stream first; the workspace is scratch between calls),
 // else the whole of it is slab and a split-K plan reduces in a separate launch. Nothing is carved out (and
 // nothing zeroed) when the plan has no slab or the in-kernel reduction is off (option splitk_ink).
-static unsigned* ws_ticks(size_t slab, void* ws, size_t& ws_bytes, hipStream_t st) {
-  const size_t tb = (size_t)DTC_TICKS * 4;
+static unsigned* op_ticks(const dtc_conv_desc* d, int pass, void* ws, size_t& ws_bytes, hipStream_t st) {
+  const size_t tb = (size_t)DTC_TICKS * 4, slab = conv_route(shape_of(d), pass).slab_bytes;
   if (ws == nullptr || slab == 0 || ws_bytes < slab + tb || option_get(OPT_SPLITK_INK) == 0) return nullptr;
   const uintptr_t end = ((uintptr_t)ws + ws_bytes - tb) & ~(uintptr_t)255;
   if (end < (uintptr_t)ws + slab) return nullptr;
   if (hipMemsetAsync((void*)end, 0, tb, st) != hipSuccess) return nullptr;
   ws_bytes = end - (uintptr_t)ws;
   return (unsigned*)end;
-}
-static unsigned* op_ticks(const dtc_conv_desc* d, int pass, void* ws, size_t& ws_bytes, hipStream_t st) {
-  return ws_ticks(plan_conv(shape_of(d), pass).slab_bytes, ws, ws_bytes, st);
 }
 
 int dtc_conv2d_fwd(const dtc_conv_desc* d, const uint16_t* x, const uint16_t* w, uint16_t* y, int64_t* stats, void* ws,
@@ -245,7 +242,6 @@ int dtc_conv2d_fwd_sc(const dtc_conv_desc* d, const uint16_t* x, const uint16_t*
   DTC_CHECK_ARG(desc_ok(d), "dtc_conv2d_fwd_sc: unsupported convolution descriptor");
   const ConvShape s = shape_of(d);
   const ConvShape sc{s.N, s.H, s.W, s.C, s.K, 1, 1, 2, 0};
-  DTC_CHECK_ARG(conv_fwd_sc_ok(s, sc), "dtc_conv2d_fwd_sc: no fused plan for this geometry");
   GUARD(return conv_fwd_sc(s, sc, x, w, y, stats, wsc, ysc, stats_sc, S(stream));)
 }
 
@@ -254,10 +250,10 @@ int dtc_conv2d_dgrad(const dtc_conv_desc* d, const uint16_t* dy, const uint16_t*
   DTC_CHECK_ARG(d && dy && w && dx, "dtc_conv2d_dgrad: null argument");
   DTC_CHECK_ARG(desc_ok(d), "dtc_conv2d_dgrad: unsupported convolution descriptor");
   unsigned* tick = op_ticks(d, CONV_DGRAD, ws, ws_bytes, S(stream));
-  GUARD(return conv_dgrad(shape_of(d), dy, w, dx, res, (float*)ws, ws ? ws_bytes : 0, S(stream), nullptr, nullptr, 0,
-                          tick);)
+  GUARD(return conv_dgrad(shape_of(d), dy, w, dx, res, (float*)ws, ws ? ws_bytes : 0, S(stream), nullptr, 0, tick);)
 }
 
+// the data gradient, then the BN-backward reduction of the post-ReLU BN output it is the gradient of, in place on dx
 int dtc_conv2d_dgrad_bn(const dtc_conv_desc* d, const uint16_t* dy, const uint16_t* w, uint16_t* dx,
                         const uint16_t* res, const uint16_t* ymask, const uint16_t* x1, const float* mean1,
                         const float* invstd1, int64_t* acc1, const uint16_t* x2, const float* mean2,
@@ -265,19 +261,17 @@ int dtc_conv2d_dgrad_bn(const dtc_conv_desc* d, const uint16_t* dy, const uint16
   DTC_CHECK_ARG(d && dy && w && dx && ymask && x1 && mean1 && invstd1 && acc1, "dtc_conv2d_dgrad_bn: null argument");
   DTC_CHECK_ARG(desc_ok(d), "dtc_conv2d_dgrad_bn: unsupported convolution descriptor");
   DTC_CHECK_ARG(!x2 || (mean2 && invstd2 && acc2), "dtc_conv2d_dgrad_bn: second BN arguments");
-  BnbArgs a;
-  a.ym = ymask; a.x1 = x1; a.mean1 = mean1; a.invstd1 = invstd1; a.acc1 = acc1;
-  a.x2 = x2; a.mean2 = mean2; a.invstd2 = invstd2; a.acc2 = acc2;
+  const ConvShape s = shape_of(d);
   unsigned* tick = op_ticks(d, CONV_DGRAD, ws, ws_bytes, S(stream));
-  GUARD(return conv_dgrad(shape_of(d), dy, w, dx, res, (float*)ws, ws ? ws_bytes : 0, S(stream), nullptr, &a, 0,
-                          tick);)
+  GUARD(DTC_TRY(conv_dgrad(s, dy, w, dx, res, (float*)ws, ws ? ws_bytes : 0, S(stream), nullptr, 0, tick));
+        return bn_bwd_reduce(dx, ymask, x1, mean1, invstd1, acc1, x2, mean2, invstd2, acc2, dx, (int64_t)s.N * s.H * s.W,
+                             s.C, S(stream));)
 }
 
 int dtc_conv2d_dgrad_sc(const dtc_conv_desc* d, const uint16_t* dy, const uint16_t* w, uint16_t* dx,
                         const uint16_t* dsc, const uint16_t* wsc, void* stream) {
   DTC_CHECK_ARG(d && dy && w && dx && dsc && wsc, "dtc_conv2d_dgrad_sc: null argument");
   DTC_CHECK_ARG(desc_ok(d), "dtc_conv2d_dgrad_sc: unsupported convolution descriptor");
-  DTC_CHECK_ARG(conv_dgrad_sc_ok(shape_of(d)), "dtc_conv2d_dgrad_sc: no fused plan for this geometry");
   GUARD(return conv_dgrad_sc(shape_of(d), dy, w, dx, dsc, wsc, S(stream));)
 }
 
@@ -290,21 +284,26 @@ int dtc_conv2d_wgrad(const dtc_conv_desc* d, const uint16_t* x, const uint16_t* 
 
 size_t dtc_conv2d_wgrad_sc_workspace_size(const dtc_conv_desc* d) {
   if (!desc_ok(d)) return 0;
-  const ConvShape s = shape_of(d);
-  return wgrad_s2_splits(s) > 0 ? conv_wgrad_s2_slab_bytes(s) + (size_t)DTC_TICKS * 4 : 0;
+  const ConvRoute r = conv_route(shape_of(d), CONV_WGRAD);
+  return r.sc_ok ? r.slab_bytes + (size_t)DTC_TICKS * 4 : 0;
 }
 
 int dtc_conv2d_wgrad_sc(const dtc_conv_desc* d, const uint16_t* x, const uint16_t* dy, const uint16_t* dsc, float* dw,
                         float* dw_sc, float scale, void* ws, size_t ws_bytes, void* stream) {
   DTC_CHECK_ARG(d && x && dy && dsc && dw && dw_sc, "dtc_conv2d_wgrad_sc: null argument");
   DTC_CHECK_ARG(desc_ok(d), "dtc_conv2d_wgrad_sc: unsupported convolution descriptor");
-  GUARD(return conv_wgrad_s2(shape_of(d), x, dy, dsc, dw, dw_sc, scale, (float*)ws, ws ? ws_bytes : 0, S(stream));)
+  const ConvShape s = shape_of(d);
+  const ConvRoute r = conv_route(s, CONV_WGRAD);  // (the launch checks the slab it really needs)
+  DTC_CHECK_ARG(r.sc_ok, "dtc_conv2d_wgrad_sc: no fused plan for this geometry");
+  GUARD(return conv_wgrad_s2(s, r.splits, x, dy, dsc, dw, dw_sc, scale, (float*)ws, ws ? ws_bytes : 0, S(stream));)
 }
 
 size_t dtc_conv2d_wgrad_batch_workspace_size(const dtc_conv_desc* d, int n) {
   if (!desc_ok(d) || n < 1 || n > DTC_WG_BATCH) return 0;
-  const ConvShape s = shape_of(d);
-  return wgrad_halo_splits(s, n) > 0 ? conv_wgrad_batch_slab_bytes(s, n) : 0;
+  ConvRequest rq;
+  rq.nprob = n;
+  const ConvRoute r = conv_route(shape_of(d), CONV_WGRAD, rq);
+  return r.kernel == CONV_K_WGRAD_HALO ? r.slab_bytes : 0;
 }
 
 int dtc_conv2d_wgrad_batch(const dtc_conv_desc* d, int n, const uint16_t* const* x, const uint16_t* const* dy,

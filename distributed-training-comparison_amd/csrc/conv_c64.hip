@@ -29,8 +29,6 @@
 
 namespace dtc {
 
-__device__ __forceinline__ int c64_hswz(int r) { return ((r >> 1) & 3) << 1; }
-
 struct C64Params {
   const u16* src;  // FWD: x, DGRAD: dy (NHWC, 64 channels)
   const u16* w;    // KRSC [64][3][3][64]
@@ -147,7 +145,7 @@ __global__ void __launch_bounds__(256, 1) conv_c64_kernel(const C64Params p) {
     for (int t = 0; t < 9; ++t) {
       const int row = hbr + (t / 3) * W2 + (t % 3);
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) boff[t][ks][j] = row * 128 + (((ks * 4 + (lane >> 4)) ^ c64_hswz(row)) << 4);
+      for (int ks = 0; ks < 2; ++ks) boff[t][ks][j] = row * 128 + (((ks * 4 + (lane >> 4)) ^ hswz(row)) << 4);
     }
   }
   // ---- halo DMA: tile-invariant per-lane parts (row decomposition, x range, swizzled channel chunk)
@@ -164,11 +162,11 @@ __global__ void __launch_bounds__(256, 1) conv_c64_kernel(const C64Params p) {
     if constexpr (GEN) {  // box row hy, column hx: byte offset from the box corner (row y0 - 1, column q0 - 1)
       hok[q] = g < C64_HCAP / 8 && hr < p.nh;
       hxx[q] = hx - 1;
-      hrel[q] = ((hy * p.W + hx) * 64 + (pc ^ c64_hswz(hr)) * 8) * 2;
+      hrel[q] = ((hy * p.W + hx) * 64 + (pc ^ hswz(hr)) * 8) * 2;
     } else {
       hok[q] = g < C64_HCAP / 8 && hr < p.nh && (unsigned)(hx - 1) < (unsigned)p.W;
       hxx[q] = 0;
-      hrel[q] = (((i * p.H + hy - 1) * p.W + hx - 1) * 64 + (pc ^ c64_hswz(hr)) * 8) * 2;
+      hrel[q] = (((i * p.H + hy - 1) * p.W + hx - 1) * 64 + (pc ^ hswz(hr)) * 8) * 2;
     }
   }
   auto stage_halo = [&](char* dst, int tile) {
@@ -424,7 +422,7 @@ static bool c64_classic_ok(const ConvShape& s);
 // GEN geometry: 8 rows x 32-column segments (rows whose width does not divide 256, or tensors past 2 GB)
 static bool c64_gen_ok(const ConvShape& s) {
   if (option_get(OPT_C64_GEN) == 0) return false;
-  if (!(s.R == 3 && s.S == 3 && s.stride == 1 && s.pad == 1 && s.C == 64 && s.K == 64)) return false;
+  if (!(conv3x3_ok(s, 1) && s.C == 64 && s.K == 64)) return false;
   if (s.W % C64_SEG != 0 || s.H % C64_GROWS != 0) return false;
   const int64_t M = (int64_t)s.N * s.H * s.W;
   return M / 256 < (1ll << 31) && M < (1ll << 31) && (int64_t)C64_GROWS * s.W * 128 < (1ll << 31);
@@ -440,7 +438,7 @@ bool conv_c64_ok(const ConvShape& s) {
   return c64_classic_ok(s) || c64_gen_ok(s);
 }
 static bool c64_classic_ok(const ConvShape& s) {
-  if (!(s.R == 3 && s.S == 3 && s.stride == 1 && s.pad == 1 && s.C == 64 && s.K == 64)) return false;
+  if (!(conv3x3_ok(s, 1) && s.C == 64 && s.K == 64)) return false;
   if (s.W < 16 || 256 % s.W != 0) return false;  // fragments of 16 contiguous pixels in one image row
   const int hw = s.H * s.W;
   int rows, imgs;
@@ -460,13 +458,13 @@ static bool c64_classic_ok(const ConvShape& s) {
 
 int conv_c64(const ConvShape& s, int mode, const u16* src, const u16* w, u16* out, const u16* res, int64_t* stats,
              hipStream_t st, u64* ts) {
-  DTC_CHECK_ARG(conv_c64_ok(s) && (mode == CONV_FWD || mode == CONV_DGRAD), "conv_c64: unsupported shape");
+  const bool gen = !c64_classic_ok(s);  // (whether to use the kernel at all is conv_route's question, not asked again)
+  DTC_CHECK_ARG((!gen || c64_gen_ok(s)) && (mode == CONV_FWD || mode == CONV_DGRAD), "conv_c64: unsupported shape");
   C64Params p{};
   p.src = src; p.w = w; p.out = out; p.res = res; p.stats = stats;
   p.N = s.N; p.H = s.H; p.W = s.W;
   const int64_t hw = (int64_t)s.H * s.W;
   const int64_t M = s.N * hw;
-  const bool gen = !c64_classic_ok(s);
   const int lw = gen ? C64_SEG : s.W;  // the LDS tile width
   if (gen) {
     p.rows = C64_GROWS;

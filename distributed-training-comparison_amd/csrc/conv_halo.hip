@@ -29,13 +29,6 @@
 
 namespace dtc {
 
-// Halo LDS swizzle: 16-B chunk c of halo row r is stored at chunk c ^ hswz(r). Every 8 B-fragment
-// lanes that share a reduction chunk read 8 halo rows that are distinct mod 8 (the per-lane pixel
-// order below guarantees it for W = 4 and 8 too), so (row parity, chunk ^ hswz) spreads them over
-// 8 different 16-B bank slots, and the chunk pair (q, q+1) read by one ds_read_b128 lane group
-// lands on even / odd slots: conflict-free for EVERY tap shift (rowswz is only for aligned rows).
-__device__ __forceinline__ int hswz(int r) { return ((r >> 1) & 3) << 1; }
-
 // Pixel of B-fragment column j (0..15) within its 16-pixel block. ds_read_b128 serves lanes in
 // groups {0-3,12-15,20-27}, ...: columns {4..11} and {0..3,12..15} must each map to halo rows
 // distinct mod 8. Contiguous image rows (W >= 16) satisfy it as is; for W = 8 (halo pitch 10) the
@@ -658,7 +651,7 @@ __global__ void __launch_bounds__(256, 2) conv_halo_kernel(const HConvParams p) 
 struct HaloCfg {
   int bm, bn, nhb, hcap, st;
 };
-// Template instances (launch_halo below). LDS: NHB * HCAP * 128 + WS * BM * 128 (+ BM * 128 with SC).
+// Template instances (launch_halo_ws below). LDS: NHB * HCAP * 128 + WS * BM * 128 (+ BM * 128 with SC).
 static const HaloCfg kHaloCfgs[] = {
     {64, 256, 1, 416, 1},   // 0: 70 KB, 2 WG/CU: big images / many tiles
     {64, 128, 2, 288, 1},   // 1: 90 KB: double-buffered halo, no chunk bubbles
@@ -679,7 +672,6 @@ constexpr int kFirstS2Cfg = 8;
 // Halo row pitch of the column-split stride-2 layout: 2 (Wo + 1) input columns, +2 where a 16-pixel
 // fragment spans output rows of width Wo = 8 mod 16 (the +1-output-row offset 2 * pitch must be 8 mod
 // 16 rows there for the ds_read_b128 lane groups to hit distinct bank slots; tools/halo_banks.py).
-static int s2_pitch(int wo) { return 2 * (wo + 1) + ((wo % 16) == 8 ? 2 : 0); }
 
 // Output tile geometry: `rows` output rows of one image slice or `imgs` whole images per tile, the
 // halo rows per slice (hb) and per tile (nh), the halo row pitch and (stride 2) the split point hwh.
@@ -714,7 +706,7 @@ static bool halo_geometry(const ConvShape& s, int st, int bn, int hcap, HaloGeom
 }
 
 static bool halo_shape_ok(const ConvShape& s, int st) {
-  if (!(s.R == 3 && s.S == 3 && s.stride == st && s.pad == 1 && s.C % 64 == 0 && s.K % 64 == 0)) return false;
+  if (!conv3x3_ok(s, st)) return false;
   if (st == 2 && (s.H % 2 || s.W % 2)) return false;
   return (uint64_t)s.N * s.H * s.W * std::max(s.C, s.K) * 2 < (1ull << 31);
 }
@@ -731,8 +723,8 @@ struct HaloGen {
 };
 static bool halo_gen_geometry(const ConvShape& s, int bn, int hcap, HaloGen& g) {
   if (option_get(OPT_HALO_GEN) == 0) return false;
-  if (!(s.R == 3 && s.S == 3 && s.stride == 1 && s.pad == 1 && s.C % 64 == 0 && s.K % 64 == 0)) return false;
-  g.seg = s.W <= 64 ? s.W : s.W % 64 == 0 ? 64 : s.W % 56 == 0 ? 56 : s.W % 32 == 0 ? 32 : 0;
+  if (!conv3x3_ok(s, 1)) return false;
+  g.seg = row_segment(s.W);
   if (g.seg == 0 || g.seg > bn) return false;
   g.rs = std::min(bn / g.seg, s.H);
   while (g.rs > 1 && s.H % g.rs != 0) --g.rs;
@@ -747,11 +739,9 @@ static bool halo_gen_geometry(const ConvShape& s, int bn, int hcap, HaloGen& g) 
 // the same for the stride-2 forward (output grid Ho x Wo, column-split input box (2 rs + 1) x pitch)
 static bool halo_gen_geometry_s2(const ConvShape& s, int bn, int hcap, HaloGen& g) {
   if (option_get(OPT_HALO_GEN) == 0) return false;
-  if (!(s.R == 3 && s.S == 3 && s.stride == 2 && s.pad == 1 && s.C % 64 == 0 && s.K % 64 == 0 && s.H % 2 == 0 &&
-        s.W % 2 == 0))
-    return false;
+  if (!conv3x3_ok(s, 2) || s.H % 2 || s.W % 2) return false;
   const int ho = s.H / 2, wo = s.W / 2;
-  g.seg = wo <= 64 ? wo : wo % 64 == 0 ? 64 : wo % 56 == 0 ? 56 : wo % 32 == 0 ? 32 : 0;
+  g.seg = row_segment(wo);
   if (g.seg == 0 || g.seg > bn) return false;
   g.rs = std::min(bn / g.seg, ho);
   while (g.rs > 1 && ho % g.rs != 0) --g.rs;
@@ -851,8 +841,7 @@ HaloPlan conv_halo_plan(const ConvShape& s, int mode) {
   return hp;
 }
 
-size_t conv_halo_slab_bytes(const ConvShape& s, int mode) {
-  const HaloPlan hp = conv_halo_plan(s, mode);
+size_t conv_halo_slab_bytes(const ConvShape& s, int mode, const HaloPlan& hp) {
   if (hp.cfg < 0 || hp.split <= 1) return 0;
   const int cout = mode == CONV_FWD ? s.K : s.C;
   return (size_t)hp.split * s.N * s.H * s.W * cout * 4;
@@ -876,10 +865,6 @@ static int launch_halo_ws(const HConvParams& p, int cfg, dim3 grid, hipStream_t 
 
 // (The two-slot weight ring, option halo_wstages=2, is removed: 441 vs 451 us isolated in round 5 but -6.5% in the
 // step at the round-6 kernels, 0 of 10 in-process rounds faster: profiles/r06bc_b256_misc.txt.)
-template <int MODE>
-static int launch_halo(const HConvParams& p, int cfg, dim3 grid, hipStream_t st) {
-  return launch_halo_ws<MODE, 3>(p, cfg, grid, st);
-}
 
 // general tile geometry instances (3-slot weight ring): configurations 0 (64 x 256) and 2 (64 x 128); the
 // stride-2 forward in configuration 8 (64 x 64), with or without the fused shortcut
@@ -911,8 +896,8 @@ static int launch_halo_s2(const HConvParams& p, int cfg, dim3 grid, hipStream_t 
 }
 
 static int conv_halo_general(const ConvShape& s, int mode, const HaloPlan& hp, const u16* src, const u16* w, u16* out,
-                             const u16* res, int64_t* stats, float* slab, size_t slab_bytes, hipStream_t st, u64* ts,
-                             const u16* wsc, u16* out2, int64_t* stats2) {
+                             const u16* res, int64_t* stats, hipStream_t st, u64* ts, const u16* wsc, u16* out2,
+                             int64_t* stats2) {
   DTC_CHECK_ARG(hp.cfg == 0 || hp.cfg == 2 || hp.cfg == kFirstS2Cfg, "conv_halo: general geometry configuration");
   const HaloCfg& c = kHaloCfgs[hp.cfg];
   const int ST = c.st;
@@ -947,7 +932,6 @@ static int conv_halo_general(const ConvShape& s, int mode, const HaloPlan& hp, c
   p.fd_spx = make_fastdiv(g.rs * g.seg);
   p.fd_w = make_fastdiv(p.Wo);
   p.ts = ts;
-  (void)slab; (void)slab_bytes;
   const int64_t ntiles = (int64_t)s.N * g.tpi * p.tiles_a;
   DTC_CHECK_ARG(ntiles < (1ll << 31), "conv_halo: too many tiles");
   const dim3 grid((unsigned)ntiles, 1);
@@ -963,12 +947,12 @@ extern "C" int dtc_probe_phase_buffer(void* buf) {  // diagnostic builds only (t
 #endif
 
 int conv_halo(const ConvShape& s, int mode, const HaloPlan& hp, const u16* src, const u16* w, u16* out,
-              const u16* res, int64_t* stats, float* slab, size_t slab_bytes, hipStream_t st, u64* ts,
-              const u16* wsc, u16* out2, int64_t* stats2, unsigned* tick) {
+              const u16* res, int64_t* stats, float* slab, hipStream_t st, u64* ts, const u16* wsc, u16* out2,
+              int64_t* stats2, unsigned* tick) {
   DTC_CHECK_ARG(hp.cfg >= 0 && hp.cfg < kNumHaloCfgs && (mode == CONV_FWD || mode == CONV_DGRAD),
                 "conv_halo: unsupported configuration");
   const HaloCfg& c = kHaloCfgs[hp.cfg];
-  if (hp.gen) return conv_halo_general(s, mode, hp, src, w, out, res, stats, slab, slab_bytes, st, ts, wsc, out2, stats2);
+  if (hp.gen) return conv_halo_general(s, mode, hp, src, w, out, res, stats, st, ts, wsc, out2, stats2);
   DTC_CHECK_ARG(halo_shape_ok(s, c.st) && (c.st == 1 || mode == CONV_FWD), "conv_halo: unsupported shape / pass");
   DTC_CHECK_ARG(wsc == nullptr || (c.st == 2 && out2 != nullptr), "conv_halo: the shortcut fusion is stride-2 FWD");
   HConvParams p{};
@@ -983,8 +967,8 @@ int conv_halo(const ConvShape& s, int mode, const HaloPlan& hp, const u16* src, 
   p.rows = g.rows; p.imgs = g.imgs; p.nh = g.nh; p.hb = g.hb;
   p.Ho = g.ho; p.Wo = g.wo; p.pitch = g.pitch; p.hwh = g.hwh;
   const int M = s.N * g.ho * g.wo;
-  int split = hp.split;
-  if (split > 1 && (slab == nullptr || slab_bytes < (size_t)split * M * p.Cout * 4)) split = 1;
+  const int split = hp.split;  // (conv_route planned one split where the slab on hand is too small)
+  DTC_CHECK_ARG(split == 1 || slab != nullptr, "conv_halo: split-K needs the slab");
   DTC_CHECK_ARG((p.Cin / 64) % split == 0, "conv_halo: split %d does not divide the reduction", split);
   DTC_CHECK_ARG(split == 1 || c.st == 1, "conv_halo: stride 2 has no split-K");
   p.slab = split > 1 ? slab : nullptr;
@@ -1010,7 +994,7 @@ int conv_halo(const ConvShape& s, int mode, const HaloPlan& hp, const u16* src, 
   if (c.st == 2) {
     return wsc ? launch_halo_s2<true>(p, hp.cfg, grid, st) : launch_halo_s2<false>(p, hp.cfg, grid, st);
   }
-  DTC_TRY(mode == CONV_FWD ? launch_halo<0>(p, hp.cfg, grid, st) : launch_halo<1>(p, hp.cfg, grid, st));
+  DTC_TRY(mode == CONV_FWD ? (launch_halo_ws<0, 3>(p, hp.cfg, grid, st)) : (launch_halo_ws<1, 3>(p, hp.cfg, grid, st)));
   if (split > 1 && !ink) return splitk_reduce(slab, split, M, p.Cout, out, res, stats, st, ts);
   return 0;
 }

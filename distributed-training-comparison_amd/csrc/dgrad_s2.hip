@@ -278,9 +278,7 @@ __global__ void __launch_bounds__(256, 2) dgrad_s2_kernel(const S2dParams p) {
 // ---------------------------------------------------------------- host side
 // Tile geometry: BN consecutive dy-grid positions = whole dy rows of one image, or whole images.
 static bool s2d_geometry(const ConvShape& s, int bn, int hcap, int& rows, int& imgs, int& hb, int& nh) {
-  if (!(s.R == 3 && s.S == 3 && s.stride == 2 && s.pad == 1 && s.C % 64 == 0 && s.K % 64 == 0 && s.H % 2 == 0 &&
-        s.W % 2 == 0))
-    return false;
+  if (!conv3x3_ok(s, 2) || s.H % 2 || s.W % 2) return false;
   const int ho = s.H / 2, wo = s.W / 2, hw = ho * wo;
   if (hw >= bn) {
     if (bn % wo || ho % (bn / wo)) return false;

@@ -737,30 +737,7 @@ __global__ void prof_accumulate_kernel(u64* ts, int n, u64* acc) {
   }
 }
 
-// ---------------------------------------------------------------- host launchers
-static int fill_common(IGemmParams& p, const ConvShape& s) {
-  p.N = s.N; p.H = s.H; p.W = s.W; p.C = s.C; p.K = s.K; p.R = s.R; p.S = s.S;
-  p.stride = s.stride; p.pad = s.pad;
-  p.P = (s.H + 2 * s.pad - s.R) / s.stride + 1;
-  p.Q = (s.W + 2 * s.pad - s.S) / s.stride + 1;
-  p.RSC = s.R * s.S * s.C;
-  DTC_CHECK_ARG(s.C % 64 == 0 && s.K % 64 == 0, "conv: C (%d) and K (%d) must be multiples of 64", s.C, s.K);
-  DTC_CHECK_ARG(s.stride == 1 || s.stride == 2, "conv: stride must be 1 or 2");
-  DTC_CHECK_ARG(s.N > 0 && s.H > 0 && s.W > 0 && p.P > 0 && p.Q > 0, "conv: bad geometry");
-  return 0;
-}
-
-template <int MODE, int BM, int BN, int WR, int WC, bool SLAB, bool SC = false>
-static int launch_igemm(IGemmParams& p, int tiles_b, int splits, hipStream_t st, int gz = 1) {
-  dim3 grid(p.tiles_a * tiles_b, splits, gz);
-  p.xcd_remap = option_get(OPT_XCD_REMAP);
-  DTC_KLAUNCH((igemm_kernel<MODE, BM, BN, WR, WC, SLAB, 2, SC>), grid, dim3(256), 0, st, p);
-  DTC_LAUNCH_CHECK();
-  return 0;
-}
-
-static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
-
+// ---------------------------------------------------------------- host side
 // Choose split-K so that the grid holds about `target` workgroups while each split keeps
 // at least `min_kt` reduction steps.
 static int pick_splits(int tiles, int num_kt, int target, int min_kt) {
@@ -769,252 +746,146 @@ static int pick_splits(int tiles, int num_kt, int target, int min_kt) {
   return std::max(1, s);
 }
 
-static bool dgrad_class_mode(const ConvShape& s) {
+bool dgrad_class_mode(const ConvShape& s) {
   return s.stride == 2 && (s.H % 2) == 0 && (s.W % 2) == 0 && option_get(OPT_DGRAD_CLASSES) != 0;
 }
 
-bool dgrad_class_ok(const ConvShape& s) { return dgrad_class_mode(s) && !conv_c64_ok(s) && conv_halo_plan(s, CONV_DGRAD).cfg < 0; }
-
-ConvPlan plan_conv(const ConvShape& s, int mode) {
-  ConvPlan pl{};
+GemmPlan igemm_plan(const ConvShape& s, int pass, bool cls) {
+  GemmPlan pl{};
   const int P = (s.H + 2 * s.pad - s.R) / s.stride + 1;
   const int Q = (s.W + 2 * s.pad - s.S) / s.stride + 1;
-  const bool cls = (mode == CONV_DGRAD) && dgrad_class_mode(s);
-  if (mode == CONV_FWD || mode == CONV_DGRAD) {
-    const int M = (mode == CONV_FWD) ? s.N * P * Q : (cls ? s.N * (s.H / 2) * (s.W / 2) : s.N * s.H * s.W);
-    const int A = (mode == CONV_FWD) ? s.K : s.C;
-    const int num_kt = s.R * s.S * ((mode == CONV_FWD) ? s.C : s.K) / 64;
+  const int ft = option_get(OPT_IGEMM_TILE);  // tuning override
+  if (pass == CONV_FWD || pass == CONV_DGRAD) {
+    const int M = (pass == CONV_FWD) ? s.N * P * Q : (cls ? s.N * (s.H / 2) * (s.W / 2) : s.N * s.H * s.W);
+    const int A = (pass == CONV_FWD) ? s.K : s.C;
+    pl.num_kt = s.R * s.S * ((pass == CONV_FWD) ? s.C : s.K) / 64;
     // big tiles while they fill the chip (>= ~2 waves of 256 CUs), else 64x64 tiles, else split-K
     if (A == 64) { pl.bm = 64; pl.bn = 256; }
     else { pl.bm = 128; pl.bn = 128; }
     if ((A / pl.bm) * ceil_div(M, pl.bn) < 400) { pl.bm = 64; pl.bn = 64; }
-    const int ft = option_get(OPT_IGEMM_TILE);  // tuning override
     if (ft == 1) { pl.bm = 64; pl.bn = 64; }
     else if (ft == 2 && A % 128 == 0) { pl.bm = 128; pl.bn = 128; }
     else if (ft == 3) { pl.bm = 64; pl.bn = 256; }
     const int tiles = (A / pl.bm) * ceil_div(M, pl.bn);
-    pl.splits = (tiles >= 256 || cls) ? 1 : pick_splits(tiles, num_kt, 480, 8);
-    if (option_get(OPT_IGEMM_SPLIT) > 0 && !cls) pl.splits = std::min(option_get(OPT_IGEMM_SPLIT), num_kt);
+    pl.splits = (tiles >= 256 || cls) ? 1 : pick_splits(tiles, pl.num_kt, 480, 8);
+    if (option_get(OPT_IGEMM_SPLIT) > 0 && !cls) pl.splits = std::min(option_get(OPT_IGEMM_SPLIT), pl.num_kt);
     pl.slab_bytes = pl.splits > 1 ? (size_t)pl.splits * M * A * 4 : 0;
-    pl.slab_bytes = std::max(pl.slab_bytes, conv_halo_slab_bytes(s, mode));
-    pl.num_kt = num_kt;
-  } else if (const int s2 = wgrad_s2_splits(s)) {  // stride-2 column-split halo kernel (wgrad_halo.hip)
-    pl.bm = 576;
-    pl.bn = 64;
-    pl.splits = s2;
-    pl.num_kt = s.N * P * Q / 64;
-    pl.slab_bytes = conv_wgrad_s2_slab_bytes(s);
-  } else if (const int hs = wgrad_halo_splits(s)) {  // halo-tiled kernel (wgrad_halo.hip)
-    pl.bm = 576;
-    pl.bn = 64;
-    pl.splits = hs;
-    pl.num_kt = s.N * P * Q / 64;
-    pl.slab_bytes = (size_t)hs * s.K * s.R * s.S * s.C * 4;
   } else {
-    const int M = s.N * P * Q;
-    const int num_kt = ceil_div(M, 64);
+    const int RSC = s.R * s.S * s.C;
+    pl.num_kt = ceil_div(s.N * P * Q, 64);
     pl.bm = (s.C == 64 || s.K == 64) ? 64 : 128;
+    if ((RSC / pl.bm) * (s.K / pl.bm) < 64) pl.bm = 64;  // few output tiles: more of them
+    if (ft == 1) pl.bm = 64;
+    else if (ft == 2 && RSC % 128 == 0 && s.K % 128 == 0) pl.bm = 128;
     pl.bn = pl.bm;
-    if ((s.R * s.S * s.C / pl.bm) * (s.K / pl.bn) < 64) pl.bm = pl.bn = 64;  // few output tiles: more of them
-    const int ft = option_get(OPT_IGEMM_TILE);  // tuning override
-    if (ft == 1) pl.bm = pl.bn = 64;
-    else if (ft == 2 && (s.R * s.S * s.C) % 128 == 0 && s.K % 128 == 0) pl.bm = pl.bn = 128;
-    const int tiles = (s.R * s.S * s.C / pl.bm) * (s.K / pl.bn);
-    pl.splits = pick_splits(tiles, num_kt, 512, tiles < 64 ? 8 : 16);
-    if (option_get(OPT_IGEMM_SPLIT) > 0) pl.splits = std::min(option_get(OPT_IGEMM_SPLIT), num_kt);
-    pl.slab_bytes = (size_t)pl.splits * s.K * s.R * s.S * s.C * 4;
-    pl.num_kt = num_kt;
+    const int tiles = (RSC / pl.bm) * (s.K / pl.bn);
+    pl.splits = pick_splits(tiles, pl.num_kt, 512, tiles < 64 ? 8 : 16);
+    if (option_get(OPT_IGEMM_SPLIT) > 0) pl.splits = std::min(option_get(OPT_IGEMM_SPLIT), pl.num_kt);
+    pl.slab_bytes = (size_t)pl.splits * s.K * RSC * 4;
   }
   return pl;
 }
 
-int conv_fwd(const ConvShape& s, const u16* x, const u16* w, u16* y, int64_t* stats, float* slab,
-             size_t slab_bytes, hipStream_t st, u64* ts, unsigned* tick) {
-  if (conv_c64_ok(s)) return conv_c64(s, CONV_FWD, x, w, y, nullptr, stats, st, ts);
-  {
-    const HaloPlan hp = conv_halo_plan(s, CONV_FWD);
-    if (hp.cfg >= 0)
-      return conv_halo(s, CONV_FWD, hp, x, w, y, nullptr, stats, slab, slab_bytes, st, ts, nullptr, nullptr, nullptr,
-                       tick);
-  }
-  IGemmParams p{};
+static int fill_common(IGemmParams& p, const ConvShape& s, const GemmPlan& pl, u64* ts) {
   p.ts = ts;
-  DTC_TRY(fill_common(p, s));
-  ConvPlan pl = plan_conv(s, CONV_FWD);
+  p.N = s.N; p.H = s.H; p.W = s.W; p.C = s.C; p.K = s.K; p.R = s.R; p.S = s.S;
+  p.stride = s.stride; p.pad = s.pad;
+  p.P = (s.H + 2 * s.pad - s.R) / s.stride + 1;
+  p.Q = (s.W + 2 * s.pad - s.S) / s.stride + 1;
+  p.RSC = s.R * s.S * s.C;
+  p.num_kt = pl.num_kt;
+  p.kt_per_split = ceil_div(pl.num_kt, std::max(pl.splits, 1));
+  DTC_CHECK_ARG(s.C % 64 == 0 && s.K % 64 == 0, "conv: C (%d) and K (%d) must be multiples of 64", s.C, s.K);
+  DTC_CHECK_ARG(s.stride == 1 || s.stride == 2, "conv: stride must be 1 or 2");
+  DTC_CHECK_ARG(s.N > 0 && s.H > 0 && s.W > 0 && p.P > 0 && p.Q > 0, "conv: bad geometry");
+  return 0;
+}
+
+template <int MODE, int BM, int BN, int WR, int WC, bool SLAB, bool SC>
+static int launch_igemm(IGemmParams& p, int splits, int gz, hipStream_t st) {
+  const int tiles_b = MODE == MODE_WGRAD ? p.K / BN : ceil_div(p.M, BN);
+  p.tiles_a = (MODE == MODE_FWD ? p.K : MODE == MODE_DGRAD ? p.C : p.RSC) / BM;
+  dim3 grid(p.tiles_a * tiles_b, splits, gz);
+  p.xcd_remap = option_get(OPT_XCD_REMAP);
+  DTC_KLAUNCH((igemm_kernel<MODE, BM, BN, WR, WC, SLAB, 2, SC>), grid, dim3(256), 0, st, p);
+  DTC_LAUNCH_CHECK();
+  return 0;
+}
+
+// The one tile switch. Instantiated: FWD and DGRAD at the three tiles, with and without the slab epilogue; the
+// shortcut-fused FWD at 64x64 and 128x128, no slab; WGRAD at 64x64 and 128x128, slab only.
+template <int MODE, bool SLAB, bool SC = false>
+static int launch_tile(IGemmParams& p, const GemmPlan& pl, hipStream_t st, int gz = 1) {
+  if (pl.bn == 64) return launch_igemm<MODE, 64, 64, 2, 2, SLAB, SC>(p, pl.splits, gz, st);
+  if constexpr (MODE != MODE_WGRAD && !SC)
+    if (pl.bm == 64) return launch_igemm<MODE, 64, 256, 1, 4, SLAB, SC>(p, pl.splits, gz, st);
+  return launch_igemm<MODE, 128, 128, 2, 2, SLAB, SC>(p, pl.splits, gz, st);
+}
+
+int igemm_fwd(const ConvShape& s, const GemmPlan& pl, const u16* x, const u16* w, u16* y, int64_t* stats, float* slab,
+              const u16* wsc, u16* ysc, int64_t* stats_sc, hipStream_t st, u64* ts) {
+  IGemmParams p{};
+  DTC_TRY(fill_common(p, s, pl, ts));
   p.src0 = x; p.src1 = w; p.out = y; p.stats = stats;
   p.M = s.N * p.P * p.Q;
   p.fd_q = make_fastdiv(p.Q); p.fd_pq = make_fastdiv(p.P * p.Q); p.fd_cc = make_fastdiv(s.C / 64);
-  p.num_kt = pl.num_kt;
-  p.tiles_a = s.K / pl.bm;
-  const int tiles_b = ceil_div(p.M, pl.bn);
-  int splits = pl.splits;
-  if (splits > 1 && (slab == nullptr || slab_bytes < pl.slab_bytes)) splits = 1;
-  p.kt_per_split = ceil_div(p.num_kt, splits);
-  splits = ceil_div(p.num_kt, p.kt_per_split);
-  if (splits > 1) {
-    p.slab = slab;
-    if (pl.bn == 64) DTC_TRY((launch_igemm<MODE_FWD, 64, 64, 2, 2, true>(p, tiles_b, splits, st)));
-    else if (pl.bm == 64) DTC_TRY((launch_igemm<MODE_FWD, 64, 256, 1, 4, true>(p, tiles_b, splits, st)));
-    else DTC_TRY((launch_igemm<MODE_FWD, 128, 128, 2, 2, true>(p, tiles_b, splits, st)));
-    return splitk_reduce(slab, splits, p.M, s.K, y, nullptr, stats, st, ts);
+  if (wsc != nullptr) {
+    // the shortcut's reduction is the 3x3's centre tap (r, s) = (1, 1) -- the pixel (2p, 2q) the 1x1 stride-2 conv
+    // reads -- so it reuses those im2col tiles; same per-output MFMA order as its own launch without split-K
+    DTC_CHECK_ARG(pl.splits == 1 && pl.bm == pl.bn && ysc, "igemm_fwd: the shortcut fusion has no split-K / 64x256 tile");
+    p.src1b = wsc; p.out2 = ysc; p.stats2 = stats_sc;
+    p.kt_c0 = (1 * s.S + 1) * (s.C / 64);
+    p.kt_c1 = p.kt_c0 + s.C / 64;
+    return launch_tile<MODE_FWD, false, true>(p, pl, st);
   }
-  if (pl.bn == 64) return launch_igemm<MODE_FWD, 64, 64, 2, 2, false>(p, tiles_b, 1, st);
-  if (pl.bm == 64) return launch_igemm<MODE_FWD, 64, 256, 1, 4, false>(p, tiles_b, 1, st);
-  return launch_igemm<MODE_FWD, 128, 128, 2, 2, false>(p, tiles_b, 1, st);
+  if (pl.splits == 1) return launch_tile<MODE_FWD, false>(p, pl, st);
+  p.slab = slab;
+  DTC_TRY((launch_tile<MODE_FWD, true>(p, pl, st)));
+  return splitk_reduce(slab, pl.splits, p.M, s.K, y, nullptr, stats, st, ts);
 }
 
-// 3x3 stride-2 conv + its block's 1x1 stride-2 projection shortcut in one launch (option sc_fuse):
-// the shortcut's reduction is the centre tap of the 3x3's, so it reuses those im2col tiles (one read
-// of x, one launch). Same per-output MFMA order as the separate launch when that one has no split-K.
-bool conv_fwd_sc_ok(const ConvShape& s, const ConvShape& sc) {
-  if (!(s.R == 3 && s.S == 3 && s.stride == 2 && s.pad == 1 && sc.R == 1 && sc.S == 1 && sc.stride == 2 &&
-        sc.pad == 0 && sc.N == s.N && sc.H == s.H && sc.W == s.W && sc.C == s.C && sc.K == s.K && s.C % 64 == 0))
-    return false;
-  if (conv_c64_ok(s)) return false;
-  if (conv_halo_plan(s, CONV_FWD).cfg >= 0) return s.stride == 2;  // column-split halo kernel with SC
-  const ConvPlan pl = plan_conv(s, CONV_FWD);
-  // sc_fuse=1: 64x64-tile plans of at most 512 workgroups (layer4 at B=256: 35.3 us fused vs 8.2 + 31.1
-  // separate); 2: every 64x64 plan (layer3: 35.6 vs 9.7 + 23.0 -- the shortcut's own 1024-workgroup launch
-  // is cheaper than the fused kernel's lower occupancy); 3: also 128x128 (layer2: its W_sc stage takes
-  // LDS to 96 KB, one workgroup per CU: 44.1 vs 11.8 + 21.2)
-  const int lvl = option_get(OPT_SC_FUSE);
-  if (pl.splits > 1) return false;
-  if (pl.bn == 64) return lvl >= 2 || (int64_t)(s.K / 64) * ceil_div(s.N * ((s.H + 1) / 2) * ((s.W + 1) / 2), 64) <= 512;
-  return pl.bm != 64 && lvl >= 3;
-}
-
-int conv_fwd_sc(const ConvShape& s, const ConvShape& sc, const u16* x, const u16* w, u16* y, int64_t* stats,
-                const u16* wsc, u16* ysc, int64_t* stats_sc, hipStream_t st, u64* ts) {
-  DTC_CHECK_ARG(conv_fwd_sc_ok(s, sc) && x && w && y && wsc && ysc, "conv_fwd_sc: unsupported shapes");
-  {
-    const HaloPlan hp = conv_halo_plan(s, CONV_FWD);
-    if (hp.cfg >= 0)
-      return conv_halo(s, CONV_FWD, hp, x, w, y, nullptr, stats, nullptr, 0, st, ts, wsc, ysc, stats_sc);
-  }
+int igemm_dgrad(const ConvShape& s, const GemmPlan& pl, bool cls, const u16* dy, const u16* w, u16* dx, const u16* res,
+                int res_compact, const u16* dsc, const u16* wsc, float* slab, hipStream_t st, u64* ts) {
   IGemmParams p{};
-  p.ts = ts;
-  DTC_TRY(fill_common(p, s));
-  const ConvPlan pl = plan_conv(s, CONV_FWD);
-  p.src0 = x; p.src1 = w; p.out = y; p.stats = stats;
-  p.src1b = wsc; p.out2 = ysc; p.stats2 = stats_sc;
-  p.M = s.N * p.P * p.Q;
-  p.fd_q = make_fastdiv(p.Q); p.fd_pq = make_fastdiv(p.P * p.Q); p.fd_cc = make_fastdiv(s.C / 64);
-  p.num_kt = pl.num_kt;
-  p.kt_per_split = p.num_kt;
-  const int nchunk = s.C / 64;
-  p.kt_c0 = (1 * s.S + 1) * nchunk;  // tap (r, s) = (1, 1): the pixel (2p, 2q) the 1x1 stride-2 conv reads
-  p.kt_c1 = p.kt_c0 + nchunk;
-  p.tiles_a = s.K / pl.bm;
-  const int tiles_b = ceil_div(p.M, pl.bn);
-  if (pl.bn == 64) return launch_igemm<MODE_FWD, 64, 64, 2, 2, false, true>(p, tiles_b, 1, st);
-  return launch_igemm<MODE_FWD, 128, 128, 2, 2, false, true>(p, tiles_b, 1, st);
-}
-
-// The BN-backward pass after a dgrad whose kernel has no fused epilogue for it (in place on dx).
-static int bnb_after(const BnbArgs* bnb, u16* dx, int64_t M, int C, hipStream_t st) {
-  if (bnb == nullptr || !bnb_on(*bnb)) return 0;
-  if (bnb->mb)  // mask bits: the sums only (dx stays the raw gradient; the BN apply masks it)
-    return bn_bwd_reduce_mask(dx, bnb->mb, bnb->x1, bnb->mean1, bnb->invstd1, bnb->acc1, bnb->x2, bnb->mean2,
-                              bnb->invstd2, bnb->acc2, M, C, st);
-  return bn_bwd_reduce(dx, bnb->ym, bnb->x1, bnb->mean1, bnb->invstd1, bnb->acc1, bnb->x2, bnb->mean2, bnb->invstd2,
-                       bnb->acc2, dx, M, C, st);
-}
-
-int conv_dgrad(const ConvShape& s, const u16* dy, const u16* w, u16* dx, const u16* res, float* slab,
-               size_t slab_bytes, hipStream_t st, u64* ts, const BnbArgs* bnb, int res_compact, unsigned* tick) {
-  if (bnb != nullptr && !bnb_on(*bnb)) bnb = nullptr;
-  DTC_CHECK_ARG(!res_compact || (res && dgrad_class_mode(s) && !conv_c64_ok(s)),
-                "conv_dgrad: a compact residual needs the stride-2 parity-class path");
-  // the BN-backward sums of dx by a reduction pass after the conv (the round-3/4 epilogue fusions measured
-  // slower than the separate pass and were removed in round 5)
-  if (bnb != nullptr) {
-    DTC_TRY(conv_dgrad(s, dy, w, dx, res, slab, slab_bytes, st, ts, nullptr, res_compact, tick));
-    return bnb_after(bnb, dx, (int64_t)s.N * s.H * s.W, s.C, st);
-  }
-  const HaloPlan hp = conv_c64_ok(s) ? HaloPlan{-1, 0} : conv_halo_plan(s, CONV_DGRAD);
-  const int kind = conv_c64_ok(s) ? 1 : (hp.cfg >= 0 ? 2 : 4);
-  if (kind == 1) return conv_c64(s, CONV_DGRAD, dy, w, dx, res, nullptr, st, ts);
-  if (kind == 2)
-    return conv_halo(s, CONV_DGRAD, hp, dy, w, dx, res, nullptr, slab, slab_bytes, st, ts, nullptr, nullptr, nullptr,
-                     tick);
-  IGemmParams p{};
-  p.ts = ts;
-  DTC_TRY(fill_common(p, s));
-  ConvPlan pl = plan_conv(s, CONV_DGRAD);
+  DTC_TRY(fill_common(p, s, pl, ts));
   p.src0 = dy; p.src1 = w; p.out = dx; p.res = res;
   p.fd_cc = make_fastdiv(s.K / 64);
-  p.num_kt = pl.num_kt;
-  p.tiles_a = s.C / pl.bm;
-  if (dgrad_class_mode(s) && res == nullptr && dgrad_s2_halo_ok(s)) {  // the halo sub-pixel kernel (dgrad_s2.hip)
-    DTC_TRY(conv_dgrad_s2_halo(s, dy, w, dx, nullptr, nullptr, st, ts));
-    return bnb_after(bnb, dx, (int64_t)s.N * s.H * s.W, s.C, st);
-  }
-  if (dgrad_class_mode(s)) {  // four parity-class GEMMs in one launch (blockIdx.z), no split-K
+  if (cls) {  // four parity-class GEMMs in one launch (blockIdx.z), each over one class's pixel grid, no split-K;
+    // class (0, 0) adds a compact residual or runs the fused shortcut's extra reduction steps
+    DTC_CHECK_ARG(pl.splits == 1 && !(res_compact && !res) && !(dsc && (res || !wsc)), "igemm_dgrad: class arguments");
     p.cls = 1;
     p.cls_order = option_get(OPT_DGRAD_CLASS_ORDER);
-    p.res_compact = res_compact;
     p.M = s.N * (s.H / 2) * (s.W / 2);
     p.fd_q = make_fastdiv(s.W / 2);
     p.fd_pq = make_fastdiv((s.H / 2) * (s.W / 2));
-    p.kt_per_split = p.num_kt;
-    const int tb = ceil_div(p.M, pl.bn);
-    if (pl.bn == 64) DTC_TRY((launch_igemm<MODE_DGRAD, 64, 64, 2, 2, false>(p, tb, 1, st, 4)));
-    else if (pl.bm == 64) DTC_TRY((launch_igemm<MODE_DGRAD, 64, 256, 1, 4, false>(p, tb, 1, st, 4)));
-    else DTC_TRY((launch_igemm<MODE_DGRAD, 128, 128, 2, 2, false>(p, tb, 1, st, 4)));
-    return bnb_after(bnb, dx, (int64_t)s.N * s.H * s.W, s.C, st);
+    p.res_compact = res_compact;
+    if (dsc != nullptr) { p.src0b = dsc; p.src1b = wsc; p.sc_kt = s.K / 64; }
+    return launch_tile<MODE_DGRAD, false>(p, pl, st, 4);
   }
+  DTC_CHECK_ARG(!res_compact && !dsc, "igemm_dgrad: a compact residual / fused shortcut needs the parity classes");
   p.M = s.N * s.H * s.W;
   p.fd_q = make_fastdiv(s.W); p.fd_pq = make_fastdiv(s.H * s.W);
-  const int tiles_b = ceil_div(p.M, pl.bn);
-  int splits = pl.splits;
-  if (splits > 1 && (slab == nullptr || slab_bytes < pl.slab_bytes)) splits = 1;
-  p.kt_per_split = ceil_div(p.num_kt, splits);
-  splits = ceil_div(p.num_kt, p.kt_per_split);
-  if (splits > 1) {
-    p.slab = slab;
-    if (pl.bn == 64) DTC_TRY((launch_igemm<MODE_DGRAD, 64, 64, 2, 2, true>(p, tiles_b, splits, st)));
-    else if (pl.bm == 64) DTC_TRY((launch_igemm<MODE_DGRAD, 64, 256, 1, 4, true>(p, tiles_b, splits, st)));
-    else DTC_TRY((launch_igemm<MODE_DGRAD, 128, 128, 2, 2, true>(p, tiles_b, splits, st)));
-    return splitk_reduce(slab, splits, p.M, s.C, dx, res, nullptr, st, ts);
-  }
-  if (pl.bn == 64) DTC_TRY((launch_igemm<MODE_DGRAD, 64, 64, 2, 2, false>(p, tiles_b, 1, st)));
-  else if (pl.bm == 64) DTC_TRY((launch_igemm<MODE_DGRAD, 64, 256, 1, 4, false>(p, tiles_b, 1, st)));
-  else DTC_TRY((launch_igemm<MODE_DGRAD, 128, 128, 2, 2, false>(p, tiles_b, 1, st)));
-  return bnb_after(bnb, dx, p.M, s.C, st);
+  if (pl.splits == 1) return launch_tile<MODE_DGRAD, false>(p, pl, st);
+  p.slab = slab;
+  DTC_TRY((launch_tile<MODE_DGRAD, true>(p, pl, st)));
+  return splitk_reduce(slab, pl.splits, p.M, s.C, dx, res, nullptr, st, ts);
 }
 
-// conv1 (3x3 stride 2) of a projection block and its 1x1 stride-2 shortcut: dx = dgrad(dc1, W1) +
-// dgrad(dsc, W_sc) in ONE parity-class launch (the shortcut's term lives at class (0, 0) only, as extra
-// reduction steps there: no separate shortcut dgrad launch and no compact residual pass).
-bool conv_dgrad_sc_ok(const ConvShape& s) { return dgrad_class_ok(s) && s.R == 3 && s.pad == 1 && option_get(OPT_DGRAD_SCF) != 0; }
-int conv_dgrad_sc(const ConvShape& s, const u16* dy, const u16* w, u16* dx, const u16* dsc, const u16* wsc,
-                  hipStream_t st, u64* ts, const BnbArgs* bnb) {
-  DTC_CHECK_ARG(conv_dgrad_sc_ok(s) && dy && w && dx && dsc && wsc, "conv_dgrad_sc: unsupported geometry / args");
-  if (bnb != nullptr && !bnb_on(*bnb)) bnb = nullptr;
-  if (dgrad_s2_halo_ok(s)) {  // option dgrad_s2h: the halo sub-pixel kernel (dgrad_s2.hip), shortcut fused
-    DTC_TRY(conv_dgrad_s2_halo(s, dy, w, dx, dsc, wsc, st, ts));
-    return bnb_after(bnb, dx, (int64_t)s.N * s.H * s.W, s.C, st);
-  }
+int igemm_wgrad(const ConvShape& s, const GemmPlan& pl, const u16* x, const u16* dy, float* slab, hipStream_t st,
+                u64* ts) {
   IGemmParams p{};
-  p.ts = ts;
-  DTC_TRY(fill_common(p, s));
-  ConvPlan pl = plan_conv(s, CONV_DGRAD);
-  p.src0 = dy; p.src1 = w; p.out = dx; p.res = nullptr;
-  p.src0b = dsc; p.src1b = wsc; p.sc_kt = s.K / 64;
-  p.fd_cc = make_fastdiv(s.K / 64);
-  p.num_kt = pl.num_kt;
-  p.tiles_a = s.C / pl.bm;
-  p.cls = 1;
-  p.cls_order = option_get(OPT_DGRAD_CLASS_ORDER);
-  p.M = s.N * (s.H / 2) * (s.W / 2);
-  p.fd_q = make_fastdiv(s.W / 2);
-  p.fd_pq = make_fastdiv((s.H / 2) * (s.W / 2));
-  p.kt_per_split = p.num_kt;
-  const int tb = ceil_div(p.M, pl.bn);
-  if (pl.bn == 64) DTC_TRY((launch_igemm<MODE_DGRAD, 64, 64, 2, 2, false>(p, tb, 1, st, 4)));
-  else if (pl.bm == 64) DTC_TRY((launch_igemm<MODE_DGRAD, 64, 256, 1, 4, false>(p, tb, 1, st, 4)));
-  else DTC_TRY((launch_igemm<MODE_DGRAD, 128, 128, 2, 2, false>(p, tb, 1, st, 4)));
-  return bnb_after(bnb, dx, (int64_t)s.N * s.H * s.W, s.C, st);
+  DTC_TRY(fill_common(p, s, pl, ts));
+  p.src0 = x; p.src1 = dy; p.slab = slab;
+  p.M = s.N * p.P * p.Q;
+  p.fd_q = make_fastdiv(p.Q); p.fd_pq = make_fastdiv(p.P * p.Q); p.fd_cc = make_fastdiv(1);
+  const int PQ = p.P * p.Q;
+  const uint64_t xb = (uint64_t)s.N * s.H * s.W * s.C * 2, db = (uint64_t)p.M * s.K * 2;
+  const bool rows = (PQ % 64 == 0) && (64 % p.Q == 0);
+  const bool imgs = (64 % PQ == 0);
+  p.wg_fast = (rows || imgs) && xb < (1ull << 31) && db < (1ull << 31) && option_get(OPT_WGRAD_FAST) != 0;
+  p.src0_bytes = (uint32_t)xb;
+  p.src1_bytes = (uint32_t)db;
+  return launch_tile<MODE_WGRAD, true>(p, pl, st);
 }
 
 static int launch_wgrad_reduce(const float* slab, int splits, int K, int RSC, int ncols, int ldo, float scale,
@@ -1037,57 +908,13 @@ static int launch_wgrad_reduce(const float* slab, int splits, int K, int RSC, in
   return 0;
 }
 
-int conv_wgrad(const ConvShape& s, const u16* x, const u16* dy, float* dw, int dw_cols, int dw_ld, float scale,
-               float* slab, size_t slab_bytes, hipStream_t st, u64* ts) {
-  if (wgrad_s2_splits(s) > 0 && (dw_cols <= 0 || dw_cols == 9 * s.C) && (dw_ld <= 0 || dw_ld == 9 * s.C) &&
-      slab_bytes >= conv_wgrad_s2_slab_bytes(s))
-    return conv_wgrad_s2(s, x, dy, nullptr, dw, nullptr, scale, slab, slab_bytes, st, ts);
-  IGemmParams p{};
-  p.ts = ts;
-  DTC_TRY(fill_common(p, s));
-  ConvPlan pl = plan_conv(s, CONV_WGRAD);
-  DTC_CHECK_ARG(slab != nullptr && slab_bytes >= (size_t)s.K * p.RSC * 4, "wgrad: slab workspace too small");
-  p.src0 = x; p.src1 = dy; p.slab = slab;
-  p.M = s.N * p.P * p.Q;
-  p.fd_q = make_fastdiv(p.Q); p.fd_pq = make_fastdiv(p.P * p.Q); p.fd_cc = make_fastdiv(1);
-  {
-    const int PQ = p.P * p.Q;
-    const uint64_t xb = (uint64_t)s.N * s.H * s.W * s.C * 2, db = (uint64_t)p.M * s.K * 2;
-    const bool rows = (PQ % 64 == 0) && (64 % p.Q == 0);
-    const bool imgs = (64 % PQ == 0);
-    p.wg_fast = (rows || imgs) && xb < (1ull << 31) && db < (1ull << 31) && option_get(OPT_WGRAD_FAST) != 0;
-    p.src0_bytes = (uint32_t)xb;
-    p.src1_bytes = (uint32_t)db;
-  }
-  int splits = pl.splits;
-  if (pl.bm == 576 && slab_bytes >= pl.slab_bytes) {
-    const bool whole = (dw_cols <= 0 || dw_cols == p.RSC) && (dw_ld <= 0 || dw_ld == p.RSC);
-    DTC_TRY(conv_wgrad_halo(s, 1, &x, &dy, slab, pl.splits, &splits, st, ts, whole ? &dw : nullptr, scale));
-    if (splits == 0) return 0;  // one split: the halo kernel wrote dw itself
-  } else {
-    if (pl.bm == 576) pl = ConvPlan{64, 64, 1, ceil_div(p.M, 64), 0};  // workspace too small for the halo plan
-    p.num_kt = pl.num_kt;
-    p.tiles_a = p.RSC / pl.bm;
-    const int tiles_b = s.K / pl.bn;
-    while (splits > 1 && (size_t)splits * s.K * p.RSC * 4 > slab_bytes) --splits;
-    p.kt_per_split = ceil_div(p.num_kt, splits);
-    splits = ceil_div(p.num_kt, p.kt_per_split);
-    if (pl.bm == 64) DTC_TRY((launch_igemm<MODE_WGRAD, 64, 64, 2, 2, true>(p, tiles_b, splits, st)));
-    else DTC_TRY((launch_igemm<MODE_WGRAD, 128, 128, 2, 2, true>(p, tiles_b, splits, st)));
-  }
-  const int ncols = dw_cols > 0 ? dw_cols : p.RSC;
-  const int ldo = dw_ld > 0 ? dw_ld : p.RSC;
+int wgrad_reduce_to(const float* slab, int splits, int K, int RSC, int ncols, int ldo, float scale, float* const* dw,
+                    int nprob, hipStream_t st, u64* ts) {
+  DTC_CHECK_ARG(slab && dw && splits > 0 && K > 0 && RSC % 4 == 0 && ncols <= RSC && nprob >= 1 && nprob <= DTC_WG_BATCH,
+                "wgrad_reduce_to: bad args");
   WgOuts outs{};
-  outs.dw[0] = dw;
-  return launch_wgrad_reduce(slab, splits, s.K, p.RSC, ncols, ldo, scale, outs, 1, 0, st, ts);
-}
-
-int wgrad_reduce_to(const float* slab, int splits, int K, int RSC, int ncols, int ldo, float scale, float* dw,
-                    hipStream_t st, u64* ts) {
-  DTC_CHECK_ARG(slab && dw && splits > 0 && K > 0 && RSC % 4 == 0 && ncols <= RSC, "wgrad_reduce_to: bad args");
-  WgOuts outs{};
-  outs.dw[0] = dw;
-  return launch_wgrad_reduce(slab, splits, K, RSC, ncols, ldo, scale, outs, 1, 0, st, ts);
+  for (int i = 0; i < nprob; ++i) outs.dw[i] = dw[i];
+  return launch_wgrad_reduce(slab, splits, K, RSC, ncols, ldo, scale, outs, nprob, (size_t)splits * K * RSC, st, ts);
 }
 
 // two dense reductions in one launch: slab[splits][K][ld0] -> dw0 and (slab + stride)[splits][K][ld1] -> dw1
@@ -1102,24 +929,6 @@ int wgrad_reduce_pair(const float* slab, int splits, int K, int ld0, float* dw0,
   outs.dw[1] = dw1;
   outs.ld[1] = ld1;
   return launch_wgrad_reduce(slab, splits, K, ld0, ld0, ld0, scale, outs, 2, stride, st, ts);
-}
-
-size_t conv_wgrad_batch_slab_bytes(const ConvShape& s, int nprob) {
-  return (size_t)nprob * wgrad_halo_splits(s, nprob) * s.K * s.R * s.S * s.C * 4;
-}
-
-int conv_wgrad_batch(const ConvShape& s, int nprob, const u16* const* x, const u16* const* dy, float* const* dw,
-                     float scale, float* slab, size_t slab_bytes, hipStream_t st, u64* ts) {
-  const int hs = wgrad_halo_splits(s, nprob);
-  if (hs <= 0 || slab == nullptr || slab_bytes < conv_wgrad_batch_slab_bytes(s, nprob))
-    return set_error(DTC_EINVAL, "conv_wgrad_batch: no halo plan for %d problems or slab too small", nprob);
-  int splits = hs;
-  DTC_TRY(conv_wgrad_halo(s, nprob, x, dy, slab, hs, &splits, st, ts, dw, scale));
-  if (splits == 0) return 0;  // one split: the halo kernel wrote dw itself
-  const int RSC = s.R * s.S * s.C;
-  WgOuts outs{};
-  for (int i = 0; i < nprob; ++i) outs.dw[i] = dw[i];
-  return launch_wgrad_reduce(slab, splits, s.K, RSC, RSC, RSC, scale, outs, nprob, (size_t)splits * s.K * RSC, st, ts);
 }
 
 int splitk_reduce(const float* slab, int splits, int M, int Nc, u16* out, const u16* res, int64_t* stats,

@@ -5,7 +5,6 @@
 #include <stddef.h>
 #include <algorithm>
 #include "common.h"
-#include "bnb_epi.h"
 
 struct dtc_eval_record;  // include/dtc.h
 
@@ -84,12 +83,57 @@ struct ConvShape {
   int stride, pad;
 };
 enum { CONV_FWD = 0, CONV_DGRAD = 1, CONV_WGRAD = 2 };
-struct ConvPlan {
-  int bm, bn, splits, num_kt;
-  size_t slab_bytes;  // fp32 workspace the plan wants (0 = none)
-};
-ConvPlan plan_conv(const ConvShape& s, int mode);
+inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
+// ---- each kernel family's own planner (which family a conv runs on is conv_route's question)
+// Implicit GEMM (igemm.hip), every geometry: tile (64x64 / 64x256 / 128x128), split-K factor and reduction steps;
+// cls: a stride-2 DGRAD as four output-parity-class GEMMs in one launch (even H and W; no split-K)
+struct GemmPlan {
+  int bm, bn, splits, num_kt;
+  size_t slab_bytes;  // fp32 slab of `splits` partial outputs (FWD / DGRAD: 0 with one split)
+};
+bool dgrad_class_mode(const ConvShape& s);  // option dgrad_classes and the geometry
+GemmPlan igemm_plan(const ConvShape& s, int pass, bool cls);
+bool conv_c64_ok(const ConvShape& s);  // persistent 64-channel 3x3 stride-1 FWD / DGRAD (conv_c64.hip)
+// Halo-tiled 3x3 FWD / DGRAD, stride 1, and FWD stride 2 column-split (conv_halo.hip): configuration for the pass
+// (cfg -1: not applicable) and its split-K factor over the reduction chunks
+struct HaloPlan {
+  int cfg, split;
+  int gen = 0;  // 1: general tile geometry (rows of seg columns, 64-bit tile bases; conv_halo.hip)
+};
+HaloPlan conv_halo_plan(const ConvShape& s, int pass);
+size_t conv_halo_slab_bytes(const ConvShape& s, int pass, const HaloPlan& hp);  // fp32 split-K slab of the plan
+bool dgrad_s2_halo_ok(const ConvShape& s);  // stride-2 3x3 DGRAD as a halo-tiled sub-pixel conv (dgrad_s2.hip)
+// Halo-tiled 3x3 WGRAD (wgrad_halo.hip): the split count it would use (0: not applicable / disabled) for stride 1,
+// nprob (<= DTC_WG_BATCH) problems per launch, and for stride 2 (conv1 of a projection block, + its shortcut).
+constexpr int DTC_WG_BATCH = 4;
+int wgrad_halo_splits(const ConvShape& s, int nprob = 1);
+int wgrad_s2_splits(const ConvShape& s);
+size_t conv_wgrad_s2_slab_bytes(const ConvShape& s, int splits);  // 9 taps + the shortcut's [K][C] per split
+
+// ---- the router (conv_route.cpp): the one place that knows the families' order of precedence
+enum ConvKernel {  // GEMM_CLASSES: igemm's stride-2 DGRAD parity classes (take a compact residual / the fused shortcut)
+  CONV_K_GEMM, CONV_K_GEMM_CLASSES, CONV_K_C64, CONV_K_HALO, CONV_K_DGRAD_S2, CONV_K_WGRAD_HALO, CONV_K_WGRAD_S2
+};
+struct ConvRequest {  // what a launch branches on besides the shape
+  bool res = false;  // DGRAD: a residual is added
+  bool sc = false;   // the block's 1x1 stride-2 shortcut in the same launch (conv_fwd_sc / conv_dgrad_sc)
+  int dw_cols = 0, dw_ld = 0;  // WGRAD: a partial dw (0: whole rows)
+  int nprob = 1;               // WGRAD: problems per launch (conv_wgrad_batch)
+  size_t slab_bytes = SIZE_MAX;  // fp32 slab on hand (default: sizing -- whatever the route wants)
+};
+struct ConvRoute {
+  int kernel = CONV_K_GEMM;
+  GemmPlan gemm{};          // GEMM kernels: splits final for the slab on hand
+  HaloPlan halo{-1, 1};     // CONV_K_HALO: split 1 when the slab on hand is too small
+  int splits = 0;           // CONV_K_WGRAD_HALO / _S2
+  bool dw_whole = true;     // WGRAD: dw is written in whole rows (the halo kernels may write it themselves)
+  size_t slab_bytes = 0;    // fp32 slab the pass wants (0 = none): this route's and its GEMM fallback's
+  bool sc_ok = false;       // 3x3 stride 2: the pass has a shortcut-fused launch (with req.sc: this route is it)
+};
+ConvRoute conv_route(const ConvShape& s, int pass, const ConvRequest& req = ConvRequest{});
+
+// ---- launchers (conv_route.cpp): route, then the family's launch
 // y = conv(x, w) (bf16 NHWC out); optional BN statistics of the bf16 output into
 // stats (sum, sum of squares; exact fixed-point accumulators, DTC_STAT_WORDS(K) int64: common.h).
 // `ts` (optional, every conv launcher): a DTC_PROF_SLOT_U64 slot receiving the entry times of the
@@ -104,72 +148,59 @@ int conv_fwd(const ConvShape& s, const u16* x, const u16* w, u16* y, int64_t* st
 bool conv_fwd_sc_ok(const ConvShape& s, const ConvShape& sc);
 int conv_fwd_sc(const ConvShape& s, const ConvShape& sc, const u16* x, const u16* w, u16* y, int64_t* stats,
                 const u16* wsc, u16* ysc, int64_t* stats_sc, hipStream_t st, u64* ts = nullptr);
-// true when conv_dgrad(s) takes the stride-2 parity-class path (the one a compact residual needs)
-bool dgrad_class_ok(const ConvShape& s);
-// true when conv_dgrad_sc takes s (a projection block's 3x3 stride-2 conv1)
-bool conv_dgrad_sc_ok(const ConvShape& s);
-// stride-2 3x3 pad-1 dgrad as a halo-tiled sub-pixel convolution (dgrad_s2.hip), optionally + the 1x1 stride-2
-// shortcut's dgrad (dsc [N][H/2][W/2][K], wsc [K][C]) at the even / even pixels
-bool dgrad_s2_halo_ok(const ConvShape& s);
-int conv_dgrad_s2_halo(const ConvShape& s, const u16* dy, const u16* w, u16* dx, const u16* dsc, const u16* wsc,
-                       hipStream_t st, u64* ts = nullptr);
-// dx = dgrad(dy, w) + dgrad_1x1_s2(dsc, wsc) for a projection block's 3x3 stride-2 conv1 and its shortcut
-// in one parity-class launch (dsc [N][H/2][W/2][K], wsc [K][C])
-int conv_dgrad_sc(const ConvShape& s, const u16* dy, const u16* w, u16* dx, const u16* dsc, const u16* wsc,
-                  hipStream_t st, u64* ts = nullptr, const BnbArgs* bnb = nullptr);
 // dx = conv_transpose(dy, w) (+ res), bf16 NHWC.
-// bnb (optional): dx is the gradient of a post-ReLU BN output; store dz = dx * [bnb->ym > 0] instead
-// and accumulate the BN-backward sums (bn_bwd_reduce's work) -- in the epilogue where the kernel
-// supports it (conv_c64, conv_halo, split-K reduce), else by a bn_bwd_reduce pass after the conv.
 // dx may alias res (in place: each element is read and written by the same lane).
 // res_compact: res is [N][H/2][W/2][C] (a 1x1 stride-2 shortcut's dx at its only nonzero parity),
-// added at the (even, even) pixels only -- stride-2 parity-class dgrads.
+// added at the (even, even) pixels only -- needs the parity-class route (CONV_K_GEMM_CLASSES).
 int conv_dgrad(const ConvShape& s, const u16* dy, const u16* w, u16* dx, const u16* res, float* slab,
-               size_t slab_bytes, hipStream_t st, u64* ts = nullptr, const BnbArgs* bnb = nullptr,
-               int res_compact = 0, unsigned* tick = nullptr);
+               size_t slab_bytes, hipStream_t st, u64* ts = nullptr, int res_compact = 0, unsigned* tick = nullptr);
+// dx = dgrad(dy, w) + dgrad_1x1_s2(dsc, wsc) for a projection block's 3x3 stride-2 conv1 and its shortcut
+// in one launch (dsc [N][H/2][W/2][K], wsc [K][C]); needs sc_ok of the DGRAD route of s
+int conv_dgrad_sc(const ConvShape& s, const u16* dy, const u16* w, u16* dx, const u16* dsc, const u16* wsc,
+                  hipStream_t st, u64* ts = nullptr);
 // dw[k][0:dw_cols] (row stride dw_ld) = scale * sum_pixels dy (x) im2col(x); fp32
 int conv_wgrad(const ConvShape& s, const u16* x, const u16* dy, float* dw, int dw_cols, int dw_ld, float scale,
                float* slab, size_t slab_bytes, hipStream_t st, u64* ts = nullptr);
-// Halo-tiled WGRAD for 3x3 / stride 1 / pad 1 (wgrad_halo.hip): split count it would use for s
-// batched nprob at a time (0 = not applicable / disabled), and the launch writing
-// slab[nprob][used][K][9C] (reduce separately).
-constexpr int DTC_WG_BATCH = 4;
-int wgrad_halo_splits(const ConvShape& s, int nprob = 1);
-// dw (optional): when the launch uses ONE split its epilogue writes dw[i] = scale * sum directly (no
-// slab, no reduce; *used_splits = 0 tells the caller), else slab[nprob][used][K][9C] as above.
-// 3x3 stride-2 weight gradient (conv1 of a projection block) on the column-split halo kernel, and with
-// dsc != null the block's 1x1 stride-2 shortcut's (dw_sc[k][c] from dsc) in the same launch; split-K over
-// output pixels into slab ([splits][K][9C] then [splits][K][C]) + deterministic reduces.
-int wgrad_s2_splits(const ConvShape& s);  // 0: no plan (option wgrad_s2 off or geometry)
-size_t conv_wgrad_s2_slab_bytes(const ConvShape& s);
-int conv_wgrad_s2(const ConvShape& s, const u16* x, const u16* dy, const u16* dsc, float* dw, float* dw_sc,
-                  float scale, float* slab, size_t slab_bytes, hipStream_t st, u64* ts = nullptr);
-int conv_wgrad_halo(const ConvShape& s, int nprob, const u16* const* x, const u16* const* dy, float* slab, int splits,
-                    int* used_splits, hipStream_t st, u64* ts, float* const* dw = nullptr, float scale = 1.f);
-// nprob (<= DTC_WG_BATCH) independent weight gradients of one 3x3 stride-1 geometry in one halo
-// launch + one reduce launch: dw[i] = scale * wgrad(x[i], dy[i]). Returns DTC_EINVAL when the
-// geometry has no halo plan or the slab is too small (callers then issue them one by one).
-size_t conv_wgrad_batch_slab_bytes(const ConvShape& s, int nprob);
+// nprob (<= DTC_WG_BATCH) weight gradients of one 3x3 stride-1 geometry in one halo launch + one reduce launch: dw[i] =
+// scale * wgrad(x[i], dy[i]). DTC_EINVAL when there is no halo plan or the slab is too small (then: one by one).
 int conv_wgrad_batch(const ConvShape& s, int nprob, const u16* const* x, const u16* const* dy, float* const* dw,
                      float scale, float* slab, size_t slab_bytes, hipStream_t st, u64* ts = nullptr);
-// Halo-tiled 3x3 / stride 1 FWD and DGRAD (conv_halo.hip): configuration for the pass (-1: not
-// applicable), and the launch (FWD: stats optional; DGRAD: res optional).
-// Persistent 64-channel 3x3 stride-1 FWD / DGRAD (conv_c64.hip).
-bool conv_c64_ok(const ConvShape& s);
+
+// ---- the families' launches (called with the router's plan)
+// igemm.hip. FWD: wsc != null also computes the shortcut (ysc, stats_sc; one split). DGRAD: cls as planned; with cls,
+// res_compact or the fused shortcut (dsc, wsc). Split-K is reduced by splitk_reduce; WGRAD only writes its slab.
+int igemm_fwd(const ConvShape& s, const GemmPlan& pl, const u16* x, const u16* w, u16* y, int64_t* stats, float* slab,
+              const u16* wsc, u16* ysc, int64_t* stats_sc, hipStream_t st, u64* ts);
+int igemm_dgrad(const ConvShape& s, const GemmPlan& pl, bool cls, const u16* dy, const u16* w, u16* dx, const u16* res,
+                int res_compact, const u16* dsc, const u16* wsc, float* slab, hipStream_t st, u64* ts);
+int igemm_wgrad(const ConvShape& s, const GemmPlan& pl, const u16* x, const u16* dy, float* slab, hipStream_t st,
+                u64* ts);
 int conv_c64(const ConvShape& s, int mode, const u16* src, const u16* w, u16* out, const u16* res, int64_t* stats,
              hipStream_t st, u64* ts);
-struct HaloPlan {
-  int cfg, split;
-  int gen = 0;  // 1: general tile geometry (rows of seg columns, 64-bit tile bases; conv_halo.hip)
-};
-HaloPlan conv_halo_plan(const ConvShape& s, int mode);
-size_t conv_halo_slab_bytes(const ConvShape& s, int mode);  // fp32 split-K slab the plan needs
+// FWD: stats optional, wsc / out2 / stats2 the fused shortcut (stride 2); DGRAD: res optional
 int conv_halo(const ConvShape& s, int mode, const HaloPlan& hp, const u16* src, const u16* w, u16* out,
-              const u16* res, int64_t* stats, float* slab, size_t slab_bytes, hipStream_t st, u64* ts = nullptr,
+              const u16* res, int64_t* stats, float* slab, hipStream_t st, u64* ts = nullptr,
               const u16* wsc = nullptr, u16* out2 = nullptr, int64_t* stats2 = nullptr, unsigned* tick = nullptr);
+// optionally + the 1x1 stride-2 shortcut's dgrad (dsc [N][H/2][W/2][K], wsc [K][C]) at the even / even pixels
+int conv_dgrad_s2_halo(const ConvShape& s, const u16* dy, const u16* w, u16* dx, const u16* dsc, const u16* wsc,
+                       hipStream_t st, u64* ts = nullptr);
+// writes slab[nprob][used][K][9C] (reduce separately); dw (optional): when the launch uses ONE split its epilogue
+// writes dw[i] = scale * sum directly (no slab, no reduce; *used_splits = 0 tells the caller)
+int conv_wgrad_halo(const ConvShape& s, int nprob, const u16* const* x, const u16* const* dy, float* slab, int splits,
+                    int* used_splits, hipStream_t st, u64* ts, float* const* dw = nullptr, float scale = 1.f);
+// 3x3 stride-2 weight gradient on the column-split halo kernel, with dsc != null also the block's 1x1 stride-2
+// shortcut's (dw_sc[k][c]); split-K (wgrad_s2_splits) over output pixels into slab ([splits][K][9C | C]) + reduces.
+int conv_wgrad_s2(const ConvShape& s, int splits, const u16* x, const u16* dy, const u16* dsc, float* dw, float* dw_sc,
+                  float scale, float* slab, size_t slab_bytes, hipStream_t st, u64* ts = nullptr);
 // out = bf16(sum_s slab[s] (+ res)) (+ the BN statistics of out): the separate split-K reduction
 int splitk_reduce(const float* slab, int splits, int M, int Nc, u16* out, const u16* res, int64_t* stats,
                   hipStream_t st, u64* ts = nullptr);
+// dw[i][k][0:ncols] (row stride ldo) = scale * sum_s slab[i][s][k][0:RSC], i < nprob (igemm.hip's deterministic
+// reduce); _pair: two dense problems of row lengths ld0 >= ld1
+int wgrad_reduce_to(const float* slab, int splits, int K, int RSC, int ncols, int ldo, float scale, float* const* dw,
+                    int nprob, hipStream_t st, u64* ts = nullptr);
+int wgrad_reduce_pair(const float* slab, int splits, int K, int ld0, float* dw0, size_t stride, int ld1, float* dw1,
+                      float scale, hipStream_t st, u64* ts = nullptr);
 // per slot i of ts[n][DTC_PROF_SLOT_U64]: acc[i] += (max end - min start, 1) if stamped; cells reset
 int prof_accumulate(u64* ts, int n, u64* acc, hipStream_t st);
 
@@ -283,6 +314,19 @@ int bn_bwd_fin_apply(const float* dz, const float* x1, const BnBwdArgs& a1, floa
 
 // slot 0 <- the exact sum over the slots (lo carried into hi), the others zeroed (SyncBN's collective)
 int bn_fold_slots(int64_t* slots, int C, hipStream_t st);
+// The arguments of a BN-backward reduction as one bundle: dy is the gradient of a post-ReLU BN output
+// y = relu(bn(x1) [+ bn(x2)]) (reference src/*/net.py:41-44, 108); the passes below accumulate sum(dz) and
+// sum(dz * xhat) of dz = dy * [y > 0]. Behind a data gradient they run in place on the conv_dgrad's dx.
+struct BnbArgs {
+  const u16* ym = nullptr;      // post-ReLU activation y (mask source), or ...
+  const uint8_t* mb = nullptr;  // ... the forward's ReLU mask bits of y (bit e & 7 of byte e >> 3 for element e)
+  const u16* x1 = nullptr;      // input of the (first) BN: the conv output it normalised
+  const float *mean1 = nullptr, *invstd1 = nullptr;
+  int64_t* acc1 = nullptr;      // [SLOTS][2][C]: sum dz, sum dz * xhat
+  const u16* x2 = nullptr;      // second BN sharing dz (projection shortcut) or null
+  const float *mean2 = nullptr, *invstd2 = nullptr;
+  int64_t* acc2 = nullptr;
+};
 // backward: dz = dy * [y > 0] (mask optional); accumulates sum(dz), sum(dz*xhat1) [, sum(dz*xhat2)]
 int bn_bwd_reduce(const u16* dy, const u16* ymask, const u16* x1, const float* mean1, const float* invstd1,
                   int64_t* acc1, const u16* x2, const float* mean2, const float* invstd2, int64_t* acc2, u16* dz,
@@ -316,11 +360,6 @@ int stem_wgrad(const float* x, const u16* dy, float* dw27, float scale, int N, i
 // tile in LDS from (dy, mask bits, the conv output c) and the BN's slots (a: as bn_bwd_fin_apply's)
 int stem_wgrad_bn(const float* x, const u16* dy, const uint8_t* mbits, const u16* c, const BnBwdArgs& a, float* dw27,
                   float scale, int N, int H, int W, float* slab, size_t slab_bytes, hipStream_t st, u64* ts = nullptr);
-// grad[k][0:ncols] (row stride ldo) = scale * sum_s slab[s][k][0:RSC] (igemm.hip's deterministic reduce)
-int wgrad_reduce_to(const float* slab, int splits, int K, int RSC, int ncols, int ldo, float scale, float* dw,
-                    hipStream_t st, u64* ts = nullptr);
-int wgrad_reduce_pair(const float* slab, int splits, int K, int ld0, float* dw0, size_t stride, int ld1, float* dw1,
-                      float scale, hipStream_t st, u64* ts = nullptr);
 // feat[n][c] = bf16round(mean_hw act); logits[n][j] = feat . W[j] + b[j]
 int head_fwd(const u16* act, int N, int HW, int C, const u16* wfc, const float* bfc, int ncls, float* feat,
              float* logits, hipStream_t st);

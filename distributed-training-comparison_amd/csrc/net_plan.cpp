@@ -205,19 +205,23 @@ static void plan_workspace(Net& n, float bucket_cap_mb) {
   size_t slab = (size_t)64 * 64 * 4;
   auto consider = [&](const ConvShape& s) {
     for (int m = 0; m < 3; ++m)
-      slab = std::max(slab, n.f32 ? f32_conv_workspace(s, m) : plan_conv(s, m).slab_bytes);
+      slab = std::max(slab, n.f32 ? f32_conv_workspace(s, m) : conv_route(s, m).slab_bytes);
+  };
+  auto consider_batch = [&](const ConvShape& s) {  // a bucket's 3x3 stride-1 wgrads, 2..DTC_WG_BATCH per launch
+    ConvRequest rq;
+    for (rq.nprob = 2; rq.nprob <= DTC_WG_BATCH; ++rq.nprob)
+      if (const ConvRoute r = conv_route(s, CONV_WGRAD, rq); r.kernel == CONV_K_WGRAD_HALO)
+        slab = std::max(slab, r.slab_bytes);
   };
   consider(n.f32 ? f32_stem_shape(n) : n.stem.s);
   for (auto& b : n.blocks) {
     consider(b.c1.s);
     consider(b.c2.s);
     if (b.proj) consider(b.sc.s);
-    if (!n.f32)
-      for (int np = 2; np <= DTC_WG_BATCH; ++np) {
-        slab = std::max(slab, conv_wgrad_batch_slab_bytes(b.c1.s, np));
-        slab = std::max(slab, conv_wgrad_batch_slab_bytes(b.c2.s, np));
-      }
-    if (!n.f32 && b.proj) slab = std::max(slab, conv_wgrad_s2_slab_bytes(b.c1.s));  // conv1 + shortcut wgrad (wgrad_s2)
+    if (!n.f32) {  // (conv1 + shortcut in one wgrad_s2 launch: its slab is conv1's own WGRAD route's)
+      consider_batch(b.c1.s);
+      consider_batch(b.c2.s);
+    }
   }
   if (p.stem_direct) slab = std::max(slab, stem_wgrad_slab_bytes(M0));
   p.slab_bytes = slab;

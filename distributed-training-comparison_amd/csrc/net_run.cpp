@@ -509,7 +509,9 @@ static int wg_flush_forked(Net& n, WgQueue& q, float gs, float* slabw, hipStream
 static int wg_issue(Net& n, WgQueue& q, const ConvShape& s, const u16* x, const u16* dy, float* dw, float gs,
                     float* slabw, hipStream_t& sd, hipStream_t st = nullptr, bool lazy = false) {
   const int bmax = wgrad_batch_max();
-  if (bmax <= 1 || wgrad_halo_splits(s, 2) <= 0) {
+  ConvRequest two;
+  two.nprob = 2;
+  if (bmax <= 1 || conv_route(s, CONV_WGRAD, two).kernel != CONV_K_WGRAD_HALO) {  // no batched launch for s
     if (lazy) DTC_TRY(fork_side(n, st, &sd));
     PROF(2, conv_flops(s), conv_wgrad(s, x, dy, dw, 0, 0, gs, slabw, n.plan.slab_bytes, sd, ts));
     return 0;
@@ -662,8 +664,7 @@ static BnBwdArgs bwd_args(Net& n, BNL& b, int64_t count, float gs) {
 
 // BN-backward reduction of the BN(s) whose post-ReLU output is `y`: b1 over x1 and, sharing dz, b2 over x2 (the
 // projection shortcut's BN). `y` is the output itself or (bits) the forward's ReLU mask bits of it. The bundle
-// is what a dgrad epilogue takes (bnb_epi.h: the conv producing dy stores dz = dy * [y > 0] and accumulates the
-// sums) and what the reduction passes below take; BnbArgsF32 is its fp32-activation sibling.
+// (kernels.h) is what the reduction passes below take; BnbArgsF32 is its fp32-activation sibling.
 struct BnbArgsF32 {
   const float *ym = nullptr, *x1 = nullptr, *mean1 = nullptr, *invstd1 = nullptr;
   int64_t* acc1 = nullptr;
@@ -892,14 +893,16 @@ static int backward_body_mask(Net& n, const float* dlogits, float gs, const BwdC
     if (b.proj) DTC_TRY(cap(n, cp + ".ds", dsc, st));
     // the shortcut's dx at its stride-2 grid only (option sc_compact): the 1x1 stride-2 conv's dgrad
     // is zero at three of four parities; conv1's parity-class dgrad adds it at the fourth
-    const bool sc_cmp = b.proj && !n.capture && option_get(OPT_SC_COMPACT) != 0 && dgrad_class_ok(b.c1.s);
+    const ConvRequest with_res{/*res=*/true};
+    const ConvRoute dg1 = b.proj && !n.capture ? conv_route(b.c1.s, CONV_DGRAD, with_res) : ConvRoute{};
+    const bool sc_cmp = option_get(OPT_SC_COMPACT) != 0 && dg1.kernel == CONV_K_GEMM_CLASSES;
     const ConvShape sc_dg = sc_cmp ? ConvShape{b.sc.s.N, b.Hout, b.Wout, b.sc.s.C, b.sc.s.K, 1, 1, 1, 0} : b.sc.s;
     // option dgrad_scf: the shortcut's dgrad as extra reduction steps of conv1's class-(0, 0) dgrad (one launch)
-    const bool dscf = b.proj && !n.capture && conv_dgrad_sc_ok(b.c1.s);
+    const bool dscf = dg1.sc_ok;
     if (!lazy) DTC_TRY(fork_side(n, st, &sd));
     DTC_TRY(wg_issue(n, wq, b.c2.s, n.at<u16>(b.A1), dc2, n.gf(b.c2.pidx), gs, slabw, sd, st, lazy));
     PROF(1, conv_flops(b.c2.s),
-         conv_dgrad(b.c2.s, dc2, n.wbf(b.c2.pidx), G[4], nullptr, slab, p.slab_bytes, st, ts, nullptr, 0, n.tick(0)));
+         conv_dgrad(b.c2.s, dc2, n.wbf(b.c2.pidx), G[4], nullptr, slab, p.slab_bytes, st, ts, 0, n.tick(0)));
     DTC_TRY(cap(n, cp + ".da1", G[4], st));
     DTC_TRY(cap_masked(n, cp + ".dz1", G[4], b.MA1, M, b.Cout, st));
     DTC_TRY(bn_bwd_mask(n, r1, b.b1, G[4], nullptr, dc1, nullptr, nullptr, M, gs, st));
@@ -907,11 +910,14 @@ static int backward_body_mask(Net& n, const float* dlogits, float gs, const BwdC
     if (!lazy || b.proj) DTC_TRY(fork_side(n, st, &sd));  // (the shortcut's wgrad below launches)
     // option wgrad_s2: conv1 (3x3 stride 2) and the shortcut (1x1 stride 2) weight gradients in one
     // column-split halo launch (x read once; the shortcut is conv1's centre tap against dsc)
-    const bool wsc = b.proj && wgrad_s2_splits(b.c1.s) > 0 && p.slab_bytes >= conv_wgrad_s2_slab_bytes(b.c1.s) &&
-                     b.sc.s.R == 1 && b.sc.s.stride == 2 && b.sc.s.C == b.c1.s.C && b.sc.s.K == b.c1.s.K;
+    ConvRequest on_hand;
+    on_hand.slab_bytes = p.slab_bytes;
+    const ConvRoute wg1 = b.proj ? conv_route(b.c1.s, CONV_WGRAD, on_hand) : ConvRoute{};
+    const bool wsc = wg1.sc_ok && b.sc.s.R == 1 && b.sc.s.stride == 2 && b.sc.s.C == b.c1.s.C && b.sc.s.K == b.c1.s.K;
     if (wsc) {
       PROF(2, conv_flops(b.c1.s) + conv_flops(b.sc.s),
-           conv_wgrad_s2(b.c1.s, in, dc1, dsc, n.gf(b.c1.pidx), n.gf(b.sc.pidx), gs, slabw, p.slab_bytes, sd, ts));
+           conv_wgrad_s2(b.c1.s, wg1.splits, in, dc1, dsc, n.gf(b.c1.pidx), n.gf(b.sc.pidx), gs, slabw, p.slab_bytes, sd,
+                         ts));
     } else {
       DTC_TRY(wg_issue(n, wq, b.c1.s, in, dc1, n.gf(b.c1.pidx), gs, slabw, sd, st, lazy && !b.proj));
     }
@@ -924,15 +930,14 @@ static int backward_body_mask(Net& n, const float* dlogits, float gs, const BwdC
              conv_dgrad_sc(b.c1.s, dc1, n.wbf(b.c1.pidx), G[0], dsc, n.wbf(b.sc.pidx), st, ts));
       } else {
         PROF(1, conv_flops(b.sc.s),
-             conv_dgrad(sc_dg, dsc, n.wbf(b.sc.pidx), G[5], nullptr, slab, p.slab_bytes, st, ts, nullptr, 0, n.tick(0)));
+             conv_dgrad(sc_dg, dsc, n.wbf(b.sc.pidx), G[5], nullptr, slab, p.slab_bytes, st, ts, 0, n.tick(0)));
         PROF(1, conv_flops(b.c1.s),
-             conv_dgrad(b.c1.s, dc1, n.wbf(b.c1.pidx), G[0], G[5], slab, p.slab_bytes, st, ts, nullptr, sc_cmp ? 1 : 0,
-                        n.tick(0)));
+             conv_dgrad(b.c1.s, dc1, n.wbf(b.c1.pidx), G[0], G[5], slab, p.slab_bytes, st, ts, sc_cmp ? 1 : 0, n.tick(0)));
       }
       DTC_TRY(cap(n, cp + ".dxs", G[5], st));
     } else {  // residual = dz of this block's output (G[0], written by bn2's apply); dx over it in place
       PROF(1, conv_flops(b.c1.s),
-           conv_dgrad(b.c1.s, dc1, n.wbf(b.c1.pidx), G[0], G[0], slab, p.slab_bytes, st, ts, nullptr, 0, n.tick(0)));
+           conv_dgrad(b.c1.s, dc1, n.wbf(b.c1.pidx), G[0], G[0], slab, p.slab_bytes, st, ts, 0, n.tick(0)));
     }
     DTC_TRY(cap(n, cp + ".dx", G[0], st));
     if (bucket_fires(n, bi)) DTC_TRY(wg_flush_forked(n, wq, gs, slabw, sd, st));
@@ -974,7 +979,7 @@ static int backward_body_mask(Net& n, const float* dlogits, float gs, const BwdC
   return bwd_end(n, cx, st);
 }
 
-// bf16 without mask bits: the BN reductions read the post-ReLU outputs, in the producing dgrad's epilogue
+// bf16 without mask bits: the BN reductions read the post-ReLU outputs, right behind the producing dgrad
 static int backward_body(Net& n, const float* dlogits, float gs, const BwdCtx& cx, hipStream_t st) {
   if (n.f32) return backward_body_f32(n, dlogits, gs, cx, st);
   if (bn_mask_on(n)) return backward_body_mask(n, dlogits, gs, cx, st);
@@ -984,10 +989,10 @@ static int backward_body(Net& n, const float* dlogits, float gs, const BwdCtx& c
   float* slab = n.at<float>(p.SLAB);
   float* slabw = n.at<float>(p.SLABW);
   hipStream_t sd = st;  // weight-gradient stream
-  // fuse: the dgrad producing a BN output's gradient also does that BN's backward reduction
-  // (captures keep the unfused order: they record dy and dz separately)
+  // fuse: the dgrad producing a BN output's gradient is followed at once by that BN's backward reduction, in
+  // place on dx (captures keep the unfused order: they record dy and dz separately)
   const bool fuse = !n.capture;
-  bool dz_ready = false;  // G[0] already holds the next BN's dz (the previous dgrad's fused epilogue)
+  bool dz_ready = false;  // G[0] already holds the next BN's dz (reduced in place behind the previous dgrad)
   WgQueue wq;
   for (int bi = (int)n.blocks.size() - 1; bi >= 0; --bi) {
     BlockL& b = n.blocks[bi];
@@ -1012,30 +1017,27 @@ static int backward_body(Net& n, const float* dlogits, float gs, const BwdCtx& c
     // conv2: dW2 (side stream) and da1
     DTC_TRY(fork_side(n, st, &sd));
     DTC_TRY(wg_issue(n, wq, b.c2.s, n.at<u16>(b.A1), dc2, n.gf(b.c2.pidx), gs, slabw, sd));
-    // a1 = relu(bn1(c1)): da1 -> dz1 (fused into the dgrad, or a separate reduction)
-    const BnbArgs bz = bnb_of(n, b.A1, b.C1, b.b1);
-    PROF(1, conv_flops(b.c2.s),
-         conv_dgrad(b.c2.s, dc2, n.wbf(b.c2.pidx), G[4], nullptr, slab, p.slab_bytes, st, ts, fuse ? &bz : nullptr));
-    if (!fuse) {
-      DTC_TRY(cap(n, cp + ".da1", G[4], st));
-      DTC_TRY(bn_reduce(bz, G[4], G[4], M, b.Cout, st));
-    }
+    // a1 = relu(bn1(c1)): da1 -> dz1 in place
+    PROF(1, conv_flops(b.c2.s), conv_dgrad(b.c2.s, dc2, n.wbf(b.c2.pidx), G[4], nullptr, slab, p.slab_bytes, st, ts));
+    if (!fuse) DTC_TRY(cap(n, cp + ".da1", G[4], st));
+    DTC_TRY(bn_reduce(bnb_of(n, b.A1, b.C1, b.b1), G[4], G[4], M, b.Cout, st));
     DTC_TRY(cap(n, cp + ".dz1", G[4], st));
     DTC_TRY(bn_bwd_coef_apply(n, b.b1, G[4], n.at<u16>(b.C1), dc1, nullptr, nullptr, nullptr, M, gs, st));
     DTC_TRY(cap(n, cp + ".dc1", dc1, st));
     // conv1 (+ shortcut): weight grads (side stream), then the block-input gradient with the residual fused
     DTC_TRY(fork_side(n, st, &sd));
     DTC_TRY(wg_issue(n, wq, b.c1.s, in, dc1, n.gf(b.c1.pidx), gs, slabw, sd));
-    // the block input's gradient feeds the previous block's bn2 (+ its projection BN) or the stem BN
-    const BnbArgs bp = bi > 0 ? bnb_out(n, n.blocks[bi - 1]) : bnb_of(n, p.A0, p.C0, n.bn0);
-    const BnbArgs* bpp = fuse ? &bp : nullptr;
     if (b.proj) {
       PROF(2, conv_flops(b.sc.s), conv_wgrad(b.sc.s, in, dsc, n.gf(b.sc.pidx), 0, 0, gs, slabw, p.slab_bytes, sd, ts));
       PROF(1, conv_flops(b.sc.s), conv_dgrad(b.sc.s, dsc, n.wbf(b.sc.pidx), G[5], nullptr, slab, p.slab_bytes, st, ts));
-      PROF(1, conv_flops(b.c1.s), conv_dgrad(b.c1.s, dc1, n.wbf(b.c1.pidx), G[0], G[5], slab, p.slab_bytes, st, ts, bpp));
-    } else {  // fused: dz2 is G[0] and the dgrad updates it in place (residual read, dz written per element)
-      PROF(1, conv_flops(b.c1.s), conv_dgrad(b.c1.s, dc1, n.wbf(b.c1.pidx), G[0], dz2, slab, p.slab_bytes, st, ts, bpp));
+      PROF(1, conv_flops(b.c1.s), conv_dgrad(b.c1.s, dc1, n.wbf(b.c1.pidx), G[0], G[5], slab, p.slab_bytes, st, ts));
+    } else {  // fused: dz2 is G[0] and the dgrad updates it in place (residual read, dx written per element)
+      PROF(1, conv_flops(b.c1.s), conv_dgrad(b.c1.s, dc1, n.wbf(b.c1.pidx), G[0], dz2, slab, p.slab_bytes, st, ts));
     }
+    // the block input's gradient feeds the previous block's bn2 (+ its projection BN) or the stem BN
+    if (fuse)
+      DTC_TRY(bn_reduce(bi > 0 ? bnb_out(n, n.blocks[bi - 1]) : bnb_of(n, p.A0, p.C0, n.bn0), G[0], G[0],
+                        (int64_t)b.c1.s.N * b.c1.s.H * b.c1.s.W, b.c1.s.C, st));
     dz_ready = fuse;
     if (b.proj) DTC_TRY(cap(n, cp + ".dxs", G[5], st));
     DTC_TRY(cap(n, cp + ".dx", G[0], st));

@@ -388,7 +388,7 @@ int stem_wgrad(const float* x, const u16* dy, float* dw27, float scale, int N, i
   DTC_CHECK_ARG(M + 256 < (1ll << 31), "stem_wgrad: more than 2^31 pixels");
   DTC_KLAUNCH(stem_wgrad_kernel, dim3(nwg), dim3(256), 0, st, x, dy, slab, stem_geom(N, H, W), tiles, ts);
   DTC_LAUNCH_CHECK();
-  return wgrad_reduce_to(slab, nwg, 64, 32, 27, 27, scale, dw27, st, ts);
+  return wgrad_reduce_to(slab, nwg, 64, 32, 27, 27, scale, &dw27, 1, st, ts);
 }
 
 
@@ -517,7 +517,7 @@ int stem_wgrad_bn(const float* x, const u16* dy, const uint8_t* mbits, const u16
   DTC_KLAUNCH(stem_wgrad_bn_kernel<STEM_BN_CAP>, dim3(nwg), dim3(256), 0, st, x, dy, mbits, c, a, slab,
                      stem_geom(N, H, W), tiles, ts);
   DTC_LAUNCH_CHECK();
-  return wgrad_reduce_to(slab, nwg, 64, 32, 27, 27, scale, dw27, st, ts);
+  return wgrad_reduce_to(slab, nwg, 64, 32, 27, 27, scale, &dw27, 1, st, ts);
 }
 
 }  // namespace dtc

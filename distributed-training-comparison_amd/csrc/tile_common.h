@@ -1,10 +1,25 @@
-// Device helpers shared by the implicit-GEMM kernels (igemm.hip, wgrad_halo.hip): LDS-DMA
-// loaders, the LDS swizzles, MFMA fragment readers and the call-timing stamps.
+// Shared by the conv kernels: the host-side tile geometry rules of the halo planners, and (HIP translation
+// units only) the device helpers -- LDS-DMA loaders, the LDS swizzles, MFMA fragment readers and the
+// call-timing stamps.
 #pragma once
 #include "common.h"
+#include "kernels.h"
 
 namespace dtc {
 
+// ------------------------------------------------------------------ host: the halo planners' tile geometry
+// the shape every halo kernel tiles: 3x3, stride st, pad 1, whole 64-channel chunks on both sides
+inline bool conv3x3_ok(const ConvShape& s, int st) {
+  return s.R == 3 && s.S == 3 && s.stride == st && s.pad == 1 && s.C % 64 == 0 && s.K % 64 == 0;
+}
+// general geometries, the piece of a w-pixel row per tile row: the row up to 64 pixels, else a dividing segment (or 0)
+inline int row_segment(int w) { return w <= 64 ? w : w % 64 == 0 ? 64 : w % 56 == 0 ? 56 : w % 32 == 0 ? 32 : 0; }
+// column-split stride-2 halo: LDS row pitch for wo output columns, 2 (wo + 1) [+ 2 where 2 * pitch must be
+// 8 mod 16 rows for the tr reads of a 64-pixel step spanning output rows]
+inline int s2_pitch(int wo) { return 2 * (wo + 1) + ((wo % 16) == 8 ? 2 : 0); }
+
+#ifdef __HIP__
+// ------------------------------------------------------------------ device
 // LDS-DMA (16 B per lane, lane-linear LDS destination at a wave-uniform base) is issued through
 // inline asm on purpose. With the builtins, hipcc treats the DMA as a pending write to LDS and
 // emits `s_waitcnt vmcnt(0)` before the next ds_read of ANY LDS buffer, i.e. it drains the
@@ -66,6 +81,12 @@ __device__ __forceinline__ void phase_mark(u64* buf, int k) {
 __device__ __forceinline__ void phase_mark(u64*, int) {}
 #endif
 
+// Halo LDS swizzle (conv_halo.hip, conv_c64.hip): 16-B chunk c of halo row r is stored at chunk c ^ hswz(r).
+// Every 8 B-fragment lanes that share a reduction chunk read 8 halo rows that are distinct mod 8 (the per-lane
+// pixel order of those kernels guarantees it for W = 4 and 8 too), so (row parity, chunk ^ hswz) spreads them
+// over 8 different 16-B bank slots, and the chunk pair (q, q+1) read by one ds_read_b128 lane group lands on
+// even / odd slots: conflict-free for EVERY tap shift (rowswz is only for aligned rows).
+__device__ __forceinline__ int hswz(int r) { return ((r >> 1) & 3) << 1; }
 __device__ __forceinline__ int rowswz(int row) { return (row >> 1) & 7; }
 __device__ __forceinline__ int trswz(int row) { return (((row >> 1) & 1) << 1) | (((row >> 3) & 1) << 2); }
 
@@ -103,5 +124,6 @@ __device__ __forceinline__ bf16x8 frag_tr(const char* region, int cb, int ks, in
   bf16x4_t t1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_v4*)(base + kr1 * 128 + ((unit ^ f1) << 3)));
   return __builtin_shufflevector(t0, t1, 0, 1, 2, 3, 4, 5, 6, 7);
 }
+#endif  // __HIP__
 
 }  // namespace dtc

@@ -400,7 +400,7 @@ struct WgGeom {
   int64_t nsteps = 0;
 };
 static bool wg_geometry(const ConvShape& s, WgGeom& g) {
-  if (!(s.R == 3 && s.S == 3 && s.stride == 1 && s.pad == 1 && s.C % 64 == 0 && s.K % 64 == 0)) return false;
+  if (!conv3x3_ok(s, 1)) return false;
   const int hw = s.H * s.W;
   if (s.W <= 64 && 64 % s.W == 0 && (hw % 64 == 0 || 64 % hw == 0)) {
     g.gen = 0;
@@ -420,15 +420,10 @@ static bool wg_geometry(const ConvShape& s, WgGeom& g) {
   if (option_get(OPT_WGRAD_GEN) == 0) return false;
   g = WgGeom{};
   g.gen = 1;
-  if (s.W <= 64) {
-    g.seg = s.W;
-    g.rs = 64 / s.W;
-    if (s.H % g.rs != 0) return false;
-  } else {
-    g.seg = s.W % 64 == 0 ? 64 : s.W % 56 == 0 ? 56 : s.W % 32 == 0 ? 32 : 0;
-    if (g.seg == 0) return false;
-    g.rs = 1;
-  }
+  g.seg = row_segment(s.W);
+  if (g.seg == 0) return false;
+  g.rs = s.W <= 64 ? 64 / s.W : 1;
+  if (s.H % g.rs != 0) return false;
   g.spr = s.W / g.seg;
   g.spimg = (s.H / g.rs) * g.spr;
   g.hb = g.nh = (g.rs + 2) * (g.seg + 2);
@@ -460,7 +455,6 @@ int conv_wgrad_halo(const ConvShape& s, int nprob, const u16* const* x, const u1
   WgGeom g;
   DTC_CHECK_ARG(wg_geometry(s, g) && splits > 0 && nprob >= 1 && nprob <= DTC_WG_BATCH,
                 "wgrad_halo: unsupported geometry");
-  const int rs = g.rs, imgs = g.imgs;
   HaloParams p{};
   for (int i = 0; i < nprob; ++i) {
     p.xs[i] = x[i];
@@ -473,10 +467,10 @@ int conv_wgrad_halo(const ConvShape& s, int nprob, const u16* const* x, const u1
   p.fd_w = make_fastdiv(s.W);
   p.nsteps = (int)g.nsteps;
   p.steps_per_split = (p.nsteps + splits - 1) / splits;
-  p.rs = rs;
+  p.rs = g.rs;
   p.hb = g.hb;
   p.nh = g.nh;
-  p.spi = rs * s.W;
+  p.spi = g.rs * s.W;
   p.pitch = (g.gen ? g.seg : s.W) + 2;
   p.ho = s.H;
   p.wo = s.W;
@@ -488,7 +482,6 @@ int conv_wgrad_halo(const ConvShape& s, int nprob, const u16* const* x, const u1
     p.fd_seg = make_fastdiv(g.seg);
     p.fd_seg2 = make_fastdiv(p.pitch);
   }
-  (void)imgs;
   p.ts = ts;
   p.xcd = option_get(OPT_WGRAD_XCD);
   p.trim = option_get(OPT_WGRAD_TRIM);
@@ -517,14 +510,10 @@ int conv_wgrad_halo(const ConvShape& s, int nprob, const u16* const* x, const u1
 
 // ---------------------------------------------------------------- stride 2 (+ shortcut)
 // conv1 of a projection block (3x3, stride 2, pad 1) and, optionally, its 1x1 stride-2 shortcut: one
-// halo launch over the OUTPUT pixels, the x halo column-split (conv_halo.hip's s2 layout: row pitch
-// 2 (Wo + 1) [+2 where 2 * pitch must be 8 mod 16 rows for the tr reads of a 64-pixel step spanning
-// output rows]); 9 taps + the shortcut from one x halo per step instead of one im2col gather per tap.
-static int s2_pitch_w(int wo) { return 2 * (wo + 1) + ((wo % 16) == 8 ? 2 : 0); }
+// halo launch over the OUTPUT pixels, the x halo column-split (conv_halo.hip's s2 layout, row pitch s2_pitch);
+// 9 taps + the shortcut from one x halo per step instead of one im2col gather per tap.
 static bool halo_geometry_s2(const ConvShape& s, int& rs, int& imgs, int& pitch, int& hb, int& nh) {
-  if (!(s.R == 3 && s.S == 3 && s.stride == 2 && s.pad == 1 && s.C % 64 == 0 && s.K % 64 == 0 && s.H % 2 == 0 &&
-        s.W % 2 == 0))
-    return false;
+  if (!conv3x3_ok(s, 2) || s.H % 2 || s.W % 2) return false;
   const int ho = s.H / 2, wo = s.W / 2, hw = ho * wo;
   if (wo > 64 || 64 % wo != 0) return false;
   if (hw % 64 == 0) {
@@ -536,7 +525,7 @@ static bool halo_geometry_s2(const ConvShape& s, int& rs, int& imgs, int& pitch,
   } else {
     return false;
   }
-  pitch = s2_pitch_w(wo);
+  pitch = s2_pitch(wo);
   hb = (2 * rs + 1) * pitch;
   nh = imgs * hb;
   return nh <= 384 && ((int64_t)s.N * hw) % 64 == 0 && (uint64_t)s.N * s.H * s.W * s.C * 2 < (1ull << 31) &&
@@ -551,15 +540,13 @@ struct WgGeomS2 {
   int64_t nsteps = 0;
 };
 static bool wg_geometry_s2_gen(const ConvShape& s, WgGeomS2& g) {
-  if (!(s.R == 3 && s.S == 3 && s.stride == 2 && s.pad == 1 && s.C % 64 == 0 && s.K % 64 == 0 && s.H % 2 == 0 &&
-        s.W % 2 == 0))
-    return false;
+  if (!conv3x3_ok(s, 2) || s.H % 2 || s.W % 2) return false;
   const int ho = s.H / 2, wo = s.W / 2;
-  g.seg = wo <= 64 ? wo : wo % 64 == 0 ? 64 : wo % 56 == 0 ? 56 : wo % 32 == 0 ? 32 : 0;
+  g.seg = row_segment(wo);
   if (g.seg == 0) return false;
   g.rs = 64 / g.seg;
   while (g.rs > 1 && ho % g.rs != 0) --g.rs;
-  g.pitch = s2_pitch_w(g.seg);
+  g.pitch = s2_pitch(g.seg);
   g.nh = (2 * g.rs + 1) * g.pitch;
   g.spr = wo / g.seg;
   g.spimg = (ho / g.rs) * g.spr;
@@ -595,15 +582,13 @@ int wgrad_s2_splits(const ConvShape& s) {
   // batch 32 -0.2 / 0.0 / -0.8%, batch 64 +1.5 / +1.5 / +1.2%: profiles/r06bg_*; kept at 4)
 }
 
-size_t conv_wgrad_s2_slab_bytes(const ConvShape& s) {
-  const int sp = wgrad_s2_splits(s);
-  return sp > 0 ? (size_t)sp * s.K * 10 * s.C * 4 : 0;  // 9 taps + the shortcut's [K][C]
+size_t conv_wgrad_s2_slab_bytes(const ConvShape& s, int splits) {
+  return (size_t)splits * s.K * 10 * s.C * 4;  // 9 taps + the shortcut's [K][C]
 }
 
-int conv_wgrad_s2(const ConvShape& s, const u16* x, const u16* dy, const u16* dsc, float* dw, float* dw_sc,
+int conv_wgrad_s2(const ConvShape& s, int splits, const u16* x, const u16* dy, const u16* dsc, float* dw, float* dw_sc,
                   float scale, float* slab, size_t slab_bytes, hipStream_t st, u64* ts) {
   int rs = 0, imgs = 0, pitch = 0, hb = 0, nh = 0;
-  const int splits = wgrad_s2_splits(s);
   bool gen = false;
   int64_t gsteps = 0;
   DTC_CHECK_ARG(splits > 0 && wgrad_s2_plan(s, gen, gsteps) && x && dy && dw && (!dsc || dw_sc),
@@ -670,7 +655,7 @@ int conv_wgrad_s2(const ConvShape& s, const u16* x, const u16* dy, const u16* ds
   if (p.direct) return 0;  // dw (and dw_sc) written by the halo kernel
   // the taps' and the shortcut's slabs in one reduce launch (round 6: one launch per projection block fewer)
   if (dsc) return wgrad_reduce_pair(slab, used, s.K, 9 * s.C, dw, p.slab_stride, s.C, dw_sc, scale, st, ts);
-  return wgrad_reduce_to(slab, used, s.K, 9 * s.C, 9 * s.C, 9 * s.C, scale, dw, st, ts);
+  return wgrad_reduce_to(slab, used, s.K, 9 * s.C, 9 * s.C, 9 * s.C, scale, &dw, 1, st, ts);
 }
 
 }  // namespace dtc

@@ -84,8 +84,8 @@ int dtc_conv2d_dgrad(const dtc_conv_desc* d, const uint16_t* dy, const uint16_t*
                      const uint16_t* res, void* ws, size_t ws_bytes, void* stream);
 /* The same dgrad when dx is the gradient of a post-ReLU BatchNorm output y = relu(bn(x1) [+ bn2(x2)])
  * (net.py:41-44, 108): stores dz = bf16(dx) * [ymask > 0] in dx and ADDS the BN-backward sums into
- * acc1 (and acc2 if x2) exactly as dtc_bn_bwd_reduce would on that dz -- in the conv's epilogue where
- * the kernel has one (3x3 stride 1 and split-K paths), else as a second pass. dx may alias res. */
+ * acc1 (and acc2 if x2) exactly as dtc_bn_bwd_reduce does on that dz: the dgrad launch(es), then that
+ * reduction in place on dx. dx may alias res. */
 int dtc_conv2d_dgrad_bn(const dtc_conv_desc* d, const uint16_t* dy, const uint16_t* w, uint16_t* dx,
                         const uint16_t* res, const uint16_t* ymask, const uint16_t* x1, const float* mean1,
                         const float* invstd1, int64_t* acc1, const uint16_t* x2, const float* mean2,

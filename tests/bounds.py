@@ -65,7 +65,7 @@ U = 2.0 ** -24
 HB = 2.0 ** -8
 # 2 = the plain dot-product bound L*U*S doubled. The doubling covers (a) an accumulator that truncates where
 # round-to-nearest was assumed (error per add up to 2U), (b) the split-K partial adds (at most num_kt <= L/16
-# of them, plan_conv) and (c) the residual add. Raise it only with a derivation from how the accumulation is
+# of them, igemm_plan) and (c) the residual add. Raise it only with a derivation from how the accumulation is
 # performed, written here; never to fit an observed ratio.
 CONV_FACTOR = 2.0
 

@@ -9,13 +9,14 @@ even H. The shapes here are those layers (and the stride-1 convs of the odd maps
 oracle/ops.py: the norm criteria of tests/test_gpu_ops.py with the element-wise bounds of tests/bounds.py beside
 them, the weight gradients' included (wgrad_tol). Inputs are bf16-representable.
 
-Paths, read from the plan code under distributed-training-comparison_amd/csrc/ (plan_conv / conv_fwd / conv_dgrad /
-conv_wgrad in igemm.hip, conv_halo_plan in conv_halo.hip, conv_c64_ok in conv_c64.hip, wg_geometry and wgrad_s2_plan in
-wgrad_halo.hip, s2d_geometry in dgrad_s2.hip) at the default options; listed, not asserted:
+Paths at the default options: conv_route in distributed-training-comparison_amd/csrc/conv_route.cpp is the one
+function that picks the kernel of a (shape, pass), from each kernel's own predicate (DESIGN.md §7m has the order);
+tools/conv_digest.py prints the kernels every shape here launches, under the forced options below too. Listed, not
+asserted:
 
 Stride 2, 3x3 / pad 1 and 1x1 / pad 0 alike -- every case is refused by every stride-2 tiled plan (odd H or W; the
 1x1 has none) and runs the implicit GEMM: forward at P x Q = ceil(H / 2) x ceil(W / 2), the masked (non-class)
-dgrad whatever dgrad_classes says, the generic wgrad. plan_conv's tiles and split-K factors (fwd | dgrad | wgrad;
+dgrad whatever dgrad_classes says, the generic wgrad. igemm_plan's tiles and split-K factors (fwd | dgrad | wgrad;
 64 / 128: 64x64 / 128x128 tiles, xS: S splits, every wgrad one split of ceil(N P Q / 64) pixel steps) and the wgrad
 loader (fast: a 64-pixel step is whole output images; slow: per-pixel decode):
 
