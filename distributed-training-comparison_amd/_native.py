@@ -160,6 +160,8 @@ _SIGS = {
                                 vp, vp]),
     "dtc_cifar_augment_mix": (i32, [vp, vp, i64, vp, vp, vp, i32, i32, i32, i32, C.POINTER(f32), C.POINTER(f32), vp,
                                     i32, vp, vp, vp, vp, vp, vp, vp]),
+    "dtc_cifar_augment_policy": (i32, [vp, vp, i64, vp, vp, vp, i32, i32, i32, i32, C.POINTER(f32), C.POINTER(f32),
+                                       vp, vp, i32, vp, vp, vp, vp, vp, vp]),
     "dtc_comm_unique_id_bytes": (sz, []),
     "dtc_comm_get_unique_id": (i32, [vp]),
     "dtc_comm_init": (i32, [C.POINTER(vp), i32, i32, vp, i32]),

@@ -579,6 +579,14 @@ int dtc_cifar_augment_mix(const uint8_t* images, const int64_t* targets, int64_t
                                  lam, box, out, labels, labels_b, status, S(stream));)
 }
 
+int dtc_cifar_augment_policy(const uint8_t* images, const int64_t* targets, int64_t n_images, const int64_t* index,
+                             const uint8_t* crop, const uint8_t* flip, int n, int h, int w, int pad, const float* mean,
+                             const float* stdv, const uint8_t* ops, const float* args, int n_ops, const uint8_t* erase,
+                             float* out, uint8_t* out_u8, int64_t* labels, int* status, void* stream) {
+  GUARD(return cifar_augment_policy(images, targets, n_images, index, crop, flip, n, h, w, pad, mean, stdv, ops, args,
+                                    n_ops, erase, out, out_u8, labels, status, S(stream));)
+}
+
 size_t dtc_comm_unique_id_bytes(void) { return comm_unique_id_bytes(); }
 int dtc_comm_get_unique_id(void* out) { GUARD(return comm_get_unique_id(out);) }
 int dtc_comm_init(dtc_comm** out, int rank, int world, const void* id, int device) {

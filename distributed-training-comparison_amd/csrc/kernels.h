@@ -537,5 +537,12 @@ int cifar_augment_mix(const uint8_t* images, const int64_t* targets, int64_t n_i
                       const uint8_t* crop, const uint8_t* flip, int n, int h, int w, int pad, const float* mean,
                       const float* stdv, const int32_t* partner, int mode, const float* lam, const uint8_t* box,
                       float* out, int64_t* labels, int64_t* labels_b, int* status, hipStream_t st);
+// the plain launch with a chain of n_ops policy ops per image (ops [n][n_ops], args [n][n_ops][6]; RandAugment /
+// TrivialAugmentWide, augment_policy.hip) between the flip and Normalize, and an optional erase box [n][4] zeroed
+// after it (RandomErasing); writes out (fp32 NCHW) or out_u8 (uint8 NHWC, before Normalize), exactly one of them
+int cifar_augment_policy(const uint8_t* images, const int64_t* targets, int64_t n_images, const int64_t* index,
+                         const uint8_t* crop, const uint8_t* flip, int n, int h, int w, int pad, const float* mean,
+                         const float* stdv, const uint8_t* ops, const float* args, int n_ops, const uint8_t* erase,
+                         float* out, uint8_t* out_u8, int64_t* labels, int* status, hipStream_t st);
 
 }  // namespace dtc

@@ -224,6 +224,120 @@ def mix_params(n_batches: int, batch: int, h: int, w: int, mixup_alpha: float = 
     return MixParams(mode, np.repeat(lam1[:, None], batch, 1), np.repeat(box1[:, None, :], batch, 1), draw)
 
 
+class PolicyParams(NamedTuple):
+    """One epoch's augmentation-policy draws (host arrays, see policy_params)."""
+
+    ops: np.ndarray   # uint8 [n_batches, batch, N]: kernel op codes (include/dtc.h, dtc_cifar_augment_policy)
+    args: np.ndarray  # fp32 [n_batches, batch, N, 6]: each op's g0..g5
+    name: np.ndarray  # uint8 [n_batches, batch, N]: index into POLICY_OPS, the named op each entry was drawn as
+
+
+POLICIES = ("none", "randaugment", "trivialwide")
+# torchvision's RandAugment / TrivialAugmentWide op space, in its order
+POLICY_OPS = ("Identity", "ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate", "Brightness", "Color", "Contrast",
+              "Sharpness", "Posterize", "Solarize", "AutoContrast", "Equalize")
+_POLICY_BINS = 31
+_KERNEL_OP = np.array([0, 1, 1, 1, 1, 1, 2, 3, 4, 5, 6, 7, 8, 9], np.uint8)
+
+
+def _policy_magnitudes(policy: str, h: int, w: int) -> np.ndarray:
+    """fp64 [14, 31]: the magnitude of each named op at each bin (torchvision's _augmentation_space tables)."""
+    nb = _POLICY_BINS
+    lin = lambda a, b: np.linspace(a, b, nb)
+    zero = np.zeros(nb)
+    if policy == "randaugment":
+        shear, tx, ty, rot, blend = lin(0, 0.3), lin(0, 150.0 / 331.0 * w), lin(0, 150.0 / 331.0 * h), lin(0, 30), \
+            lin(0, 0.9)
+        bits = 8 - np.round(np.arange(nb) / ((nb - 1) / 4))
+    else:
+        shear, tx, ty, rot, blend = lin(0, 0.99), lin(0, 32), lin(0, 32), lin(0, 135), lin(0, 0.99)
+        bits = 8 - np.round(np.arange(nb) / ((nb - 1) / 6))
+    return np.stack([zero, shear, shear, np.trunc(tx), np.trunc(ty), rot, blend, blend, blend, blend, bits,
+                     lin(255, 0), zero, zero])
+
+
+def policy_params(n_batches: int, batch: int, h: int, w: int, policy: str = "randaugment", num_ops: int = 2,
+                  magnitude: int = 9, rng: Optional[np.random.Generator] = None) -> PolicyParams:
+    """RandAugment / TrivialAugmentWide draws of a whole epoch, per sample, on the host (torchvision's rules over
+    its 14 named ops, POLICY_OPS): ``randaugment`` draws `num_ops` ops uniformly, all at bin `magnitude` of 31;
+    ``trivialwide`` draws one op and a uniform bin from its wider ranges. The geometric ops and the four blends
+    are negated with probability 1/2. Each named op becomes a kernel op and six args (float64, then rounded to
+    fp32): the shears, translations (whole pixels) and the rotation an Affine matrix, a blend of signed magnitude
+    m the pair (1 + m, -m), Posterize its bit mask, Solarize its threshold."""
+    if policy not in POLICIES[1:]:
+        raise ValueError(f"policy_params: policy must be one of {POLICIES[1:]}, got {policy!r}")
+    if not 1 <= int(num_ops) <= 4 or not 0 <= int(magnitude) < _POLICY_BINS:
+        raise ValueError("policy_params: num_ops must be in [1, 4] and magnitude in [0, 30]")
+    rng = rng if rng is not None else np.random.default_rng()
+    shape = (int(n_batches), int(batch), int(num_ops) if policy == "randaugment" else 1)
+    name = rng.integers(0, len(POLICY_OPS), shape)
+    bins = rng.integers(0, _POLICY_BINS, shape)
+    neg = rng.random(shape) < 0.5
+    if policy == "randaugment":
+        bins = np.full(shape, int(magnitude))
+    m = _policy_magnitudes(policy, h, w)[name, bins]
+    m = np.where(neg & (name >= 1) & (name <= 9), -m, m)
+    args = np.zeros(shape + (6,), np.float64)
+    affine = (name >= 1) & (name <= 5)
+    args[..., 0] = np.where(affine, 1.0, args[..., 0])
+    args[..., 4] = np.where(affine, 1.0, args[..., 4])
+    args[..., 1] = np.where(name == 1, m, args[..., 1])   # ShearX
+    args[..., 3] = np.where(name == 2, m, args[..., 3])   # ShearY
+    args[..., 2] = np.where(name == 3, -m, args[..., 2])  # TranslateX
+    args[..., 5] = np.where(name == 4, -m, args[..., 5])  # TranslateY
+    rot = name == 5
+    th = np.deg2rad(np.where(rot, m, 0.0))
+    args[..., 0] = np.where(rot, np.cos(th), args[..., 0])
+    args[..., 1] = np.where(rot, -np.sin(th), args[..., 1])
+    args[..., 3] = np.where(rot, np.sin(th), args[..., 3])
+    args[..., 4] = np.where(rot, np.cos(th), args[..., 4])
+    blend = (name >= 6) & (name <= 9)
+    args[..., 0] = np.where(blend, 1.0 + m, args[..., 0])
+    args[..., 1] = np.where(blend, -m, args[..., 1])
+    mask = 0xFF & (0xFF << (8 - np.where(name == 10, m, 8.0).astype(np.int64)))
+    args[..., 0] = np.where(name == 10, mask, args[..., 0])
+    args[..., 0] = np.where(name == 11, m, args[..., 0])
+    return PolicyParams(_KERNEL_OP[name], args.astype(np.float32), name.astype(np.uint8))
+
+
+def erase_params(n_batches: int, batch: int, h: int, w: int, prob: float, rng: Optional[np.random.Generator] = None,
+                 scale=(0.02, 0.33), ratio=(0.3, 3.3)) -> np.ndarray:
+    """RandomErasing boxes of a whole epoch, uint8 [n_batches, batch, 4] = (y0, y1, x0, x1), half open
+    (torchvision.transforms.RandomErasing.get_params' rule): a sample is selected with probability `prob`; up to 10
+    attempts draw an area of h * w * U(scale) and an aspect ratio log-uniform in `ratio`, giving a box of
+    round(sqrt(area * ratio)) x round(sqrt(area / ratio)); the first attempt whose box is strictly smaller than the
+    image in both extents is kept, at a uniform corner. A sample that is not selected, or with no fitting attempt,
+    gets the empty box (0, 0, 0, 0)."""
+    if not 0.0 <= prob <= 1.0:
+        raise ValueError("erase_params: prob must be in [0, 1]")
+    if not (0 < h <= 255 and 0 < w <= 255):
+        raise ValueError("erase_params: boxes are uint8, h and w must be in [1, 255]")
+    rng = rng if rng is not None else np.random.default_rng()
+    shape = (int(n_batches), int(batch))
+    selected = rng.random(shape) < prob
+    area = h * w * rng.uniform(scale[0], scale[1], shape + (10,))
+    aspect = np.exp(rng.uniform(math.log(ratio[0]), math.log(ratio[1]), shape + (10,)))
+    u_y, u_x = rng.random(shape), rng.random(shape)
+    eh = np.rint(np.sqrt(area * aspect)).astype(np.int64)
+    ew = np.rint(np.sqrt(area / aspect)).astype(np.int64)
+    fits = (eh < h) & (ew < w)
+    first = np.argmax(fits, axis=-1)[..., None]
+    eh, ew = np.take_along_axis(eh, first, -1)[..., 0], np.take_along_axis(ew, first, -1)[..., 0]
+    keep = selected & fits.any(axis=-1)
+    y0 = np.floor(u_y * (h - eh + 1)).astype(np.int64)
+    x0 = np.floor(u_x * (w - ew + 1)).astype(np.int64)
+    box = np.stack([y0, y0 + eh, x0, x0 + ew], -1)
+    return np.where(keep[..., None], box, 0).astype(np.uint8)
+
+
+class LastPolicy(NamedTuple):
+    """The policy parameters of a DeviceLoader's last batch (device tensors; None where the part is off)."""
+
+    ops: Optional[torch.Tensor]
+    args: Optional[torch.Tensor]
+    erase: Optional[torch.Tensor]
+
+
 class DeviceLoader:
     """``DataLoader(Subset(dataset, subset_idx), batch_size, sampler=sampler, drop_last=...)`` with
     the reference's train (or valid/test) transform (src/ddp/dataset.py:43-64, 95-116) executed on
@@ -241,11 +355,20 @@ class DeviceLoader:
     (``ops.cifar_augment_mix``). The epoch's parameters are drawn on the host from ``seed + epoch``
     (``mix_params``) and uploaded once, like the index list; a mixed batch yields ``(images, nn.MixedTarget)``,
     an unmixed one the plain launch's ``(images, labels)``. ``last_params`` is then ``(index, crop, flip, mix)``
-    with ``mix`` a dict of the batch's ``mode``, ``lam`` (the loss's), ``box`` and the Beta ``draw``."""
+    with ``mix`` a dict of the batch's ``mode``, ``lam`` (the loss's), ``box`` and the Beta ``draw``.
+
+    ``policy`` = ``"randaugment"`` / ``"trivialwide"`` and ``erase_prob`` > 0 (train loaders only): an augmentation
+    policy's op chain per sample between the flip and Normalize, and RandomErasing after it, in the one launch of
+    ``ops.cifar_augment_policy``. Both parameter sets are drawn once per epoch on the host from a generator of their
+    own, ``default_rng([seed + epoch, 1])`` (``policy_params`` then ``erase_params``; the Mixup / CutMix stream is
+    untouched), and uploaded once. A mixed batch is the policy launch writing the augmented uint8 batch, then the
+    mix launch on that batch. ``last_policy`` holds the last batch's ``(ops, args, erase)``; RandomErasing does not
+    combine with Mixup / CutMix. With the defaults the loader issues exactly the launches it issues without them."""
 
     def __init__(self, images, targets, batch_size: int, subset_idx=None, sampler=None, train: bool = True,
                  mean=CIFAR_MEAN, std=CIFAR_STD, pad: int = 4, drop_last: bool = True, seed: int = 0,
-                 device=None, mixup_alpha: float = 0.0, cutmix_alpha: float = 0.0, mix_prob: float = 1.0):
+                 device=None, mixup_alpha: float = 0.0, cutmix_alpha: float = 0.0, mix_prob: float = 1.0,
+                 policy: str = "none", policy_num_ops: int = 2, policy_magnitude: int = 9, erase_prob: float = 0.0):
         from . import ops
 
         self.mixup_alpha, self.cutmix_alpha, self.mix_prob = float(mixup_alpha), float(cutmix_alpha), float(mix_prob)
@@ -254,6 +377,21 @@ class DeviceLoader:
             raise ValueError("DeviceLoader: Mixup / CutMix are training transforms (train=False with an alpha > 0)")
         if self.mixup_alpha < 0 or self.cutmix_alpha < 0 or not 0.0 <= self.mix_prob <= 1.0:
             raise ValueError("DeviceLoader: alphas must be >= 0 and mix_prob in [0, 1]")
+        self.policy, self.policy_num_ops, self.policy_magnitude = str(policy), int(policy_num_ops), int(policy_magnitude)
+        self.erase_prob = float(erase_prob)
+        if self.policy not in POLICIES:
+            raise ValueError(f"DeviceLoader: policy must be one of {POLICIES}, got {policy!r}")
+        if not 1 <= self.policy_num_ops <= 4 or not 0 <= self.policy_magnitude < _POLICY_BINS:
+            raise ValueError("DeviceLoader: policy_num_ops must be in [1, 4] and policy_magnitude in [0, 30]")
+        if not 0.0 <= self.erase_prob <= 1.0:
+            raise ValueError("DeviceLoader: erase_prob must be in [0, 1]")
+        self.policing = self.policy != "none" or self.erase_prob > 0
+        if self.policing and not train:
+            raise ValueError("DeviceLoader: augmentation policies and RandomErasing are training transforms "
+                             "(train=False with a policy or erase_prob > 0)")
+        if self.erase_prob > 0 and self.mixing:
+            raise ValueError("DeviceLoader: RandomErasing does not combine with Mixup / CutMix (erase_prob > 0 with "
+                             "an alpha > 0)")
 
         self._ops = ops
         dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -266,6 +404,7 @@ class DeviceLoader:
         self.seed, self.device, self.epoch = int(seed), dev, 0
         self.status = torch.zeros(1, dtype=torch.int32, device=dev)
         self.last_params = None  # (index, crop, flip) of the last batch, for tests
+        self.last_policy = None  # LastPolicy(ops, args, erase) of the last batch (None without a policy / erasing)
 
     def set_epoch(self, epoch: int) -> None:
         self.epoch = int(epoch)
@@ -281,6 +420,30 @@ class DeviceLoader:
         n = len(self.sampler) if self.sampler is not None else len(self.subset_idx)
         return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
 
+    def _policy_batch(self, k, idx, crop, flip, mix, lam_d, box_d, pol):
+        """Batch k with a policy and / or erasing: one ops.cifar_augment_policy launch; a mixed batch is that launch
+        writing the augmented uint8 batch and its labels, then the mix launch on that batch."""
+        n = idx.numel()
+        self.last_policy = pol
+        common = dict(targets=self.targets, ops=pol.ops, args=pol.args, status=self.status)
+        mode = 0
+        if mix is not None:
+            mode = int(mix.mode[k])
+            self.last_params = (idx, crop, flip, {"mode": mode, "lam": lam_d[k, :n], "box": box_d[k, :n],
+                                                  "draw": float(mix.draw[k])})
+        else:
+            self.last_params = (idx, crop, flip)
+        if not mode:
+            return self._ops.cifar_augment_policy(self.images, idx, crop, flip, self.mean, self.std, self.pad,
+                                                  erase=pol.erase, **common)
+        from .nn import MixedTarget
+
+        u8, lab = self._ops.cifar_augment_policy(self.images, idx, crop, flip, self.mean, self.std, self.pad,
+                                                 to_u8=True, **common)
+        x, ya, yb = self._ops.cifar_augment_mix(u8, None, None, None, self.mean, self.std, self.pad, targets=lab,
+                                                mode=mode, lam=lam_d[k, :n], box=box_d[k, :n], status=self.status)
+        return x, MixedTarget(ya, yb, lam_d[k, :n])
+
     def __iter__(self):
         rows = torch.from_numpy(self._rows()).to(self.device)
         gen = torch.Generator(device=self.device)
@@ -294,6 +457,16 @@ class DeviceLoader:
                              self.cutmix_alpha, self.mix_prob, np.random.default_rng(self.seed + self.epoch))
             lam_d = torch.from_numpy(mix.lam).to(self.device)
             box_d = torch.from_numpy(mix.box).to(self.device)
+        pol_ops = pol_args = pol_erase = None
+        if self.policing:
+            h, w = self.images.shape[1], self.images.shape[2]
+            prng = np.random.default_rng([self.seed + self.epoch, 1])
+            if self.policy != "none":
+                pol = policy_params(len(self), B, h, w, self.policy, self.policy_num_ops, self.policy_magnitude, prng)
+                pol_ops = torch.from_numpy(pol.ops).to(self.device)
+                pol_args = torch.from_numpy(pol.args).to(self.device)
+            if self.erase_prob > 0:
+                pol_erase = torch.from_numpy(erase_params(len(self), B, h, w, self.erase_prob, prng)).to(self.device)
         finished = False
         try:
             for k in range(len(self)):
@@ -304,6 +477,10 @@ class DeviceLoader:
                     crop = torch.randint(0, 2 * self.pad + 1, (n, 2), dtype=torch.uint8, device=self.device,
                                          generator=gen)
                     flip = torch.randint(0, 2, (n,), dtype=torch.uint8, device=self.device, generator=gen)
+                if self.policing:
+                    yield self._policy_batch(k, idx, crop, flip, mix, lam_d, box_d, LastPolicy(
+                        *(None if t is None else t[k, :n] for t in (pol_ops, pol_args, pol_erase))))
+                    continue
                 if mix is not None:
                     mode = int(mix.mode[k])
                     self.last_params = (idx, crop, flip, {"mode": mode, "lam": lam_d[k, :n], "box": box_d[k, :n],

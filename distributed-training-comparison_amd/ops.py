@@ -805,3 +805,46 @@ def cifar_augment_mix(images, index, crop, flip, mean, std, pad=4, targets=None,
          int(pad), m, s, ptr(partner), int(mode), ptr(lam), ptr(box), ptr(out), ptr(labels), ptr(labels_b),
          ptr(status), stream_ptr())
     return out, labels, labels_b
+
+
+def cifar_augment_policy(images, index, crop, flip, mean, std, pad=4, targets=None, ops=None, args=None, erase=None,
+                         to_u8=False, out=None, labels=None, status=None):
+    """cifar_augment with a chain of policy ops per image between the flip and Normalize (RandAugment /
+    TrivialAugmentWide; op codes and their arithmetic: include/dtc.h, dtc_cifar_augment_policy) and an optional
+    RandomErasing box zeroed after Normalize, in one launch. ops: uint8 [n, N], N in 0..4 (None: no ops); args:
+    fp32 [n, N, 6]; erase: uint8 [n, 4] = (y0, y1, x0, x1), half open (None: none). Returns (fp32 [n,3,H,W], labels)
+    or, with to_u8, (uint8 [n,H,W,3] before Normalize, labels) -- the `images` of a following cifar_augment_mix
+    with index = crop = flip = None and targets = these labels."""
+    require_cuda(images, index, crop, flip, targets, ops, args, erase, out, labels, status)
+    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3 or not images.is_contiguous():
+        raise ValueError(f"images must be contiguous uint8 [N,H,W,3], got {images.dtype} {tuple(images.shape)}")
+    n_images, h, w, _ = images.shape
+    n = index.numel() if index is not None else (crop.shape[0] if crop is not None else n_images)
+    if (ops is None) != (args is None):
+        raise ValueError("cifar_augment_policy: ops and args go together")
+    n_ops = 0
+    if ops is not None:
+        if ops.dim() != 2:
+            raise ValueError(f"ops must be uint8 [n, N], got {tuple(ops.shape)}")
+        n_ops = int(ops.shape[1])
+    if to_u8 and erase is not None:
+        raise ValueError("cifar_augment_policy: erase applies to the normalized output, not with to_u8")
+    for t, shape, dt in ((index, (n,), torch.int64), (crop, (n, 2), torch.uint8), (flip, (n,), torch.uint8),
+                         (targets, (n_images,), torch.int64), (ops, (n, n_ops), torch.uint8),
+                         (args, (n, n_ops, 6), torch.float32), (erase, (n, 4), torch.uint8)):
+        if t is not None and (t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous()):
+            raise ValueError(f"expected contiguous {dt} {shape}, got {t.dtype} {tuple(t.shape)}")
+    if n_ops == 0:
+        ops = args = None
+    if to_u8:
+        out = _out(out, (n, h, w, 3), torch.uint8, images.device, "cifar_augment_policy")
+    else:
+        out = _out(out, (n, 3, h, w), torch.float32, images.device, "cifar_augment_policy")
+    if targets is not None and labels is None:
+        labels = torch.empty(n, dtype=torch.int64, device=images.device)
+    m = (C.c_float * 3)(*[float(v) for v in mean])
+    s = (C.c_float * 3)(*[float(v) for v in std])
+    call("dtc_cifar_augment_policy", ptr(images), ptr(targets), n_images, ptr(index), ptr(crop), ptr(flip), n, h, w,
+         int(pad), m, s, ptr(ops), ptr(args), n_ops, ptr(erase), None if to_u8 else ptr(out),
+         ptr(out) if to_u8 else None, ptr(labels), ptr(status), stream_ptr())
+    return out, labels

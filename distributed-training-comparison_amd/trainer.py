@@ -78,6 +78,16 @@ def load_config(argv=None, mode: str = "ddp"):
                    help="CutMix with lam ~ Beta(alpha, alpha) per batch, on the device (needs --device-data; 0 = off)")
     p.add_argument("--mix-prob", type=float, default=1.0,
                    help="probability that a batch is mixed; with both alphas set each kind is picked half the time")
+    # the data side of the same recipes (timm --aa rand-m9-n2 --reprob 0.25, torchvision --auto-augment ta_wide)
+    p.add_argument("--auto-augment", choices=["none", "randaugment", "trivialwide"], default="none",
+                   help="augmentation policy applied per sample on the device, between the flip and Normalize "
+                        "(needs --device-data)")
+    p.add_argument("--ra-num-ops", type=int, default=2, help="--auto-augment randaugment: ops per sample, 1..4")
+    p.add_argument("--ra-magnitude", type=int, default=9,
+                   help="--auto-augment randaugment: magnitude bin of 31, 0..30")
+    p.add_argument("--random-erasing", type=float, default=0.0,
+                   help="RandomErasing probability per sample, value 0, on the device (needs --device-data; not with "
+                        "--mixup-alpha / --cutmix-alpha; 0 = off)")
     # timm's / torchvision's --model-ema: the weights worth keeping at large batches and under Mixup / CutMix
     p.add_argument("--model-ema", action="store_true", default=False,
                    help="keep an exponential moving average of the weights and running statistics on the device "
@@ -119,6 +129,12 @@ def load_config(argv=None, mode: str = "ddp"):
         p.error("--warmup-epochs must be >= 0 and --lars-trust-coef > 0")
     if (h.mixup_alpha > 0 or h.cutmix_alpha > 0) and not h.device_data:
         p.error("--mixup-alpha / --cutmix-alpha need --device-data (the host loader does not mix)")
+    if not 1 <= h.ra_num_ops <= 4 or not 0 <= h.ra_magnitude <= 30 or not 0.0 <= h.random_erasing <= 1.0:
+        p.error("--ra-num-ops must be in [1, 4], --ra-magnitude in [0, 30] and --random-erasing in [0, 1]")
+    if (h.auto_augment != "none" or h.random_erasing > 0) and not h.device_data:
+        p.error("--auto-augment / --random-erasing need --device-data (the host loader applies no policy)")
+    if h.random_erasing > 0 and (h.mixup_alpha > 0 or h.cutmix_alpha > 0):
+        p.error("--random-erasing does not combine with --mixup-alpha / --cutmix-alpha")
     if not 0.0 <= h.model_ema_decay < 1.0 or h.model_ema_steps < 1:
         p.error("--model-ema-decay must be in [0, 1) and --model-ema-steps >= 1")
     if h.accum_steps < 1:
@@ -174,6 +190,15 @@ def mix_kwargs(hparams) -> dict:
     if ma <= 0 and ca <= 0:
         return {}
     return {"mixup_alpha": ma, "cutmix_alpha": ca, "mix_prob": float(getattr(hparams, "mix_prob", 1.0))}
+
+
+def policy_kwargs(hparams) -> dict:
+    """The train DeviceLoader's augmentation-policy and RandomErasing keywords (none with the default flags)."""
+    policy, erase = getattr(hparams, "auto_augment", "none"), float(getattr(hparams, "random_erasing", 0.0))
+    if policy == "none" and erase <= 0:
+        return {}
+    return {"policy": policy, "policy_num_ops": int(getattr(hparams, "ra_num_ops", 2)),
+            "policy_magnitude": int(getattr(hparams, "ra_magnitude", 9)), "erase_prob": erase}
 
 
 def make_scheduler(optimizer, hparams):
@@ -258,7 +283,8 @@ class Trainer:
                    else torch.utils.data.SubsetRandomSampler(list(range(len(train_idx)))))
         bs = hparams.batch_size
         self.train_loader = D.DeviceLoader(imgs, tg, bs, subset_idx=train_idx, sampler=sampler, train=True,
-                                           seed=hparams.seed, device=self.device, **mix_kwargs(hparams))
+                                           seed=hparams.seed, device=self.device, **mix_kwargs(hparams),
+                                           **policy_kwargs(hparams))
         self.train_sampler = self.train_loader
         self.val_loader = D.DeviceLoader(imgs, tg, bs, subset_idx=valid_idx, train=False, drop_last=False,
                                          device=self.device)

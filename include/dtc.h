@@ -441,6 +441,35 @@ int dtc_cifar_augment_mix(const uint8_t* images, const int64_t* targets, int64_t
                           const float* std, const int32_t* partner, int mode, const float* lam, const uint8_t* box,
                           float* out, int64_t* labels, int64_t* labels_b, int* status, void* stream);
 
+/* dtc_cifar_augment with an augmentation policy (RandAugment / TrivialAugmentWide) and RandomErasing in the same
+ * launch: gather, crop, flip, then n_ops (0..4) ops per image on the uint8 image, then ToTensor / Normalize, then
+ * the erase box set to 0.0f. ops: uint8 [n][n_ops] op codes; args: fp32 [n][n_ops][6], the op's g0..g5 (both may be
+ * NULL when n_ops == 0); erase: uint8 [n][4] = (y0, y1, x0, x1), half open, output coordinates (NULL: none; an empty
+ * box is legal). Exactly one of out (fp32 [n][3][h][w]) and out_u8 (uint8 [n][h][w][3], the image before
+ * Normalize -- what a following dtc_cifar_augment_mix takes as its `images`, with index = crop = flip = NULL and
+ * targets = this call's labels) is non-NULL; erase needs out. All randomness is the caller's. With a the current
+ * image, every fp32 expression evaluated as written (no fused multiply-add), conversions to uint8 clamping to
+ * [0, 255] and then truncating:
+ *   0 Identity
+ *   1 Affine (nearest, fill 0): X = ox + 0.5f - 0.5f*w, Y = oy + 0.5f - 0.5f*h; sx = (g0*X + g1*Y) + g2,
+ *     sy = (g3*X + g4*Y) + g5; rx = rintf(sx + (0.5f*w - 0.5f)), ry = rintf(sy + (0.5f*h - 0.5f)); a[ry][rx] when
+ *     0 <= rx <= w-1 and 0 <= ry <= h-1, else 0
+ *   2 Brightness g0*a + g1*0      3 Color g0*a + g1*gray, gray = trunc((0.2989f*R + 0.587f*G) + 0.114f*B)
+ *   4 Contrast g0*a + g1*m, m = (float)(sum of gray over the image) / (float)(h*w)
+ *   5 Sharpness g0*a + g1*blur; blur = a on the border, (8 neighbours + 5*centre + 6) / 13 in integers inside
+ *   6 Posterize a & (int)g0       7 Solarize (float)a >= g0 ? 255 - a : a
+ *   8 AutoContrast, per channel with lo / hi its min / max: a when lo == hi, else
+ *     trunc(clamp(((float)a - lo) * (255.0f / (float)(hi - lo))))
+ *   9 Equalize, per channel: step = (h*w - hist[last non-empty bin]) / 255; a when step == 0, else
+ *     min(255, (exclusive_cumsum(hist)[a] + step/2) / step)
+ * status is also set when an op code is above 9, an arg that the op reads is not finite or Posterize's g0 is no
+ * integer in [0, 255] (that op then acts as Identity), or an erase box is inverted or leaves the image (not
+ * applied). Other arguments, conditions and shape limits as dtc_cifar_augment. */
+int dtc_cifar_augment_policy(const uint8_t* images, const int64_t* targets, int64_t n_images, const int64_t* index,
+                             const uint8_t* crop, const uint8_t* flip, int n, int h, int w, int pad, const float* mean,
+                             const float* std, const uint8_t* ops, const float* args, int n_ops, const uint8_t* erase,
+                             float* out, uint8_t* out_u8, int64_t* labels, int* status, void* stream);
+
 /* ------------------------------------------------------------------ RCCL communicator
  * Replaces the NCCL traffic of DistributedDataParallel (trainer.py:31): the construction-time
  * parameter broadcast, the per-forward buffer broadcast and the bucketed gradient all-reduce.
