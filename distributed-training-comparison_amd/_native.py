@@ -81,6 +81,16 @@ class SamKeep(C.Structure):
 
 
 PSamKeep = C.POINTER(SamKeep)
+
+
+class PsgdTensor(C.Structure):
+    """dtc_psgd_tensor: one tensor of a PowerSGD plan, a row-major rows x cols matrix (rank 0 = uncompressed)."""
+
+    _fields_ = [("offset", C.c_int64), ("rows", C.c_int64), ("cols", C.c_int64), ("rank", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+PPsgdTensor = C.POINTER(PsgdTensor)
 SAM_MAX_KEEP = 4  # include/dtc.h DTC_SAM_MAX_KEEP
 
 
@@ -148,6 +158,15 @@ _SIGS = {
     "dtc_grad_accum_flat": (i32, [vp, vp, i64, i32, vp]),
     "dtc_grad_compress_bf16": (i32, [vp, vp, vp, i64, vp]),
     "dtc_grad_decompress_bf16": (i32, [vp, vp, i64, vp]),
+    "dtc_psgd_plan_create": (i32, [C.POINTER(vp), PPsgdTensor, i32]),
+    "dtc_psgd_plan_destroy": (i32, [vp]),
+    "dtc_psgd_plan_numel": (i64, [vp, i32]),
+    "dtc_psgd_plan_device_bytes": (sz, [vp]),
+    "dtc_psgd_plan_bind": (i32, [vp, vp, sz, vp]),
+    "dtc_psgd_orthonormalize": (i32, [vp, i32, vp, vp, vp, f64, vp]),
+    "dtc_psgd_project": (i32, [vp, vp, vp, vp, vp, vp]),
+    "dtc_psgd_backproject": (i32, [vp, vp, vp, vp, vp, vp]),
+    "dtc_psgd_reconstruct": (i32, [vp, vp, vp, vp, vp, vp, f64, vp]),
     "dtc_sam_state_words": (i32, []),
     "dtc_sam_workspace_bytes": (sz, [i64]),
     "dtc_sam_perturb": (i32, [vp, vp, vp, vp, i64, f64, f64, i32, vp, PSamKeep, i32, vp, vp, vp]),

@@ -535,6 +535,35 @@ int dtc_grad_compress_bf16(const float* g, const float* acc, uint16_t* c, int64_
 int dtc_grad_decompress_bf16(const uint16_t* c, float* g, int64_t n, void* stream) {
   return grad_decompress_bf16(c, g, n, S(stream));
 }
+static_assert(sizeof(dtc_psgd_tensor) == sizeof(PsgdDesc) && offsetof(dtc_psgd_tensor, rows) == offsetof(PsgdDesc, rows) &&
+                  offsetof(dtc_psgd_tensor, cols) == offsetof(PsgdDesc, cols) &&
+                  offsetof(dtc_psgd_tensor, rank) == offsetof(PsgdDesc, rank),
+              "dtc_psgd_tensor is PsgdDesc");
+int dtc_psgd_plan_create(dtc_psgd_plan** out, const dtc_psgd_tensor* tensors, int n) {
+  GUARD(return psgd_plan_create((PsgdPlan**)out, (const PsgdDesc*)tensors, n);)
+}
+int dtc_psgd_plan_destroy(dtc_psgd_plan* plan) { return psgd_plan_destroy((PsgdPlan*)plan); }
+int64_t dtc_psgd_plan_numel(const dtc_psgd_plan* plan, int what) { return psgd_plan_numel((const PsgdPlan*)plan, what); }
+size_t dtc_psgd_plan_device_bytes(const dtc_psgd_plan* plan) { return psgd_plan_device_bytes((const PsgdPlan*)plan); }
+int dtc_psgd_plan_bind(dtc_psgd_plan* plan, void* dev, size_t bytes, void* stream) {
+  return psgd_plan_bind((PsgdPlan*)plan, dev, bytes, S(stream));
+}
+int dtc_psgd_orthonormalize(dtc_psgd_plan* plan, int what, float* q, float* staging, int* state, double epsilon,
+                            void* stream) {
+  return psgd_orthonormalize((PsgdPlan*)plan, what, q, staging, state, epsilon, S(stream));
+}
+int dtc_psgd_project(dtc_psgd_plan* plan, const float* g, const float* e, const float* q, float* staging,
+                     void* stream) {
+  return psgd_project((PsgdPlan*)plan, g, e, q, staging, S(stream));
+}
+int dtc_psgd_backproject(dtc_psgd_plan* plan, const float* g, const float* e, const float* staging, float* q,
+                         void* stream) {
+  return psgd_backproject((PsgdPlan*)plan, g, e, staging, q, S(stream));
+}
+int dtc_psgd_reconstruct(dtc_psgd_plan* plan, float* g, float* e, const float* staging, const float* q, int* state,
+                         double c, void* stream) {
+  return psgd_reconstruct((PsgdPlan*)plan, g, e, staging, q, state, c, S(stream));
+}
 static_assert(sizeof(dtc_sam_keep) == sizeof(SamKeep) && offsetof(dtc_sam_keep, saved) == offsetof(SamKeep, saved) &&
                   offsetof(dtc_sam_keep, bytes) == offsetof(SamKeep, bytes),
               "dtc_sam_keep is SamKeep");

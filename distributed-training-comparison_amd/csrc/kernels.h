@@ -481,6 +481,28 @@ int grad_accum(float* acc, float* g, int64_t n, int mode, hipStream_t st);
 #define DTC_COMPRESS_MAX_BLOCKS 1024
 int grad_compress_bf16(const float* g, const float* acc, u16* c, int64_t n, hipStream_t st);
 int grad_decompress_bf16(const u16* c, float* g, int64_t n, hipStream_t st);
+// PowerSGD (powersgd.hip): rank-r gradient compression on the flat gradient buffer. The plan (host data; bind uploads
+// its tables into caller-owned device memory that also holds the back-project slots and counters) is built from a
+// sorted table of tensors; rank 0 = all-reduced as it is. what of psgd_plan_numel: 0 P, 1 Q, 2 uncompressed,
+// 3 staging (= uncompressed + P) elements, 4 the stride between the two Q copies. q: [2][stride] fp32 (q[0] the warm
+// start kept across a non-finite step, q[1] the working copy the Q collective runs on); staging: [uncompressed | P];
+// state: 4 int32 words, zeroed by the caller (word 0: 1 = the next warm start is q[1]; word 1: the last step was
+// non-finite); e (error feedback) may be null. One launch each.
+struct PsgdDesc {  // layout of the ABI's dtc_psgd_tensor
+  int64_t offset, rows, cols;
+  int32_t rank, reserved;
+};
+struct PsgdPlan;
+int psgd_plan_create(PsgdPlan** out, const PsgdDesc* tensors, int n);
+int psgd_plan_destroy(PsgdPlan* plan);
+int64_t psgd_plan_numel(const PsgdPlan* plan, int what);
+size_t psgd_plan_device_bytes(const PsgdPlan* plan);
+int psgd_plan_bind(PsgdPlan* plan, void* dev, size_t bytes, hipStream_t st);
+int psgd_orthonormalize(PsgdPlan* plan, int what, float* q, float* staging, int* state, double eps, hipStream_t st);
+int psgd_project(PsgdPlan* plan, const float* g, const float* e, const float* q, float* staging, hipStream_t st);
+int psgd_backproject(PsgdPlan* plan, const float* g, const float* e, const float* staging, float* q, hipStream_t st);
+int psgd_reconstruct(PsgdPlan* plan, float* g, float* e, const float* staging, const float* q, int* state, double c,
+                     hipStream_t st);
 // SAM / ASAM (sam.hip) over the whole flat buffer. perturb: p_saved = p, p += coef * g (adaptive: * p * p) with
 // coef = rho * m / (|m| * ||t|| + eps), t = g or p * g, m = *gmul, p_bf16 = bf16(p); a non-finite norm moves nothing
 // and marks `state` (DTC_SAM_STATE_WORDS 32-bit words, 16-byte aligned: fp32 coef, fp32 norm, int32 skipped) --

@@ -46,7 +46,7 @@ def set_autocast_enabled(enabled: bool) -> None:
 
 
 PRECISIONS = ("bf16", "fp32")
-GRAD_COMPRESSIONS = (None, "bf16")  # ResNet.grad_compression
+GRAD_COMPRESSIONS = (None, "bf16", "powersgd")  # ResNet.grad_compression
 
 
 # ----------------------------------------------------------------------------- layout
@@ -119,6 +119,15 @@ class FlatState:
         self.clip_pending = False
         self._grad_acc = None
         self._grad_c16 = None
+        self._grad_err = None
+
+    @property
+    def grad_err(self) -> torch.Tensor:
+        """The error-feedback buffer of PowerSGD (ResNet.grad_compression = "powersgd"): the layout of `grads`,
+        zeros, allocated on first use. It holds what the low-rank approximations have left out so far."""
+        if self._grad_err is None:
+            self._grad_err = torch.zeros_like(self.grads)
+        return self._grad_err
 
     @property
     def grad_c16(self) -> torch.Tensor:
@@ -300,6 +309,59 @@ def _raw_stream(index) -> int:
     if _RAW_STREAM is not None:
         return _RAW_STREAM(index if index is not None else torch.cuda.current_device())
     return stream_ptr()
+
+
+# ----------------------------------------------------------------------------- PowerSGD
+class PowerSGD:
+    """PowerSGD on a model's flat gradients (ResNet.grad_compression = "powersgd"; set up by
+    DistributedDataParallel.register_comm_hook). `state` is a parallel.PowerSGDState or torch's, read by attribute
+    name; its `iter` counts the reducing backwards, as torch's hook does: the first `start_powerSGD_iter` of them
+    take the native Reducer, every later one runs the executor without a communicator and then `step()`: five
+    launches and two small collectives on the caller's stream (ops.psgd_step). The plan, the staging / Q buffers
+    (Q drawn once on the CPU from the state's seed) and `flat.grad_err` are made at the first compressed step;
+    after it nothing is allocated, copied from the host or waited for.
+
+    A non-finite step writes NaN into the compressed gradients (GradScaler then skips the step on every rank) and
+    leaves the error buffer and the warm-start Q as they were. A change of the loss scale leaves the error buffer
+    in the old scale for one step, as in torch."""
+
+    def __init__(self, state):
+        rank = getattr(state, "matrix_approximation_rank")
+        if not isinstance(rank, int) or not 1 <= rank <= ops.PSGD_MAX_RANK:
+            raise ValueError(f"matrix_approximation_rank must be an integer in [1, {ops.PSGD_MAX_RANK}] (the "
+                             f"kernels' maximum), not {rank!r}")
+        if not getattr(state, "warm_start", True):
+            raise NotImplementedError("PowerSGD with warm_start=False is not supported: it would draw a new Q on the "
+                                      "host at every step")
+        self.state = state
+        self.rank = rank
+        self.start = int(state.start_powerSGD_iter)
+        self.min_compression_rate = state.min_compression_rate
+        self.error_feedback = bool(state.use_error_feedback)
+        self.eps = float(getattr(state, "orthogonalization_epsilon", 0.0))
+        seed = getattr(state, "random_seed", None)
+        if seed is None:  # torch's state keeps only a numpy RandomState seeded with it: draw the seed as its hook does
+            seed = int(state.rng.randint(1_000_000_000))
+        self.seed = int(seed)
+        if not hasattr(state, "iter"):
+            state.iter = 0
+        self.plan = self.staging = self.q = self.dev_state = None
+
+    def take(self) -> bool:
+        """Count one reducing backward; True when it is a compressed one."""
+        compress = self.state.iter >= self.start
+        self.state.iter += 1
+        return compress
+
+    def step(self, flat: "FlatState", comm) -> None:
+        if self.plan is None:
+            self.plan = ops.psgd_plan(flat.layout, self.rank, self.min_compression_rate, flat.device)
+            self.staging, self.q, self.dev_state = ops.psgd_buffers(self.plan, self.seed, flat.device)
+            if self.error_feedback:
+                flat.grad_err  # noqa: B018 - allocated here, not inside a later step
+        world = comm.world if comm is not None else 1
+        ops.psgd_step(self.plan, flat.grads, flat.grad_err if self.error_feedback else None, self.staging, self.q,
+                      self.dev_state, 1.0 / world, self.eps, comm.allreduce_sum_ if comm is not None else None)
 
 
 # ----------------------------------------------------------------------------- autograd nodes
@@ -778,7 +840,11 @@ class ResNet(nn.Module):
         # gradient compression of the bucket all-reduces: None, or "bf16" (torch's bf16_compress_hook; set by
         # DistributedDataParallel.register_comm_hook / gradient_compression=). Only a backward that all-reduces
         # compresses anything; the gradients the optimizer reads stay fp32.
+        # "powersgd" (torch's powerSGD_hook) needs a state and so comes only through register_comm_hook, which
+        # also sets `_powersgd`; it runs after the native backward, not inside the Reducer.
         self.grad_compression = None
+        self._powersgd: Optional[PowerSGD] = None
+        self._psgd_pending = False  # the backward that is running is followed by a PowerSGD step
         self._accum_depth = 0
         self._accum_open = False
         self._local_depth = 0  # nesting depth of local_grads()
@@ -968,7 +1034,9 @@ class ResNet(nn.Module):
         """(grad_scale, comm) of the native backward about to run on `exe`, whose accumulation mode is set
         from the window's state: STORE / ADD without a communicator inside accumulate(), FINISH for the backward
         that closes a window, OFF otherwise; its compression mode from `grad_compression`. Inside local_grads():
-        OFF and no communicator."""
+        OFF and no communicator. With PowerSGD armed, a reducing backward past the state's start iteration also runs
+        without a communicator (its accumulation mode as usual: FINISH still folds the window's sum in) and
+        _end_backward() runs the PowerSGD step on the gradients it left."""
         if self.grad_compression not in GRAD_COMPRESSIONS:
             raise ValueError(f"grad_compression must be one of {GRAD_COMPRESSIONS}, not {self.grad_compression!r}")
         steps = self.grad_accum_steps
@@ -982,12 +1050,21 @@ class ResNet(nn.Module):
             mode, comm = (ops.ACCUM_ADD if self._accum_open else ops.ACCUM_STORE), None
         else:
             mode = ops.ACCUM_FINISH if self._accum_open else ops.ACCUM_OFF
+            if self.grad_compression == "powersgd":
+                if self._powersgd is None:
+                    raise NativeError('grad_compression = "powersgd" needs a state: use DistributedDataParallel.'
+                                      'register_comm_hook(PowerSGDState(...), powerSGD_hook)')
+                if self._powersgd.take():
+                    self._psgd_pending, comm = True, None
         exe.set_grad_accum(mode)
         exe.set_grad_compress(ops.COMPRESS_BF16 if self.grad_compression == "bf16" else ops.COMPRESS_OFF)
         return self._grad_scale / steps, comm
 
     def _end_backward(self) -> None:
         self._accum_open = self._accum_depth > 0
+        if self._psgd_pending:
+            self._psgd_pending = False
+            self._powersgd.step(self.flat, self._comm)
 
     # ------------------------------------------------------------------ forward
     def forward(self, x: torch.Tensor) -> torch.Tensor:

@@ -11,8 +11,8 @@ import ctypes as C
 
 import torch
 
-from ._native import (SAM_MAX_KEEP, SEG_ADAPT, ConvDesc, EmaRange, NativeError, SamKeep, Seg, call, lib, ptr,
-                      require_cuda, stream_ptr)
+from ._native import (SAM_MAX_KEEP, SEG_ADAPT, ConvDesc, EmaRange, NativeError, PsgdTensor, SamKeep, Seg, call, lib,
+                      ptr, require_cuda, stream_ptr)
 
 
 
@@ -671,6 +671,150 @@ def grad_decompress_bf16(c, g):
     if g.dtype != torch.float32 or not g.is_contiguous() or c.numel() != g.numel():
         raise NativeError("grad_decompress_bf16: g must be a contiguous fp32 tensor of c's element count")
     call("dtc_grad_decompress_bf16", ptr(c), ptr(g), g.numel(), stream_ptr())
+
+
+# ----------------------------------------------------------------------------- PowerSGD
+PSGD_P, PSGD_Q, PSGD_UNCOMPRESSED, PSGD_STAGING, PSGD_QSTRIDE = 0, 1, 2, 3, 4  # include/dtc.h DTC_PSGD_*
+PSGD_MAX_RANK = 4
+
+
+def psgd_should_compress(rows, cols, rank, min_compression_rate=2):
+    """torch's ``powerSGD_hook._should_compress``: a rows x cols tensor is compressed at `rank` when the P and Q
+    blocks together, times the rate, are smaller than the tensor."""
+    return (rows + cols) * rank * min_compression_rate < rows * cols
+
+
+class PsgdPlan:
+    """A PowerSGD plan (dtc_psgd_plan) with the device memory it is bound to. `tensors`: (offset, rows, cols, rank)
+    in offset order, rank 0 = all-reduced uncompressed. n_p / n_q / n_unc / n_staging / q_stride: the element
+    counts of include/dtc.h; `end`: the first element past the last tensor."""
+
+    def __init__(self, tensors, names=None, device=None):
+        tensors = [(int(o), int(r), int(c), int(k)) for o, r, c, k in tensors]
+        table = (PsgdTensor * max(1, len(tensors)))(*[PsgdTensor(o, r, c, k, 0) for o, r, c, k in tensors])
+        self.handle = C.c_void_p()
+        self._destroy = lib.dtc_psgd_plan_destroy  # held here: module globals are gone at interpreter exit
+        call("dtc_psgd_plan_create", C.byref(self.handle), table, len(tensors))
+        self.tensors = tensors
+        self.names = list(names) if names is not None else [str(i) for i in range(len(tensors))]
+        self.n_p, self.n_q, self.n_unc, self.n_staging, self.q_stride = (
+            int(lib.dtc_psgd_plan_numel(self.handle, w))
+            for w in (PSGD_P, PSGD_Q, PSGD_UNCOMPRESSED, PSGD_STAGING, PSGD_QSTRIDE))
+        self.end = tensors[-1][0] + tensors[-1][1] * tensors[-1][2]
+        self.mem = None
+        if device is not None:
+            self.bind(device)
+
+    def bind(self, device):
+        """Upload the tables into fresh device memory (the only copy: nothing is copied per step)."""
+        nbytes = lib.dtc_psgd_plan_device_bytes(self.handle)
+        self.mem = torch.empty(nbytes, dtype=torch.uint8, device=device)  # the allocator aligns to 512 bytes
+        require_cuda(self.mem)
+        call("dtc_psgd_plan_bind", self.handle, ptr(self.mem), nbytes, stream_ptr())
+
+    def q_blocks(self):
+        """[(tensor index, Q offset, cols, rank)] of the compressed tensors: where each Q block lies in a Q copy."""
+        out, off = [], 0
+        for i, (_, _, c, k) in enumerate(self.tensors):
+            if k:
+                out.append((i, off, c, k))
+                off += c * k
+        return out
+
+    def __del__(self):
+        h, self.handle = getattr(self, "handle", None), None
+        if h:
+            self._destroy(h)
+
+
+def psgd_plan(layout_or_tensors, rank=1, min_compression_rate=2, device=None) -> PsgdPlan:
+    """The PowerSGD plan of a model's Layout -- every parameter with more than one dimension is the row-major
+    shape[0] x (numel / shape[0]) matrix it is stored as (conv weights: K x R*S*C) and is compressed at
+    min(rows, cols, rank) when torch's rule (psgd_should_compress) says so; everything else is rank 0 -- or of a
+    list of (offset, rows, cols, rank) in offset order. Bound to fresh memory on `device` (None: left unbound)."""
+    params = getattr(layout_or_tensors, "params", None)
+    if params is None:
+        return PsgdPlan(layout_or_tensors, None, device)
+    if not isinstance(rank, int) or not 1 <= rank <= PSGD_MAX_RANK:
+        raise ValueError(f"PowerSGD rank must be an integer in [1, {PSGD_MAX_RANK}], not {rank!r}")
+    tensors = []
+    params = sorted(params, key=lambda q: q.offset)
+    for q in params:
+        rows = q.shape[0] if len(q.shape) > 1 else q.numel
+        cols = q.numel // rows
+        k = min(rows, cols, rank) if len(q.shape) > 1 and psgd_should_compress(rows, cols, rank,
+                                                                               min_compression_rate) else 0
+        tensors.append((q.offset, rows, cols, k))
+    return PsgdPlan(tensors, [q.name for q in params], device)
+
+
+def psgd_buffers(plan, seed=0, device=None):
+    """(staging, q, state) of one PowerSGD plan on its device: staging fp32 [n_staging] = [uncompressed | P]; q fp32
+    [2, q_stride] with q[0] = torch.randn(n_q) drawn on the CPU from `seed` (the same on every rank; per tensor a
+    row-major cols x rank block, columns in storage order) and uploaded once; state int32 [4], zeroed."""
+    device = device if device is not None else plan.mem.device
+    staging = torch.zeros(max(plan.n_staging, 4), dtype=torch.float32, device=device)
+    q = torch.zeros(2, max(plan.q_stride, 4), dtype=torch.float32, device=device)  # (4: only without any Q)
+    init = torch.randn(plan.n_q, generator=torch.Generator().manual_seed(int(seed)), dtype=torch.float32)
+    q[0, :plan.n_q].copy_(init)
+    return staging, q, torch.zeros(4, dtype=torch.int32, device=device)
+
+
+def _psgd_check(plan, g, e, staging, q, state=None):
+    require_cuda(g, e, staging, q, state)
+    if plan.mem is None:
+        raise NativeError("the PowerSGD plan is not bound to a device (ops.psgd_plan(..., device))")
+    for t in (g, e):
+        if t is not None and (t.dtype != torch.float32 or t.numel() < plan.end or not t.is_contiguous()):
+            raise NativeError(f"PowerSGD: g and e must be contiguous fp32 tensors of at least the plan's {plan.end} "
+                              "elements")
+    if staging.dtype != torch.float32 or staging.numel() < plan.n_staging or not staging.is_contiguous():
+        raise NativeError(f"PowerSGD: staging must be a contiguous fp32 tensor of {plan.n_staging} elements")
+    if q.dtype != torch.float32 or q.numel() < 2 * plan.q_stride or not q.is_contiguous():
+        raise NativeError(f"PowerSGD: q must be a contiguous fp32 tensor of 2 x {plan.q_stride} elements")
+    if state is not None and (state.dtype != torch.int32 or state.numel() < 4):
+        raise NativeError("PowerSGD: state must be an int32 tensor of 4 words")
+
+
+def psgd_orthonormalize(plan, what, q, staging, state, eps=0.0):
+    """Modified Gram-Schmidt of every Q block (what = PSGD_Q: warm start -> q[1]) or P block (PSGD_P: in staging)."""
+    _psgd_check(plan, None, None, staging, q, state)
+    call("dtc_psgd_orthonormalize", plan.handle, int(what), ptr(q), ptr(staging), ptr(state), float(eps),
+         stream_ptr())
+
+
+def psgd_project(plan, g, e, q, staging):
+    """staging = [uncompressed tensors of g | P = (g + e) Qh] (e may be None)."""
+    _psgd_check(plan, g, e, staging, q)
+    call("dtc_psgd_project", plan.handle, ptr(g), ptr(e), ptr(q), ptr(staging), stream_ptr())
+
+
+def psgd_backproject(plan, g, e, staging, q):
+    """q[1] = (g + e)^T Ph, Ph the orthonormalised P blocks in staging."""
+    _psgd_check(plan, g, e, staging, q)
+    call("dtc_psgd_backproject", plan.handle, ptr(g), ptr(e), ptr(staging), ptr(q), stream_ptr())
+
+
+def psgd_reconstruct(plan, g, e, staging, q, state, c=1.0):
+    """g = Ph Q^T, e = (g + e) - c * that, uncompressed tensors scattered back from staging; NaN and nothing else
+    when the all-reduced P or Q was not finite."""
+    _psgd_check(plan, g, e, staging, q, state)
+    call("dtc_psgd_reconstruct", plan.handle, ptr(g), ptr(e), ptr(staging), ptr(q), ptr(state), float(c),
+         stream_ptr())
+
+
+def psgd_step(plan, g, e, staging, q, state, c=1.0, eps=0.0, allreduce=None):
+    """One PowerSGD step on the current stream: the five launches with the two SUM all-reduces `allreduce(tensor)`
+    between them (None: one rank, the collectives elided): [uncompressed | P], then Q."""
+    psgd_orthonormalize(plan, PSGD_Q, q, staging, state, eps)
+    psgd_project(plan, g, e, q, staging)
+    if allreduce is not None and plan.n_staging:
+        allreduce(staging[:plan.n_staging])
+    psgd_orthonormalize(plan, PSGD_P, q, staging, state, eps)
+    psgd_backproject(plan, g, e, staging, q)
+    if allreduce is not None and plan.n_q:
+        allreduce(q.view(-1)[plan.q_stride:plan.q_stride + plan.n_q])
+    psgd_reconstruct(plan, g, e, staging, q, state, c)
 
 
 def sam_state(device):

@@ -20,7 +20,10 @@ on a ``dist.init_process_group('nccl', 'tcp://127.0.0.1:3456', world, rank)`` gr
   ahead of each bucket's all-reduce -- one set of collectives per window of micro-batches;
 * ``register_comm_hook(state, bf16_compress_hook)`` / ``gradient_compression="bf16"``: each bucket is rounded to
   bf16 into a staging buffer, all-reduced there at half the bytes and widened back into the fp32 gradients behind
-  its collective (torch's ``default_hooks.bf16_compress_hook``); ``allreduce_hook`` is the plain fp32 all-reduce.
+  its collective (torch's ``default_hooks.bf16_compress_hook``); ``allreduce_hook`` is the plain fp32 all-reduce;
+* ``register_comm_hook(PowerSGDState(...), powerSGD_hook)``: rank-r PowerSGD (torch's ``powerSGD_hook``). After the
+  state's ``start_powerSGD_iter`` plain steps a reducing backward runs without the Reducer and is followed by five
+  launches and two collectives of tens of kilobytes on the caller's stream (nn.PowerSGD).
 """
 from __future__ import annotations
 
@@ -50,15 +53,68 @@ def allreduce_hook(state=None, bucket=None):
     raise NativeError("allreduce_hook is a marker for register_comm_hook, not a callable hook")
 
 
+def powerSGD_hook(state=None, bucket=None):  # noqa: N802 - torch's name
+    """Sentinel for ``DistributedDataParallel.register_comm_hook``: rank-r PowerSGD gradient compression (the
+    counterpart of torch's ``ddp_comm_hooks.powerSGD_hook.powerSGD_hook``, which is accepted too), configured by a
+    ``PowerSGDState``. The kernels of nn.PowerSGD do the work; this function is never called."""
+    raise NativeError("powerSGD_hook is a marker for register_comm_hook, not a callable hook")
+
+
+class PowerSGDState:
+    """torch's ``ddp_comm_hooks.powerSGD_hook.PowerSGDState`` for the native PowerSGD: the same arguments, defaults
+    and validation. `process_group` is ignored (the collectives run on the wrapper's communicator).
+    `matrix_approximation_rank` is at most 4. The first `start_powerSGD_iter` reducing backwards are plain
+    all-reduces (`iter` counts them); `min_compression_rate` is torch's per-tensor test; `use_error_feedback=False`
+    keeps no error buffer; `warm_start=False` is not supported; `orthogonalization_epsilon` is added to every norm
+    the Gram-Schmidt divides by; `random_seed` seeds the one CPU draw of the initial Q."""
+
+    def __init__(self, process_group=None, matrix_approximation_rank=1, start_powerSGD_iter=1000,
+                 min_compression_rate=2, use_error_feedback=True, warm_start=True, orthogonalization_epsilon=0,
+                 random_seed=0):
+        if (use_error_feedback or warm_start) and start_powerSGD_iter <= 1:
+            raise ValueError("Expect `start_powerSGD_iter` > 1 if `use_error_feedback` or `warm_start` is enabled, "
+                             "because PowerSGD can only be applied after the first two iterations in DDP.")
+        if not isinstance(matrix_approximation_rank, int) or not 1 <= matrix_approximation_rank <= 4:
+            raise ValueError(f"matrix_approximation_rank must be an integer in [1, 4], not "
+                             f"{matrix_approximation_rank!r}")
+        if not min_compression_rate > 0 or orthogonalization_epsilon < 0:
+            raise ValueError("min_compression_rate must be positive and orthogonalization_epsilon not negative")
+        if not warm_start:
+            raise NotImplementedError("PowerSGDState(warm_start=False) is not supported: it would draw a new Q on "
+                                      "the host at every step")
+        self.process_group = process_group
+        self.matrix_approximation_rank = matrix_approximation_rank
+        self.start_powerSGD_iter = int(start_powerSGD_iter)
+        self.min_compression_rate = min_compression_rate
+        self.use_error_feedback = bool(use_error_feedback)
+        self.warm_start = True
+        self.orthogonalization_epsilon = float(orthogonalization_epsilon)
+        self.random_seed = int(random_seed)
+        self.iter = 0
+
+
+def _torch_powersgd():
+    try:
+        from torch.distributed.algorithms.ddp_comm_hooks import powerSGD_hook as mod
+    except ImportError:  # a torch built without distributed support
+        return None
+    return mod
+
+
 def resolve_comm_hook(hook):
     """The module's ``grad_compression`` for a communication hook: "bf16" for ``bf16_compress_hook``, None for
-    ``allreduce_hook`` -- this module's sentinels or, by identity, the functions of the same names in
-    ``torch.distributed.algorithms.ddp_comm_hooks.default_hooks``. Any other hook is refused: the native Reducer
-    runs no Python between a bucket's gradients and its collective."""
+    ``allreduce_hook``, "powersgd" for ``powerSGD_hook`` -- this module's sentinels or, by identity, the functions of
+    the same names in ``torch.distributed.algorithms.ddp_comm_hooks`` (``default_hooks``, ``powerSGD_hook``). Any
+    other hook is refused: the native Reducer runs no Python between a bucket's gradients and its collective."""
     if hook is bf16_compress_hook:
         return "bf16"
     if hook is allreduce_hook:
         return None
+    if hook is powerSGD_hook:
+        return "powersgd"
+    torch_psgd = _torch_powersgd()
+    if torch_psgd is not None and hook is torch_psgd.powerSGD_hook:
+        return "powersgd"
     try:
         from torch.distributed.algorithms.ddp_comm_hooks import default_hooks as torch_hooks
     except ImportError:  # a torch built without distributed support
@@ -377,11 +433,24 @@ class DistributedDataParallel(nn.Module):
         return self.module.accumulate()
 
     def register_comm_hook(self, state, hook) -> None:
-        """torch's ``DistributedDataParallel.register_comm_hook(state, hook)`` for the two hooks the native Reducer
+        """torch's ``DistributedDataParallel.register_comm_hook(state, hook)`` for the hooks the native side
         implements (``resolve_comm_hook``): ``bf16_compress_hook`` turns bf16 compression of the bucket all-reduces
-        on (``module.grad_compression = "bf16"``), ``allreduce_hook`` turns it off. `state` (a process group in
-        torch) is ignored: the buckets are reduced on this wrapper's communicator."""
-        self.module.grad_compression = resolve_comm_hook(hook)
+        on (``module.grad_compression = "bf16"``), ``allreduce_hook`` turns it off; for both `state` (a process
+        group in torch) is ignored: the buckets are reduced on this wrapper's communicator. ``powerSGD_hook`` takes
+        a ``PowerSGDState`` (this module's or torch's, read by the same attribute names) and arms PowerSGD
+        (``module.grad_compression = "powersgd"``, nn.PowerSGD)."""
+        kind = resolve_comm_hook(hook)
+        psgd = None
+        if kind == "powersgd":
+            torch_psgd = _torch_powersgd()
+            if not isinstance(state, PowerSGDState) and not (torch_psgd is not None
+                                                             and isinstance(state, torch_psgd.PowerSGDState)):
+                raise TypeError(f"powerSGD_hook needs a PowerSGDState (dtc.parallel's or torch's), not {state!r}")
+            from .nn import PowerSGD
+
+            psgd = PowerSGD(state)
+        self.module._powersgd = psgd
+        self.module.grad_compression = kind
 
     @property
     def buckets(self):

@@ -24,7 +24,7 @@ from .amp import GradScaler, autocast
 from .ema import ModelEma
 from .nn import CrossEntropyLoss, ResNet18, SyncBatchNorm
 from .optim import LARS, SAM, SGD, Adam, AdamW, clip_grad_norm_
-from .parallel import DDP, DataParallel, barrier, bf16_compress_hook
+from .parallel import DDP, DataParallel, PowerSGDState, barrier, bf16_compress_hook, powerSGD_hook
 
 
 def load_config(argv=None, mode: str = "ddp"):
@@ -45,9 +45,15 @@ def load_config(argv=None, mode: str = "ddp"):
         p.add_argument("--sync-bn", action="store_true", default=False,
                        help="SyncBatchNorm.convert_sync_batchnorm (README.md:40; off in the reference)")
         # not in the reference: torch's ddp.register_comm_hook(None, default_hooks.bf16_compress_hook)
-        p.add_argument("--grad-compress", choices=("none", "bf16"), default="none",
+        p.add_argument("--grad-compress", choices=("none", "bf16", "powersgd"), default="none",
                        help="bf16: all-reduce the gradient buckets in bf16 (half the bytes per step); the optimizer "
-                            "still reads fp32 gradients")
+                            "still reads fp32 gradients. powersgd: rank-r PowerSGD with error feedback (torch's "
+                            "powerSGD_hook): two all-reduces of tens of kilobytes per step after the start iteration")
+        p.add_argument("--powersgd-rank", type=int, default=2, choices=(1, 2, 3, 4),
+                       help="--grad-compress powersgd: matrix_approximation_rank")
+        p.add_argument("--powersgd-start-iter", type=int, default=1000,
+                       help="--grad-compress powersgd: start_powerSGD_iter, the plain all-reduced steps before the "
+                            "compression starts (at least 2)")
     p.add_argument("--epoch", type=int, default=200 if mode == "single" else 100)
     p.add_argument("--batch-size", type=int, default=128)
     p.add_argument("--model", type=str, default="resnet18")
@@ -125,6 +131,8 @@ def load_config(argv=None, mode: str = "ddp"):
         p.error("--label-smoothing must be in [0, 1]")
     if h.mixup_alpha < 0 or h.cutmix_alpha < 0 or not 0.0 <= h.mix_prob <= 1.0:
         p.error("--mixup-alpha / --cutmix-alpha must be >= 0 and --mix-prob in [0, 1]")
+    if mode == "ddp" and h.powersgd_start_iter < 2:
+        p.error("--powersgd-start-iter must be at least 2")
     if h.warmup_epochs < 0 or not h.lars_trust_coef > 0:
         p.error("--warmup-epochs must be >= 0 and --lars-trust-coef > 0")
     if (h.mixup_alpha > 0 or h.cutmix_alpha > 0) and not h.device_data:
@@ -228,6 +236,10 @@ class Trainer:
             self.model = DDP(self.model, device_ids=[rank], find_unused_parameters=True)   # ddp/trainer.py:31
             if getattr(hparams, "grad_compress", "none") == "bf16":
                 self.model.register_comm_hook(None, bf16_compress_hook)
+            elif getattr(hparams, "grad_compress", "none") == "powersgd":
+                self.model.register_comm_hook(PowerSGDState(matrix_approximation_rank=hparams.powersgd_rank,
+                                                            start_powerSGD_iter=hparams.powersgd_start_iter),
+                                              powerSGD_hook)
             hparams.batch_size = int(hparams.batch_size / ngpus_per_node)                  # ddp/trainer.py:34
         self.scaler = scaler
         self.optimizer, self.lr_scheduler = self.configure_optimizers()

@@ -368,6 +368,55 @@ int dtc_grad_accum_flat(float* acc, float* g, int64_t n, int mode, void* stream)
  * g and acc 16-byte aligned, c 8-byte aligned; [c, c + n) overlapping neither [g, g + n) nor [acc, acc + n). */
 int dtc_grad_compress_bf16(const float* g, const float* acc, uint16_t* c, int64_t n, void* stream);
 int dtc_grad_decompress_bf16(const uint16_t* c, float* g, int64_t n, void* stream);
+/* psgd: PowerSGD rank-r gradient compression (Vogels et al. 2019; torch's ddp_comm_hooks.powerSGD_hook) on the flat
+ * gradient buffer, run after a local backward. The plan is built from a table of tensors in strictly increasing,
+ * non-overlapping order: offset a non-negative multiple of 4 elements, rows, cols >= 1 with rows * cols not
+ * overflowing, 0 <= rank <= min(rows, cols, 4) (rank 0: the tensor is all-reduced as it is), reserved zero,
+ * 1 <= n <= 4096; anything else: DTC_EINVAL and *out = NULL. dtc_psgd_plan_create is pure host code.
+ * dtc_psgd_plan_numel(what): DTC_PSGD_P the elements of all P blocks (sum rows * rank), DTC_PSGD_Q of all Q blocks
+ * (sum cols * rank), DTC_PSGD_UNCOMPRESSED of the rank-0 tensors, DTC_PSGD_STAGING = uncompressed + P,
+ * DTC_PSGD_QSTRIDE the Q count rounded up to a multiple of 4. dtc_psgd_plan_device_bytes / dtc_psgd_plan_bind as
+ * for dtc_segplan (tables, the back-project slots of doubles, arrival counters and per-tensor marks; 16-byte aligned
+ * region; the only copy). Caller-owned fp32 buffers, 16-byte aligned: g (gradients) and e (error feedback, flat
+ * layout, zeroed before the first step; NULL: none), staging [DTC_PSGD_STAGING] = [uncompressed | P], q
+ * [2][DTC_PSGD_QSTRIDE] -- q[0] the warm start (filled by the caller before the first step: the same values on every
+ * rank), q[1] the working copy -- and `state`, 4 int32 words zeroed before the first step (word 0: the next warm
+ * start is q[1], not q[0]; word 1: the last step was non-finite; the host need not read either). One step, every
+ * compressed tensor seen as a row-major rows x cols matrix, A = g + e (one fp32 add), one launch per call:
+ *   dtc_psgd_orthonormalize(DTC_PSGD_Q)  Qh = orthonormalize(state[0] ? q[1] : q[0]) -> q[1]; the source -> q[0]
+ *   dtc_psgd_project                     P = A Qh; staging = [the rank-0 tensors | P]
+ *        -- the caller all-reduces (SUM) staging, DTC_PSGD_STAGING elements --
+ *   dtc_psgd_orthonormalize(DTC_PSGD_P)  Ph = orthonormalize(P) in staging; notes a non-finite P
+ *   dtc_psgd_backproject                 Q = A^T Ph -> q[1]
+ *        -- the caller all-reduces (SUM) q[1] = q + DTC_PSGD_QSTRIDE, DTC_PSGD_Q elements --
+ *   dtc_psgd_reconstruct                 gh = Ph Q^T -> g;  e = __fsub_rn(__fadd_rn(g, e), __fmul_rn(c, gh)) (c: 1 /
+ *                                        world size; bit-defined, no contraction); rank-0 tensors staging -> g
+ * orthonormalize is modified Gram-Schmidt dividing by (norm + epsilon); norm + epsilon == 0 gives a zero column
+ * (torch gives NaN), and a column whose norm fell to 2^-20 of its norm before the projections -- it lay in the span
+ * of its predecessors, what is left is rounding noise -- is divided by that earlier norm, so it stays negligible. Dot products are summed in double in a fixed order and rounded to fp32 once; the back-project
+ * splits the rows over workgroups with one slot per chunk, folded in index order. No floating-point atomics: every
+ * result is bit-identical from run to run. Elements between the tensors are neither read nor written.
+ * If the all-reduced P or Q holds a non-finite value (the same verdict on every rank) dtc_psgd_reconstruct writes NaN
+ * into the compressed tensors' gradients and leaves e bit-unchanged, q[0] holds the warm start as before the step and
+ * state[0] = 0 selects it for the next; after a finite step state[0] = 1. No host synchronisation. Requires (else
+ * DTC_EINVAL, before any device call): non-NULL, 16-byte aligned pointers (e may be NULL); a bound plan; what in
+ * {DTC_PSGD_Q, DTC_PSGD_P}; epsilon >= 0; 0 < c <= 1. A plan serves one stream at a time. */
+typedef struct { int64_t offset, rows, cols; int32_t rank; int32_t reserved; } dtc_psgd_tensor;
+enum { DTC_PSGD_P = 0, DTC_PSGD_Q = 1, DTC_PSGD_UNCOMPRESSED = 2, DTC_PSGD_STAGING = 3, DTC_PSGD_QSTRIDE = 4 };
+typedef struct dtc_psgd_plan dtc_psgd_plan;
+int dtc_psgd_plan_create(dtc_psgd_plan** out, const dtc_psgd_tensor* tensors_host, int n);
+int dtc_psgd_plan_destroy(dtc_psgd_plan* plan);
+int64_t dtc_psgd_plan_numel(const dtc_psgd_plan* plan, int what);
+size_t dtc_psgd_plan_device_bytes(const dtc_psgd_plan* plan);
+int dtc_psgd_plan_bind(dtc_psgd_plan* plan, void* dev, size_t bytes, void* stream);
+int dtc_psgd_orthonormalize(dtc_psgd_plan* plan, int what, float* q, float* staging, int* state, double epsilon,
+                            void* stream);
+int dtc_psgd_project(dtc_psgd_plan* plan, const float* g, const float* e, const float* q, float* staging,
+                     void* stream);
+int dtc_psgd_backproject(dtc_psgd_plan* plan, const float* g, const float* e, const float* staging, float* q,
+                         void* stream);
+int dtc_psgd_reconstruct(dtc_psgd_plan* plan, float* g, float* e, const float* staging, const float* q, int* state,
+                         double c, void* stream);
 /* sam: sharpness-aware minimisation (SAM, Foret et al. 2021) and its scale-adaptive form (ASAM, Kwon et al. 2021)
  * over the whole flat buffers (n a positive multiple of 4; alignment padding holds zeros in p and g and so is not
  * moved). dtc_sam_perturb, after the first backward, with m = *gmul (NULL: 1; GradScaler's 1 / scale):
