@@ -21,6 +21,7 @@ from .ema import ModelEma  # noqa: F401
 from .optim import LARS, SAM, SGD, Adam, AdamW, clip_grad_norm_  # noqa: F401
 from .parallel import DDP, Comm, DataParallel, DistributedDataParallel, barrier  # noqa: F401
 from . import parallel  # noqa: F401
+from . import checkpoint  # noqa: F401
 from . import trainer  # noqa: F401
 
 _sys.modules.setdefault("dtc_amd", _sys.modules[__name__])

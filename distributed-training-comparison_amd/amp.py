@@ -44,6 +44,7 @@ class GradScaler:
         self._growth = float(growth_factor)
         self._backoff = float(backoff_factor)
         self._interval = int(growth_interval)
+        self._init_tracker = 0  # load_state_dict before the device words exist: the tracker they start from
         self._scale = None
         self._inv_scale = None
         self._tracker = None
@@ -55,7 +56,7 @@ class GradScaler:
         if self._scale is None:
             self._scale = torch.full((1,), self._init_scale, dtype=torch.float32, device=device)
             self._inv_scale = torch.full((1,), 1.0 / self._init_scale, dtype=torch.float32, device=device)
-            self._tracker = torch.zeros(1, dtype=torch.int32, device=device)
+            self._tracker = torch.full((1,), self._init_tracker, dtype=torch.int32, device=device)
             self._found_inf = torch.zeros(1, dtype=torch.int32, device=device)
             _PRESCALER[0] = weakref.ref(self)
 
@@ -115,4 +116,27 @@ class GradScaler:
     def state_dict(self):
         return {"scale": self.get_scale(), "growth_factor": self._growth, "backoff_factor": self._backoff,
                 "growth_interval": self._interval,
-                "_growth_tracker": 0 if self._tracker is None else int(self._tracker.item())}
+                "_growth_tracker": self._init_tracker if self._tracker is None else int(self._tracker.item())}
+
+    def load_state_dict(self, state_dict) -> None:
+        """torch's ``GradScaler.load_state_dict``: the keys ``state_dict()`` writes. Before the device words exist
+        the values are kept for ``_lazy_init``; afterwards the words are filled (``_inv_scale`` as 1 / scale).
+        ``found_inf`` is not state: ``update()`` clears it at the end of every step."""
+        if not self._enabled:
+            return
+        missing = [k for k in ("scale", "growth_factor", "backoff_factor", "growth_interval", "_growth_tracker")
+                   if k not in state_dict]
+        if missing:
+            raise KeyError(f"GradScaler.load_state_dict: missing {missing}")
+        scale, tracker = float(state_dict["scale"]), int(state_dict["_growth_tracker"])
+        if not scale > 0.0 or tracker < 0:
+            raise ValueError(f"GradScaler.load_state_dict: scale {scale} / _growth_tracker {tracker} out of range")
+        self._growth = float(state_dict["growth_factor"])
+        self._backoff = float(state_dict["backoff_factor"])
+        self._interval = int(state_dict["growth_interval"])
+        self._init_scale, self._init_tracker = scale, tracker
+        if self._scale is not None:
+            self._scale.fill_(scale)
+            self._inv_scale.fill_(1.0 / scale)
+            self._tracker.fill_(tracker)
+        self._version += 1  # the scale may have changed: prescaled losses are stale

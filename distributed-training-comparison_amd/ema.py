@@ -89,6 +89,21 @@ class ModelEma:
                 view.copy_(state_dict[key])
         ops.cast_f32_bf16(self.params, self.params_bf16)
 
+    def train_state(self) -> dict:
+        """What a resumed run needs beyond ``state_dict()``: the weights and the update count, which the warm-up
+        decay depends on (a host synchronisation). The bf16 copy is not stored: every update writes it as the
+        rounding of the fp32 EMA, which ``load_state_dict`` repeats."""
+        return {"weights": self.state_dict(), "num_updates": self.num_updates}
+
+    def load_train_state(self, state) -> None:
+        """Load ``train_state()``: the weights as ``load_state_dict`` and word 0 of the device record (the tick
+        kernel writes the rest ahead of every update)."""
+        n = int(state["num_updates"])
+        if n < 0:
+            raise ValueError(f"ModelEma.load_train_state: num_updates = {n}")
+        self.load_state_dict(state["weights"])
+        self.state[:1].copy_(torch.tensor([n], dtype=torch.int32))
+
     def copy_to(self, model=None) -> None:
         """Copy the EMA parameters, bf16 copy and running statistics into `model` (default: the tracked one)."""
         if model is None:

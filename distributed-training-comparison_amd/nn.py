@@ -325,7 +325,7 @@ class PowerSGD:
     leaves the error buffer and the warm-start Q as they were. A change of the loss scale leaves the error buffer
     in the old scale for one step, as in torch."""
 
-    def __init__(self, state):
+    def __init__(self, state, flat: Optional["FlatState"] = None):
         rank = getattr(state, "matrix_approximation_rank")
         if not isinstance(rank, int) or not 1 <= rank <= ops.PSGD_MAX_RANK:
             raise ValueError(f"matrix_approximation_rank must be an integer in [1, {ops.PSGD_MAX_RANK}] (the "
@@ -346,6 +346,7 @@ class PowerSGD:
         if not hasattr(state, "iter"):
             state.iter = 0
         self.plan = self.staging = self.q = self.dev_state = None
+        self.flat = flat  # the model's flat buffers: given here, or known from the first compressed step
 
     def take(self) -> bool:
         """Count one reducing backward; True when it is a compressed one."""
@@ -353,12 +354,64 @@ class PowerSGD:
         self.state.iter += 1
         return compress
 
+    def _setup(self, flat: "FlatState") -> None:
+        self.flat = flat
+        self.plan = ops.psgd_plan(flat.layout, self.rank, self.min_compression_rate, flat.device)
+        self.staging, self.q, self.dev_state = ops.psgd_buffers(self.plan, self.seed, flat.device)
+        if self.error_feedback:
+            flat.grad_err  # noqa: B018 - allocated here, not inside a later step
+
+    def _shape(self) -> dict:
+        """The hyperparameters that shape the plan and the buffers: a saved state loads only under the same ones."""
+        return {"matrix_approximation_rank": self.rank, "min_compression_rate": self.min_compression_rate,
+                "use_error_feedback": self.error_feedback, "random_seed": self.seed}
+
+    def state_dict(self) -> dict:
+        """What a resumed run needs: ``iter`` and, once a compressed step has run, the plan-shaping hyperparameters,
+        both copies of Q (``q``), the device record that says which copy is the warm start (``dev_state``) and,
+        with error feedback, THIS RANK's ``flat.grad_err`` -- the only entry that differs between the ranks. The
+        tensors are the live device buffers (copy to keep). ``staging`` is scratch: every step writes it whole
+        before reading it (csrc/powersgd.hip, steps 2 and 3)."""
+        out = {"iter": int(self.state.iter)}
+        if self.plan is None:
+            return out
+        out.update(self._shape(), q=self.q, dev_state=self.dev_state)
+        if self.error_feedback:
+            out["grad_err"] = self.flat.grad_err
+        return out
+
+    @torch.no_grad()
+    def load_state_dict(self, state, flat: Optional["FlatState"] = None) -> None:
+        """Load ``state_dict()``. A state saved after a compressed step builds the plan and the buffers first (on
+        `flat`, or the buffers already known) and is refused under other plan-shaping
+        hyperparameters; one saved before it only sets ``iter``."""
+        if "q" in state:
+            diff = {k: (state.get(k), v) for k, v in self._shape().items() if state.get(k) != v}
+            if diff:
+                raise ValueError("PowerSGD.load_state_dict: the state was saved under other hyperparameters: "
+                                 + ", ".join(f"{k} = {a!r} (now {b!r})" for k, (a, b) in diff.items()))
+            flat = flat if flat is not None else self.flat
+            if flat is None:
+                raise NativeError("PowerSGD.load_state_dict: the model's flat buffers are not known yet (load "
+                                  "through DistributedDataParallel.load_comm_hook_state_dict)")
+            if self.error_feedback and "grad_err" not in state:
+                raise KeyError("PowerSGD.load_state_dict: use_error_feedback is on but the state has no 'grad_err'")
+            if self.plan is None:
+                self._setup(flat)
+            pairs = [(self.q, state["q"], "q"), (self.dev_state, state["dev_state"], "dev_state")]
+            if self.error_feedback:
+                pairs.append((flat.grad_err, state["grad_err"], "grad_err"))
+            for own, t, name in pairs:
+                if tuple(t.shape) != tuple(own.shape) or t.dtype != own.dtype:
+                    raise ValueError(f"PowerSGD.load_state_dict: {name!r} is {t.dtype} {tuple(t.shape)}, expected "
+                                     f"{own.dtype} {tuple(own.shape)}")
+            for own, t, _ in pairs:
+                own.copy_(t)
+        self.state.iter = int(state["iter"])
+
     def step(self, flat: "FlatState", comm) -> None:
         if self.plan is None:
-            self.plan = ops.psgd_plan(flat.layout, self.rank, self.min_compression_rate, flat.device)
-            self.staging, self.q, self.dev_state = ops.psgd_buffers(self.plan, self.seed, flat.device)
-            if self.error_feedback:
-                flat.grad_err  # noqa: B018 - allocated here, not inside a later step
+            self._setup(flat)
         world = comm.world if comm is not None else 1
         ops.psgd_step(self.plan, flat.grads, flat.grad_err if self.error_feedback else None, self.staging, self.q,
                       self.dev_state, 1.0 / world, self.eps, comm.allreduce_sum_ if comm is not None else None)

@@ -14,6 +14,8 @@ reads them. ``p.grad`` keeps showing the unclipped gradients.
 """
 from __future__ import annotations
 
+import copy
+
 import torch
 from torch.optim import Optimizer
 
@@ -70,6 +72,103 @@ class _FlatOptimizer(Optimizer):
         # the state zero_grad() + backward() produces in the reference; nothing to clear.
         return None
 
+    # ------------------------------------------------------------------ state_dict, in torch's format
+    # (key of torch's per-parameter state, attribute holding the flat fp32 buffer), per subclass
+    _STATE_BUFFERS = ()
+
+    def _check_group(self, group) -> None:
+        """Refuse hyperparameters the fused kernel does not implement (load_state_dict takes them from a file)."""
+
+    def _get_step(self):
+        """The step count torch keeps per parameter (Adam), or None for optimizers that keep none."""
+        return None
+
+    def _set_step(self, step: int) -> None:
+        pass
+
+    def _param_infos(self, flat):
+        """The layout entry of every parameter of the group, in the group's order (the order of
+        ``named_parameters()`` for ``model.parameters()``), found by the address of the parameter's view."""
+        base = flat.params.data_ptr()
+        by_ptr = {base + 4 * q.offset: q for q in flat.layout.params}
+        return [by_ptr[p.data_ptr()] for p in self.param_groups[0]["params"]]
+
+    @staticmethod
+    def _view(buf, q):
+        return torch.as_strided(buf, q.shape, q.stride, q.offset)
+
+    def state_dict(self):
+        """torch's ``Optimizer.state_dict()``: ``state[i]`` of the i-th parameter holds views of the flat state
+        buffers in the parameter's logical shape (conv weights: strided [K,C,R,S] views over the KRSC storage),
+        under ``torch.optim``'s keys, so the dict loads into ``torch.optim`` over the reference model and back.
+        Adam's ``step`` is read from the device record: one host synchronisation. Before the first step (nothing
+        attached): torch's shell with an empty ``state``."""
+        out = super().state_dict()
+        if self._flat is None:
+            return out
+        step = self._get_step()
+        state = {}
+        for i, q in enumerate(self._param_infos(self._flat)):
+            entry = {} if step is None else {"step": torch.tensor(float(step), dtype=torch.float32)}
+            for key, attr in self._STATE_BUFFERS:
+                entry[key] = self._view(getattr(self, attr), q)
+            state[i] = entry
+        out["state"] = state
+        return out
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict) -> None:
+        """torch's ``Optimizer.load_state_dict()`` on the flat buffers: binds to the model first (parameters of no
+        native model: NativeError), copies every per-parameter entry into its view of the state buffer -- the
+        alignment padding between the parameters is never written -- and takes the hyperparameters of
+        ``param_groups``. The group dicts are updated IN PLACE: SAM shares the list, schedulers hold the optimizer.
+        An empty ``state`` (saved before the first step) resets the buffers. Everything is checked before anything
+        is written."""
+        who = type(self).__name__
+        if self._flat is None:
+            self.attach(self._find_flat())
+        flat = self._flat
+        groups = state_dict["param_groups"]
+        if len(groups) != 1:
+            raise ValueError(f"{who}.load_state_dict: {len(groups)} parameter groups, expected 1")
+        infos = self._param_infos(flat)
+        if len(groups[0]["params"]) != len(infos):
+            raise ValueError(f"{who}.load_state_dict: the state holds {len(groups[0]['params'])} parameters, the "
+                             f"model has {len(infos)}")
+        new_group = {k: copy.deepcopy(v) for k, v in groups[0].items() if k != "params"}
+        self._check_group({**self.param_groups[0], **new_group})
+        saved = state_dict["state"]
+        ids = list(groups[0]["params"])  # torch's packed ids: position i holds the key of parameter i
+        copies, step = [], None
+        for i, q in enumerate(infos if len(saved) else ()):
+            if ids[i] not in saved:
+                raise KeyError(f"{who}.load_state_dict: no state for parameter {i} ({q.name})")
+            entry = saved[ids[i]]
+            for key, attr in self._STATE_BUFFERS:
+                if key not in entry:
+                    raise KeyError(f"{who}.load_state_dict: parameter {i} ({q.name}) has no {key!r}")
+                t = entry[key]
+                if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(q.shape):
+                    raise ValueError(f"{who}.load_state_dict: {key!r} of parameter {i} ({q.name}) has shape "
+                                     f"{tuple(getattr(t, 'shape', ()))}, expected {tuple(q.shape)}")
+                copies.append((attr, q, t))
+            if self._get_step() is not None:
+                if "step" not in entry:
+                    raise KeyError(f"{who}.load_state_dict: parameter {i} ({q.name}) has no 'step'")
+                s = float(entry["step"])  # a tensor or a number
+                if s < 0 or s != int(s) or (step is not None and s != step):
+                    raise ValueError(f"{who}.load_state_dict: 'step' of parameter {i} ({q.name}) is {s}; the fused "
+                                     f"kernel keeps one non-negative integer count for all parameters")
+                step = s
+        if not len(saved):
+            for _, attr in self._STATE_BUFFERS:
+                getattr(self, attr).zero_()
+            step = 0
+        for attr, q, t in copies:
+            self._view(getattr(self, attr), q).copy_(t)
+        self._set_step(int(step or 0))
+        self.param_groups[0].update(new_group)
+
     @torch.no_grad()
     def step(self, closure=None, inv_scale=None, found_inf=None):
         if closure is not None:
@@ -92,6 +191,13 @@ class SGD(_FlatOptimizer):
             raise NotImplementedError("the fused kernel implements SGD(momentum>0, dampening=0, nesterov=True) "
                                       "as used by the reference (trainer.py:92-98)")
         self._mom = None
+
+    _STATE_BUFFERS = (("momentum_buffer", "_mom"),)
+
+    def _check_group(self, g):
+        if not g["nesterov"] or g["dampening"] != 0.0 or g["momentum"] <= 0.0 or g.get("maximize", False):
+            raise NotImplementedError("the fused kernel implements SGD(momentum>0, dampening=0, nesterov=True, "
+                                      "maximize=False)")
 
     def _init_state(self, flat):
         self._mom = torch.zeros_like(flat.params)
@@ -122,6 +228,20 @@ class Adam(_FlatOptimizer):
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize)
         super().__init__(params, defaults)
         self._exp_avg = self._exp_avg_sq = self._step_state = None
+
+    _STATE_BUFFERS = (("exp_avg", "_exp_avg"), ("exp_avg_sq", "_exp_avg_sq"))
+
+    def _check_group(self, g):
+        if g.get("amsgrad", False) or g.get("maximize", False):
+            raise NotImplementedError("the fused kernel implements amsgrad=False, maximize=False")
+
+    def _get_step(self):
+        """Word 0 of the device record (a host synchronisation); 0 before the record exists."""
+        return 0 if self._step_state is None else int(self._step_state[0].item())
+
+    def _set_step(self, step: int) -> None:
+        # only the count: the tick kernel recomputes the factors that depend on it ahead of every update
+        self._step_state[:1].copy_(torch.tensor([step], dtype=torch.int32))
 
     def _init_state(self, flat):
         self._exp_avg = torch.zeros_like(flat.params)
@@ -168,6 +288,8 @@ class LARS(_FlatOptimizer):
                         trust_coef=trust_coef, eps=eps, trust_clip=trust_clip)
         super().__init__(params, defaults)
         self._mom = self._plan = self._norms = None
+
+    _STATE_BUFFERS = (("momentum_buffer", "_mom"),)  # (_norms is rewritten whole by every step)
 
     def _init_state(self, flat):
         self._mom = torch.zeros_like(flat.params)
@@ -238,6 +360,20 @@ class SAM(Optimizer):
 
     def zero_grad(self, set_to_none: bool = True):
         return self.base.zero_grad(set_to_none)
+
+    def _refuse_perturbed(self, what: str) -> None:
+        if self._perturbed:
+            raise NativeError(f"SAM.{what}: the weights are perturbed between first_step() and step(); call it "
+                              "after step()")
+
+    def state_dict(self):
+        """The base optimizer's (SAM keeps no state of its own across steps)."""
+        self._refuse_perturbed("state_dict")
+        return self.base.state_dict()
+
+    def load_state_dict(self, state_dict) -> None:
+        self._refuse_perturbed("load_state_dict")
+        self.base.load_state_dict(state_dict)
 
     def _keep(self, flat):
         _, _, bufs_saved, nbt_saved = self._saved

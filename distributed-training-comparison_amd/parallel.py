@@ -452,6 +452,23 @@ class DistributedDataParallel(nn.Module):
         self.module._powersgd = psgd
         self.module.grad_compression = kind
 
+    def comm_hook_state_dict(self) -> dict:
+        """The state of the registered communication hook that a resumed run needs. PowerSGD: nn.PowerSGD.state_dict
+        (``iter``, Q, the device record, this rank's error-feedback buffer: per rank, so every rank saves its own).
+        The other hooks keep none: an empty dict."""
+        psgd = self.module._powersgd
+        return psgd.state_dict() if psgd is not None else {}
+
+    def load_comm_hook_state_dict(self, state) -> None:
+        """Load ``comm_hook_state_dict()`` into the hook registered on this wrapper (register it first)."""
+        psgd = self.module._powersgd
+        if psgd is None:
+            if state:
+                raise NativeError("load_comm_hook_state_dict: the state is PowerSGD's but no powerSGD_hook is "
+                                  "registered on this wrapper")
+            return
+        psgd.load_state_dict(state, self.module.flat)
+
     @property
     def buckets(self):
         return self.module.buckets()

@@ -14,11 +14,14 @@ import glob
 import json
 import logging
 import os
+import re
+import time
 from typing import Tuple
 
 import torch
 import torch.distributed as dist
 
+from . import checkpoint
 from . import data as D
 from .amp import GradScaler, autocast
 from .ema import ModelEma
@@ -123,6 +126,14 @@ def load_config(argv=None, mode: str = "ddp"):
     p.add_argument("--fused-eval", action="store_true", default=False,
                    help="validate()/test() on the device: one native call per batch (eval forward + loss + top-k "
                         "counts), one device-to-host copy per evaluation (ResNet.evaluate); same numbers")
+    # not in the reference, which saves the best epoch's weights and cannot continue a run
+    p.add_argument("--checkpoint-every", type=int, default=0,
+                   help="write the full training state to <version dir>/last.ckpt after every N-th epoch and after "
+                        "the last one (0 = off; single and ddp only)")
+    p.add_argument("--resume", type=str, default=None, metavar="PATH",
+                   help="continue the run of a version directory (or its last.ckpt) in that directory, bit for bit "
+                        "as if it had not stopped; the flags that shape the state must be the saved run's, --epoch "
+                        "may be raised (single and ddp only)")
     if mode == "dp":  # not in the reference (nn.DataParallel takes every visible GPU): replica placement
         p.add_argument("--device-ids", type=lambda v: [int(d) for d in v.split(",")], default=None,
                        help="comma-separated GPU ids of the replicas (may repeat); default: all visible")
@@ -155,7 +166,50 @@ def load_config(argv=None, mode: str = "ddp"):
         p.error("--sam-rho is not available with --accum-steps > 1 (its first backward is a whole step's gradient)")
     if h.sam_rho > 0 and mode == "dp":
         p.error("--sam-rho is not available under DataParallel (single and ddp only)")
+    if h.checkpoint_every < 0:
+        p.error("--checkpoint-every must be >= 0")
+    if mode == "dp" and (h.checkpoint_every > 0 or h.resume is not None):
+        p.error("--checkpoint-every / --resume are not available under DataParallel (single and ddp only)")
     return h
+
+
+# The flags a resumed run must share with the run that wrote the checkpoint: they shape the saved state (which
+# optimizer, scaler, EMA, hook state exist and what they mean) or the data stream of the epochs still to come.
+# --epoch, --eval-step, --contain-test, --workers, --checkpoint-every, --max-steps, --fused-eval, the paths and the
+# process-group address may differ.
+RESUME_KEYS = (
+    "dset", "model", "seed", "batch_size", "synthetic_train", "device_data", "amp",
+    "optimizer", "lr", "weight_decay", "lars_trust_coef", "lars_clip", "clip_grad_norm",
+    "lr_decay_step_size", "lr_decay_gamma", "warmup_epochs",
+    "label_smoothing", "mixup_alpha", "cutmix_alpha", "mix_prob",
+    "auto_augment", "ra_num_ops", "ra_magnitude", "random_erasing",
+    "model_ema", "model_ema_decay", "model_ema_warmup", "model_ema_steps",
+    "accum_steps", "sam_rho", "sam_adaptive",
+    "world_size", "sync_bn", "grad_compress", "powersgd_rank", "powersgd_start_iter",
+)
+
+
+def hparam_mismatch(saved: dict, current: dict) -> list:
+    """[(key, saved value, current value)] over RESUME_KEYS, in their order; a key neither side has (a flag of
+    another mode) is equal."""
+    missing = object()
+    out = []
+    for k in RESUME_KEYS:
+        a, b = saved.get(k, missing), current.get(k, missing)
+        if a is missing and b is missing:
+            continue
+        if a is missing or b is missing or a != b:
+            out.append((k, None if a is missing else a, None if b is missing else b))
+    return out
+
+
+def resolve_resume(path: str) -> Tuple[str, str]:
+    """(version directory, checkpoint file) of --resume PATH, a version directory or its last.ckpt."""
+    file = os.path.join(path, "last.ckpt") if os.path.isdir(path) else path
+    if not os.path.isfile(file):
+        raise checkpoint.CheckpointError(f"--resume {path}: there is no last.ckpt (was the run started with "
+                                         "--checkpoint-every?)")
+    return os.path.dirname(os.path.abspath(file)), file
 
 
 def accuracy(output, target, topk=(1,)):
@@ -228,6 +282,12 @@ class Trainer:
         self.rank = rank
         self.distributed = distributed
         self.data_parallel = data_parallel
+        self.checkpoint_every = int(getattr(hparams, "checkpoint_every", 0) or 0)
+        self.start_epoch = 0
+        resume = None
+        if getattr(hparams, "resume", None):  # read on every rank, before anything is built
+            resume_dir, resume_file = resolve_resume(hparams.resume)
+            resume = checkpoint.load(resume_file)
         self.device = torch.device("cuda", rank if distributed else torch.cuda.current_device())
         self.model = model.to(self.device)
         if data_parallel:
@@ -241,6 +301,12 @@ class Trainer:
                                                             start_powerSGD_iter=hparams.powersgd_start_iter),
                                               powerSGD_hook)
             hparams.batch_size = int(hparams.batch_size / ngpus_per_node)                  # ddp/trainer.py:34
+        if resume is not None:
+            diff = hparam_mismatch(resume["extra"]["hparams"], vars(hparams))
+            if diff:
+                raise checkpoint.CheckpointError(
+                    f"--resume {hparams.resume}: the checkpoint was written under other flags: "
+                    + "; ".join(f"{k}: saved {a!r}, now {b!r}" for k, a, b in diff))
         self.scaler = scaler
         self.optimizer, self.lr_scheduler = self.configure_optimizers()
         self.criterion, self.eval_criterion = make_criteria(hparams)
@@ -269,19 +335,87 @@ class Trainer:
         self.global_top1_acc = 0.0
         self.eval_step = hparams.eval_step
         self.version = None
+        if resume is not None:  # the run goes on in its own directory (every rank knows it)
+            self.save_path = resume_dir
         if rank == 0:
-            self.version = 0
-            while True:
-                self.save_path = os.path.join(hparams.ckpt_path, f"version-{self.version}")
-                if not os.path.exists(self.save_path):
-                    os.makedirs(self.save_path)
-                    break
-                self.version += 1
+            if resume is not None:
+                m = re.fullmatch(r"version-(\d+)", os.path.basename(resume_dir))
+                self.version = int(m.group(1)) if m else None
+            else:
+                self.version = 0
+                while True:
+                    self.save_path = os.path.join(hparams.ckpt_path, f"version-{self.version}")
+                    if not os.path.exists(self.save_path):
+                        os.makedirs(self.save_path)
+                        break
+                    self.version += 1
             logging.basicConfig(filename=os.path.join(self.save_path, "experiment.log"), level=logging.INFO,
                                 format="%(asctime)s > %(message)s", force=True)
-            with open(os.path.join(self.save_path, "hparams.json"), "w") as f:
-                json.dump(vars(hparams), f, indent=1)
+            if resume is None:  # a resumed run leaves hparams.json as it is
+                with open(os.path.join(self.save_path, "hparams.json"), "w") as f:
+                    json.dump(vars(hparams), f, indent=1)
             self._scalars = open(os.path.join(self.save_path, "scalars.jsonl"), "a")
+        # every rank of a checkpointing ddp run writes a file of its own next to rank 0's (_write_checkpoint)
+        self.global_rank = dist.get_rank() if distributed else 0
+        self._rank_files = distributed and (dist.get_world_size() > 1
+                                            or getattr(hparams, "grad_compress", "none") == "powersgd")
+        if resume is None and self._rank_files and self.checkpoint_every > 0 and dist.get_world_size() > 1:
+            box = [self.save_path if rank == 0 else None]  # rank 0's new directory, for the others' files
+            dist.broadcast_object_list(box, src=0)
+            self.save_path = box[0]
+        if resume is not None:
+            self._restore(resume)
+
+    def _rank_file(self) -> str:
+        return os.path.join(self.save_path, f"last.rank{self.global_rank}.ckpt")
+
+    def _restore(self, state) -> None:
+        """--resume: `state` (last.ckpt, read by every rank) into the freshly built objects, this rank's own file
+        (the PowerSGD hook state with its error-feedback buffer, and this rank's generators) on top; the random
+        generators last, since building the model and the loaders has drawn from them."""
+        mine = None
+        if self._rank_files:
+            if not os.path.isfile(self._rank_file()):
+                raise checkpoint.CheckpointError(f"--resume: {self._rank_file()} is missing (every rank of a ddp "
+                                                 "run writes one next to last.ckpt)")
+            mine = checkpoint.load(self._rank_file())
+            if mine["epoch"] != state["extra"]["epoch"]:
+                raise checkpoint.CheckpointError(f"--resume: {self._rank_file()} is of epoch {mine['epoch']}, "
+                                                 f"last.ckpt of epoch {state['extra']['epoch']}")
+            self.model.load_comm_hook_state_dict(mine["hook"])
+        extra = checkpoint.restore(state, self.model, self.optimizer, self.scaler, self.ema, self.lr_scheduler)
+        self.start_epoch = int(extra["epoch"])
+        self.global_step, self.optimizer_step = int(extra["global_step"]), int(extra["optimizer_step"])
+        self.global_top1_acc = float(extra["global_top1_acc"])
+        if mine is not None:
+            checkpoint.set_rng_state(mine["rng"])
+        logging.info(f"Resumed from {self.save_path}: next epoch {self.start_epoch}, global step {self.global_step}")
+
+    def _write_checkpoint(self, epoch: int) -> None:
+        """--checkpoint-every N: after epoch `epoch` (the scheduler has stepped) rank 0 writes last.ckpt -- the
+        whole training state plus the next epoch, the step counts, the best accuracy so far with its file's name
+        and the flags --, every rank of a ddp run its last.rank<r>.ckpt first. An epoch boundary is the only point
+        where no gradient-accumulation window, SAM perturbation or pending clip is open."""
+        n = self.checkpoint_every
+        if n <= 0 or not ((epoch + 1) % n == 0 or epoch == self.hparams.epoch - 1):
+            return
+        t0 = time.perf_counter()
+        if self._rank_files:
+            checkpoint.save(self._rank_file(), {
+                checkpoint.FORMAT_KEY: checkpoint.FORMAT, "rank": self.global_rank, "epoch": epoch + 1,
+                "hook": checkpoint.to_plain(self.model.comm_hook_state_dict(), "hook"),
+                "rng": checkpoint.get_rng_state()})
+        if self.rank != 0:
+            return
+        best = glob.glob(os.path.join(self.save_path, "best_model_*.pt"))
+        extra = {"epoch": epoch + 1, "global_step": self.global_step, "optimizer_step": self.optimizer_step,
+                 "global_top1_acc": float(self.global_top1_acc),
+                 "best_model": os.path.basename(best[0]) if best else None, "hparams": vars(self.hparams)}
+        path = os.path.join(self.save_path, "last.ckpt")
+        checkpoint.save(path, checkpoint.capture(self.model, self.optimizer, self.scaler, self.ema,
+                                                 self.lr_scheduler, extra))
+        logging.info(f"Checkpoint after epoch {epoch}: {os.path.getsize(path) / 2 ** 20:.1f} MiB in "
+                     f"{time.perf_counter() - t0:.2f} s")
 
     def _device_loaders(self, hparams, distributed):
         """--device-data: the loaders of dataset.py:15-168 with the transforms on the GPU
@@ -341,7 +475,7 @@ class Trainer:
         self.global_top1_acc = val_acc
 
     def fit(self):
-        for epoch in range(self.hparams.epoch):
+        for epoch in range(self.start_epoch, self.hparams.epoch):
             if self.distributed or isinstance(self.train_loader, D.DeviceLoader):
                 self.train_sampler.set_epoch(epoch)                                       # trainer.py:125
             logging.info(f"* Learning Rate: {self.optimizer.param_groups[0]['lr']:.5f}")
@@ -349,6 +483,7 @@ class Trainer:
             if self.rank == 0 and result["val_acc"] > self.global_top1_acc:
                 self.save_checkpoint(epoch, result["val_acc"], self.model)
             self.lr_scheduler.step()
+            self._write_checkpoint(epoch)
         return self.version
 
     def _backward(self, loss, closing: bool) -> None:
@@ -546,9 +681,9 @@ def _run(hparams, rank, ngpus, distributed, data_parallel=False):
     if getattr(hparams, "sync_bn", False):
         model = SyncBatchNorm.convert_sync_batchnorm(model)
     trainer = Trainer(hparams, model, scaler, rank, ngpus, distributed, data_parallel)
-    version = trainer.fit()
+    trainer.fit()
     if rank == 0 and hparams.contain_test:
-        path = glob.glob(os.path.join(hparams.ckpt_path, f"version-{version}/best_model_*.pt"))
+        path = glob.glob(os.path.join(trainer.save_path, "best_model_*.pt"))  # (--resume: not under ckpt_path)
         if path:
             state = torch.load(path[0], weights_only=True)
             print(json.dumps(trainer.test(state)))
