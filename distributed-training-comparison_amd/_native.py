@@ -49,6 +49,18 @@ class ConvDesc(C.Structure):
 PConv = C.POINTER(ConvDesc)
 
 
+class ConvRoute(C.Structure):
+    """dtc_conv_route: what dtc_conv2d_route_query reports (kernel: one of CONV_KERNELS' indices)."""
+
+    _fields_ = [(n, C.c_int) for n in ("kernel", "gemm_bm", "gemm_bn", "splits", "halo_cfg", "halo_gen",
+                                       "reduce_in_kernel", "sc_ok", "refused", "reserved")] + \
+               [("slab_wanted", C.c_size_t), ("slab_used", C.c_size_t)]
+
+
+CONV_KERNELS = ("GEMM", "GEMM_CLASSES", "C64", "HALO", "DGRAD_S2", "WGRAD_HALO", "WGRAD_S2")  # DTC_CONV_K_*
+CONV_ROUTE_RES, CONV_ROUTE_SC = 1, 2
+
+
 class EvalRecord(C.Structure):
     """dtc_eval_record: one evaluation batch's metrics (16 bytes, device memory)."""
 
@@ -103,6 +115,7 @@ _SIGS = {
     "dtc_get_option": (i32, [cstr]),
     "dtc_conv2d_workspace_size": (sz, [PConv, i32]),
     "dtc_conv2d_fwd": (i32, [PConv, vp, vp, vp, vp, vp, sz, vp]),
+    "dtc_conv2d_route_query": (i32, [PConv, i32, i32, i32, vp, sz, C.POINTER(ConvRoute)]),
     "dtc_conv2d_dgrad": (i32, [PConv, vp, vp, vp, vp, vp, sz, vp]),
     "dtc_conv2d_fwd_sc": (i32, [PConv, vp, vp, vp, vp, vp, vp, vp, vp]),
     "dtc_conv2d_dgrad_sc": (i32, [PConv, vp, vp, vp, vp, vp, vp]),

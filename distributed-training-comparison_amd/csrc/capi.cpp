@@ -217,23 +217,81 @@ size_t dtc_conv2d_workspace_size(const dtc_conv_desc* d, int pass) {
 // FWD / DGRAD workspace: [split-K slab][DTC_TICKS u32 arrival counters] when it holds both (the counters of
 // the in-kernel reduction are zeroed on the call's stream first; the workspace is scratch between calls),
 // else the whole of it is slab and a split-K plan reduces in a separate launch. Nothing is carved out (and
-// nothing zeroed) when the plan has no slab or the in-kernel reduction is off (option splitk_ink).
-static unsigned* op_ticks(const dtc_conv_desc* d, int pass, void* ws, size_t& ws_bytes, hipStream_t st) {
-  const size_t tb = (size_t)DTC_TICKS * 4, slab = conv_route(shape_of(d), pass).slab_bytes;
-  if (ws == nullptr || slab == 0 || ws_bytes < slab + tb || option_get(OPT_SPLITK_INK) == 0) return nullptr;
+// nothing zeroed) when the plan has no slab or the in-kernel reduction is off (option splitk_ink). WGRAD: all of
+// it is slab, except that dtc_conv2d_wgrad_sc's size query reserves DTC_TICKS words behind its slab and the entry
+// point holds the caller to that layout. ws_carve is pure (the route query asks it too); op_ws adds the memset.
+struct WsCarve {
+  size_t slab_bytes;  // fp32 slab on hand (0 without a workspace)
+  unsigned* tick;     // the arrival counters, or nullptr
+};
+static WsCarve ws_carve(const dtc_conv_desc* d, int pass, bool sc, const void* ws, size_t ws_bytes) {
+  const size_t tb = (size_t)DTC_TICKS * 4;
+  WsCarve c{ws ? ws_bytes : 0, nullptr};
+  if (pass == CONV_WGRAD) {
+    if (sc) c.slab_bytes = c.slab_bytes >= tb ? c.slab_bytes - tb : 0;
+    return c;
+  }
+  const size_t slab = conv_route(shape_of(d), pass).slab_bytes;
+  if (ws == nullptr || slab == 0 || ws_bytes < slab + tb || option_get(OPT_SPLITK_INK) == 0) return c;
   const uintptr_t end = ((uintptr_t)ws + ws_bytes - tb) & ~(uintptr_t)255;
-  if (end < (uintptr_t)ws + slab) return nullptr;
-  if (hipMemsetAsync((void*)end, 0, tb, st) != hipSuccess) return nullptr;
-  ws_bytes = end - (uintptr_t)ws;
-  return (unsigned*)end;
+  if (end < (uintptr_t)ws + slab) return c;
+  return WsCarve{(size_t)(end - (uintptr_t)ws), (unsigned*)end};
+}
+static WsCarve op_ws(const dtc_conv_desc* d, int pass, void* ws, size_t ws_bytes, hipStream_t st) {
+  const WsCarve c = ws_carve(d, pass, false, ws, ws_bytes);
+  if (c.tick && hipMemsetAsync(c.tick, 0, (size_t)DTC_TICKS * 4, st) != hipSuccess) return WsCarve{ws ? ws_bytes : 0, nullptr};
+  return c;
+}
+
+static_assert(DTC_CONV_K_GEMM == CONV_K_GEMM && DTC_CONV_K_GEMM_CLASSES == CONV_K_GEMM_CLASSES &&
+                  DTC_CONV_K_C64 == CONV_K_C64 && DTC_CONV_K_HALO == CONV_K_HALO &&
+                  DTC_CONV_K_DGRAD_S2 == CONV_K_DGRAD_S2 && DTC_CONV_K_WGRAD_HALO == CONV_K_WGRAD_HALO &&
+                  DTC_CONV_K_WGRAD_S2 == CONV_K_WGRAD_S2,
+              "DTC_CONV_K_* mirror ConvKernel");
+static int route_answer(const ConvShape& s, int pass, const ConvRequest& rq, bool ticks, dtc_conv_route* out) {
+  const ConvLaunch l = conv_launch(s, pass, rq);
+  const ConvRoute& r = l.route;
+  const bool gemm = r.kernel == CONV_K_GEMM || r.kernel == CONV_K_GEMM_CLASSES;
+  const bool halo = r.kernel == CONV_K_HALO;
+  memset(out, 0, sizeof(*out));
+  out->kernel = r.kernel;
+  out->gemm_bm = gemm ? r.gemm.bm : 0;
+  out->gemm_bn = gemm ? r.gemm.bn : 0;
+  out->splits = gemm ? r.gemm.splits : halo ? r.halo.split : r.splits > 0 ? r.splits : 1;
+  out->halo_cfg = halo ? r.halo.cfg : -1;
+  out->halo_gen = halo ? r.halo.gen : 0;
+  out->reduce_in_kernel = ticks && halo && r.halo.split > 1;
+  out->sc_ok = r.sc_ok;
+  out->refused = l.refused != nullptr;
+  out->slab_wanted = r.slab_bytes;
+  out->slab_used = l.slab_used;
+  return 0;
+}
+
+int dtc_conv2d_route_query(const dtc_conv_desc* d, int pass, int flags, int nprob, const void* ws, size_t ws_bytes,
+                           dtc_conv_route* out) {
+  DTC_CHECK_ARG(d && out, "dtc_conv2d_route_query: null argument");
+  DTC_CHECK_ARG(desc_ok(d), "dtc_conv2d_route_query: unsupported convolution descriptor");
+  const bool res = (flags & DTC_CONV_ROUTE_RES) != 0, sc = (flags & DTC_CONV_ROUTE_SC) != 0;
+  DTC_CHECK_ARG(pass >= 0 && pass <= 2 && nprob >= 1 && nprob <= DTC_WG_BATCH && (flags & ~3) == 0 &&
+                    (!res || pass == CONV_DGRAD) && (nprob == 1 || (pass == CONV_WGRAD && !sc)) && !(res && sc),
+                "dtc_conv2d_route_query: pass %d flags %d nprob %d name no entry point", pass, flags, nprob);
+  const WsCarve c = ws_carve(d, pass, sc, ws, ws_bytes);
+  ConvRequest rq;
+  rq.res = res;
+  rq.sc = sc;
+  rq.nprob = nprob;
+  rq.batch = nprob > 1;
+  rq.slab_bytes = c.slab_bytes;
+  GUARD(return route_answer(shape_of(d), pass, rq, c.tick != nullptr, out);)
 }
 
 int dtc_conv2d_fwd(const dtc_conv_desc* d, const uint16_t* x, const uint16_t* w, uint16_t* y, int64_t* stats, void* ws,
                    size_t ws_bytes, void* stream) {
   DTC_CHECK_ARG(d && x && w && y, "dtc_conv2d_fwd: null argument");
   DTC_CHECK_ARG(desc_ok(d), "dtc_conv2d_fwd: unsupported convolution descriptor");
-  unsigned* tick = op_ticks(d, CONV_FWD, ws, ws_bytes, S(stream));
-  GUARD(return conv_fwd(shape_of(d), x, w, y, stats, (float*)ws, ws ? ws_bytes : 0, S(stream), nullptr, tick);)
+  const WsCarve c = op_ws(d, CONV_FWD, ws, ws_bytes, S(stream));
+  GUARD(return conv_fwd(shape_of(d), x, w, y, stats, (float*)ws, c.slab_bytes, S(stream), nullptr, c.tick);)
 }
 
 int dtc_conv2d_fwd_sc(const dtc_conv_desc* d, const uint16_t* x, const uint16_t* w, uint16_t* y, int64_t* stats,
@@ -249,8 +307,8 @@ int dtc_conv2d_dgrad(const dtc_conv_desc* d, const uint16_t* dy, const uint16_t*
                      void* ws, size_t ws_bytes, void* stream) {
   DTC_CHECK_ARG(d && dy && w && dx, "dtc_conv2d_dgrad: null argument");
   DTC_CHECK_ARG(desc_ok(d), "dtc_conv2d_dgrad: unsupported convolution descriptor");
-  unsigned* tick = op_ticks(d, CONV_DGRAD, ws, ws_bytes, S(stream));
-  GUARD(return conv_dgrad(shape_of(d), dy, w, dx, res, (float*)ws, ws ? ws_bytes : 0, S(stream), nullptr, 0, tick);)
+  const WsCarve c = op_ws(d, CONV_DGRAD, ws, ws_bytes, S(stream));
+  GUARD(return conv_dgrad(shape_of(d), dy, w, dx, res, (float*)ws, c.slab_bytes, S(stream), nullptr, 0, c.tick);)
 }
 
 // the data gradient, then the BN-backward reduction of the post-ReLU BN output it is the gradient of, in place on dx
@@ -262,8 +320,8 @@ int dtc_conv2d_dgrad_bn(const dtc_conv_desc* d, const uint16_t* dy, const uint16
   DTC_CHECK_ARG(desc_ok(d), "dtc_conv2d_dgrad_bn: unsupported convolution descriptor");
   DTC_CHECK_ARG(!x2 || (mean2 && invstd2 && acc2), "dtc_conv2d_dgrad_bn: second BN arguments");
   const ConvShape s = shape_of(d);
-  unsigned* tick = op_ticks(d, CONV_DGRAD, ws, ws_bytes, S(stream));
-  GUARD(DTC_TRY(conv_dgrad(s, dy, w, dx, res, (float*)ws, ws ? ws_bytes : 0, S(stream), nullptr, 0, tick));
+  const WsCarve c = op_ws(d, CONV_DGRAD, ws, ws_bytes, S(stream));
+  GUARD(DTC_TRY(conv_dgrad(s, dy, w, dx, res, (float*)ws, c.slab_bytes, S(stream), nullptr, 0, c.tick));
         return bn_bwd_reduce(dx, ymask, x1, mean1, invstd1, acc1, x2, mean2, invstd2, acc2, dx, (int64_t)s.N * s.H * s.W,
                              s.C, S(stream));)
 }
@@ -292,10 +350,8 @@ int dtc_conv2d_wgrad_sc(const dtc_conv_desc* d, const uint16_t* x, const uint16_
                         float* dw_sc, float scale, void* ws, size_t ws_bytes, void* stream) {
   DTC_CHECK_ARG(d && x && dy && dsc && dw && dw_sc, "dtc_conv2d_wgrad_sc: null argument");
   DTC_CHECK_ARG(desc_ok(d), "dtc_conv2d_wgrad_sc: unsupported convolution descriptor");
-  const ConvShape s = shape_of(d);
-  const ConvRoute r = conv_route(s, CONV_WGRAD);  // (the launch checks the slab it really needs)
-  DTC_CHECK_ARG(r.sc_ok, "dtc_conv2d_wgrad_sc: no fused plan for this geometry");
-  GUARD(return conv_wgrad_s2(s, r.splits, x, dy, dsc, dw, dw_sc, scale, (float*)ws, ws ? ws_bytes : 0, S(stream));)
+  const WsCarve c = ws_carve(d, CONV_WGRAD, true, ws, ws_bytes);
+  GUARD(return conv_wgrad_sc(shape_of(d), x, dy, dsc, dw, dw_sc, scale, (float*)ws, c.slab_bytes, S(stream));)
 }
 
 size_t dtc_conv2d_wgrad_batch_workspace_size(const dtc_conv_desc* d, int n) {

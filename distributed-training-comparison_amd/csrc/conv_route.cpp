@@ -4,7 +4,8 @@
 //   FWD    conv_c64 > conv_halo (stride 1, stride 2 column-split) > GEMM
 //   DGRAD  conv_c64 > conv_halo (stride 1) > stride-2 classes: dgrad_s2 (no residual) > class GEMM > GEMM
 //   WGRAD  wgrad_s2 (one problem, whole dw) > wgrad_halo > GEMM
-// Options are read at call time; nothing is cached (tests flip options between calls).
+// Options are read at call time; nothing is cached (tests flip options between calls). conv_launch puts a launcher's
+// request, its route and its refusals in one place, for the launchers and for dtc_conv2d_route_query alike.
 #include "kernels.h"
 #include "tile_common.h"
 
@@ -91,9 +92,46 @@ static ConvRequest with_slab(const float* slab, size_t slab_bytes) {
   return rq;
 }
 
+// The request as the pass's launcher states it, its route, what the launch writes into the slab, and the launcher's
+// refusals. The fused FWD launch takes no slab: the statistics and the second output live in the epilogue, so it is
+// offered only where the plan is ONE split before any demotion -- conv_route decides sc_ok on the GEMM's planned
+// splits, and a split-K plan (a grid too small to fill the chip) is refused, not run on one split; callers then run
+// the two convs separately (tests/test_conv_route.py pins this).
+ConvLaunch conv_launch(const ConvShape& s, int pass, const ConvRequest& req) {
+  ConvLaunch l;
+  ConvRequest rq = req;
+  if (rq.sc) rq.slab_bytes = pass == CONV_FWD ? 0 : SIZE_MAX;  // (DGRAD: classes or nothing; WGRAD: the launch checks)
+  ConvRoute& r = l.route = conv_route(s, pass, rq);
+  if (pass != CONV_WGRAD) {
+    if (rq.sc && !r.sc_ok) l.refused = pass == CONV_FWD ? "conv_fwd_sc: unsupported shapes" : "conv_dgrad_sc: unsupported geometry / args";
+    if (r.kernel == CONV_K_HALO) l.slab_used = conv_halo_slab_bytes(s, pass, r.halo);
+    else if (r.kernel == CONV_K_GEMM) l.slab_used = igemm_slab_used(s, pass, r.gemm);
+    if (l.refused) l.slab_used = 0;
+    return l;
+  }
+  if (rq.sc) {
+    l.slab_used = conv_wgrad_s2_slab_used(s, r.splits);
+    if (!r.sc_ok) l.refused = "conv_wgrad_sc: no fused plan for this geometry";
+    else if (l.slab_used > req.slab_bytes) l.refused = "conv_wgrad_s2: slab too small";
+  } else if (rq.batch) {
+    l.slab_used = conv_wgrad_halo_slab_used(s, rq.nprob, r.splits, true);
+    if (r.kernel != CONV_K_WGRAD_HALO) l.refused = "conv_wgrad_batch: no halo plan for the problems or slab too small";
+  } else if (r.kernel == CONV_K_WGRAD_S2) {
+    l.slab_used = conv_wgrad_s2_slab_used(s, r.splits);
+  } else {
+    if (rq.slab_bytes < (size_t)s.K * s.R * s.S * s.C * 4) l.refused = "wgrad: slab workspace too small";
+    l.slab_used = r.kernel == CONV_K_WGRAD_HALO ? conv_wgrad_halo_slab_used(s, 1, r.splits, r.dw_whole)
+                                                : igemm_slab_used(s, CONV_WGRAD, r.gemm);
+  }
+  if (l.refused) l.slab_used = 0;
+  return l;
+}
+#define DTC_LAUNCH_OR_REFUSE(l) \
+  if ((l).refused) return set_error(DTC_EINVAL, "%s", (l).refused)
+
 int conv_fwd(const ConvShape& s, const u16* x, const u16* w, u16* y, int64_t* stats, float* slab, size_t slab_bytes,
              hipStream_t st, u64* ts, unsigned* tick) {
-  const ConvRoute r = conv_route(s, CONV_FWD, with_slab(slab, slab_bytes));
+  const ConvRoute r = conv_launch(s, CONV_FWD, with_slab(slab, slab_bytes)).route;
   if (r.kernel == CONV_K_C64) return conv_c64(s, CONV_FWD, x, w, y, nullptr, stats, st, ts);
   if (r.kernel == CONV_K_HALO)
     return conv_halo(s, CONV_FWD, r.halo, x, w, y, nullptr, stats, slab, st, ts, nullptr, nullptr, nullptr, tick);
@@ -101,21 +139,23 @@ int conv_fwd(const ConvShape& s, const u16* x, const u16* w, u16* y, int64_t* st
 }
 
 // 3x3 stride-2 conv + its block's 1x1 stride-2 projection shortcut in one launch (option sc_fuse): one read of x
-static ConvRoute route_fwd_sc(const ConvShape& s, const ConvShape& sc) {
+static ConvLaunch launch_fwd_sc(const ConvShape& s, const ConvShape& sc) {
   ConvRequest rq;
   rq.sc = true;
-  rq.slab_bytes = 0;  // the statistics and the second output live in the epilogue: no split-K
-  ConvRoute r = conv_route(s, CONV_FWD, rq);
-  r.sc_ok = r.sc_ok && sc.R == 1 && sc.S == 1 && sc.stride == 2 && sc.pad == 0 && sc.N == s.N && sc.H == s.H &&
-            sc.W == s.W && sc.C == s.C && sc.K == s.K;
-  return r;
+  ConvLaunch l = conv_launch(s, CONV_FWD, rq);
+  if (!(sc.R == 1 && sc.S == 1 && sc.stride == 2 && sc.pad == 0 && sc.N == s.N && sc.H == s.H && sc.W == s.W &&
+        sc.C == s.C && sc.K == s.K))
+    l.refused = "conv_fwd_sc: unsupported shapes";
+  return l;
 }
-bool conv_fwd_sc_ok(const ConvShape& s, const ConvShape& sc) { return route_fwd_sc(s, sc).sc_ok; }
+bool conv_fwd_sc_ok(const ConvShape& s, const ConvShape& sc) { return launch_fwd_sc(s, sc).refused == nullptr; }
 
 int conv_fwd_sc(const ConvShape& s, const ConvShape& sc, const u16* x, const u16* w, u16* y, int64_t* stats,
                 const u16* wsc, u16* ysc, int64_t* stats_sc, hipStream_t st, u64* ts) {
-  const ConvRoute r = route_fwd_sc(s, sc);
-  DTC_CHECK_ARG(r.sc_ok && x && w && y && wsc && ysc, "conv_fwd_sc: unsupported shapes");
+  const ConvLaunch l = launch_fwd_sc(s, sc);
+  DTC_LAUNCH_OR_REFUSE(l);
+  const ConvRoute& r = l.route;
+  DTC_CHECK_ARG(x && w && y && wsc && ysc, "conv_fwd_sc: unsupported shapes");
   if (r.kernel == CONV_K_HALO)
     return conv_halo(s, CONV_FWD, r.halo, x, w, y, nullptr, stats, nullptr, st, ts, wsc, ysc, stats_sc);
   return igemm_fwd(s, r.gemm, x, w, y, stats, nullptr, wsc, ysc, stats_sc, st, ts);
@@ -125,7 +165,7 @@ int conv_dgrad(const ConvShape& s, const u16* dy, const u16* w, u16* dx, const u
                size_t slab_bytes, hipStream_t st, u64* ts, int res_compact, unsigned* tick) {
   ConvRequest rq = with_slab(slab, slab_bytes);
   rq.res = res != nullptr;
-  const ConvRoute r = conv_route(s, CONV_DGRAD, rq);
+  const ConvRoute r = conv_launch(s, CONV_DGRAD, rq).route;
   DTC_CHECK_ARG(!res_compact || (res && r.kernel == CONV_K_GEMM_CLASSES),
                 "conv_dgrad: a compact residual needs the stride-2 parity-class path");
   switch (r.kernel) {
@@ -146,8 +186,10 @@ int conv_dgrad_sc(const ConvShape& s, const u16* dy, const u16* w, u16* dx, cons
                   hipStream_t st, u64* ts) {
   ConvRequest rq;
   rq.sc = true;
-  const ConvRoute r = conv_route(s, CONV_DGRAD, rq);
-  DTC_CHECK_ARG(r.sc_ok && dy && w && dx && dsc && wsc, "conv_dgrad_sc: unsupported geometry / args");
+  const ConvLaunch l = conv_launch(s, CONV_DGRAD, rq);
+  DTC_LAUNCH_OR_REFUSE(l);
+  const ConvRoute& r = l.route;
+  DTC_CHECK_ARG(dy && w && dx && dsc && wsc, "conv_dgrad_sc: unsupported geometry / args");
   if (r.kernel == CONV_K_DGRAD_S2) return conv_dgrad_s2_halo(s, dy, w, dx, dsc, wsc, st, ts);
   return igemm_dgrad(s, r.gemm, true, dy, w, dx, nullptr, 0, dsc, wsc, nullptr, st, ts);
 }
@@ -157,11 +199,12 @@ int conv_wgrad(const ConvShape& s, const u16* x, const u16* dy, float* dw, int d
   ConvRequest rq = with_slab(slab, slab_bytes);
   rq.dw_cols = dw_cols;
   rq.dw_ld = dw_ld;
-  const ConvRoute r = conv_route(s, CONV_WGRAD, rq);
+  const ConvLaunch l = conv_launch(s, CONV_WGRAD, rq);
+  DTC_LAUNCH_OR_REFUSE(l);
+  const ConvRoute& r = l.route;
   if (r.kernel == CONV_K_WGRAD_S2)
     return conv_wgrad_s2(s, r.splits, x, dy, nullptr, dw, nullptr, scale, slab, slab_bytes, st, ts);
   const int RSC = s.R * s.S * s.C, ncols = dw_cols > 0 ? dw_cols : RSC, ldo = dw_ld > 0 ? dw_ld : RSC;
-  DTC_CHECK_ARG(slab != nullptr && slab_bytes >= (size_t)s.K * RSC * 4, "wgrad: slab workspace too small");
   int splits = r.gemm.splits;
   if (r.kernel == CONV_K_WGRAD_HALO) {
     DTC_TRY(conv_wgrad_halo(s, 1, &x, &dy, slab, r.splits, &splits, st, ts, r.dw_whole ? &dw : nullptr, scale));
@@ -172,13 +215,25 @@ int conv_wgrad(const ConvShape& s, const u16* x, const u16* dy, float* dw, int d
   return wgrad_reduce_to(slab, splits, s.K, RSC, ncols, ldo, scale, &dw, 1, st, ts);
 }
 
+// conv1's weight gradient and its shortcut's in one launch (wgrad_s2 with dsc); the slab on hand must hold the
+// splits that run
+int conv_wgrad_sc(const ConvShape& s, const u16* x, const u16* dy, const u16* dsc, float* dw, float* dw_sc, float scale,
+                  float* slab, size_t slab_bytes, hipStream_t st, u64* ts) {
+  ConvRequest rq = with_slab(slab, slab_bytes);
+  rq.sc = true;
+  const ConvLaunch l = conv_launch(s, CONV_WGRAD, rq);
+  DTC_LAUNCH_OR_REFUSE(l);
+  return conv_wgrad_s2(s, l.route.splits, x, dy, dsc, dw, dw_sc, scale, slab, slab ? slab_bytes : 0, st, ts);
+}
+
 int conv_wgrad_batch(const ConvShape& s, int nprob, const u16* const* x, const u16* const* dy, float* const* dw,
                      float scale, float* slab, size_t slab_bytes, hipStream_t st, u64* ts) {
   ConvRequest rq = with_slab(slab, slab_bytes);
   rq.nprob = nprob;
-  const ConvRoute r = conv_route(s, CONV_WGRAD, rq);
-  if (r.kernel != CONV_K_WGRAD_HALO)
-    return set_error(DTC_EINVAL, "conv_wgrad_batch: no halo plan for %d problems or slab too small", nprob);
+  rq.batch = true;
+  const ConvLaunch l = conv_launch(s, CONV_WGRAD, rq);
+  DTC_LAUNCH_OR_REFUSE(l);
+  const ConvRoute& r = l.route;
   int splits = 0;
   DTC_TRY(conv_wgrad_halo(s, nprob, x, dy, slab, r.splits, &splits, st, ts, dw, scale));
   if (splits == 0) return 0;  // one split: the halo kernel wrote dw itself

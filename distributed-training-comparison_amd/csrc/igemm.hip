@@ -786,6 +786,12 @@ GemmPlan igemm_plan(const ConvShape& s, int pass, bool cls) {
   return pl;
 }
 
+size_t igemm_slab_used(const ConvShape& s, int pass, const GemmPlan& pl) {  // (DGRAD: the generic launch; classes never split)
+  if (pass == CONV_WGRAD) return (size_t)pl.splits * s.K * s.R * s.S * s.C * 4;
+  const int P = (s.H + 2 * s.pad - s.R) / s.stride + 1, Q = (s.W + 2 * s.pad - s.S) / s.stride + 1;
+  return pl.splits > 1 ? (size_t)pl.splits * (pass == CONV_FWD ? (size_t)s.N * P * Q * s.K : (size_t)s.N * s.H * s.W * s.C) * 4 : 0;
+}
+
 static int fill_common(IGemmParams& p, const ConvShape& s, const GemmPlan& pl, u64* ts) {
   p.ts = ts;
   p.N = s.N; p.H = s.H; p.W = s.W; p.C = s.C; p.K = s.K; p.R = s.R; p.S = s.S;

@@ -103,6 +103,8 @@ struct HaloPlan {
 };
 HaloPlan conv_halo_plan(const ConvShape& s, int pass);
 size_t conv_halo_slab_bytes(const ConvShape& s, int pass, const HaloPlan& hp);  // fp32 split-K slab of the plan
+// (the slab a conv_halo launch writes is conv_halo_slab_bytes of the plan it is given: split 1 writes none)
+size_t igemm_slab_used(const ConvShape& s, int pass, const GemmPlan& pl);  // fp32 slab an igemm launch of pl writes
 bool dgrad_s2_halo_ok(const ConvShape& s);  // stride-2 3x3 DGRAD as a halo-tiled sub-pixel conv (dgrad_s2.hip)
 // Halo-tiled 3x3 WGRAD (wgrad_halo.hip): the split count it would use (0: not applicable / disabled) for stride 1,
 // nprob (<= DTC_WG_BATCH) problems per launch, and for stride 2 (conv1 of a projection block, + its shortcut).
@@ -110,6 +112,10 @@ constexpr int DTC_WG_BATCH = 4;
 int wgrad_halo_splits(const ConvShape& s, int nprob = 1);
 int wgrad_s2_splits(const ConvShape& s);
 size_t conv_wgrad_s2_slab_bytes(const ConvShape& s, int splits);  // 9 taps + the shortcut's [K][C] per split
+// fp32 slab the launches write when asked for `splits` (no split is empty, so fewer may run; 0: one split that
+// writes dw itself, option wgrad_direct)
+size_t conv_wgrad_halo_slab_used(const ConvShape& s, int nprob, int splits, bool dw_given);
+size_t conv_wgrad_s2_slab_used(const ConvShape& s, int splits);
 
 // ---- the router (conv_route.cpp): the one place that knows the families' order of precedence
 enum ConvKernel {  // GEMM_CLASSES: igemm's stride-2 DGRAD parity classes (take a compact residual / the fused shortcut)
@@ -120,6 +126,7 @@ struct ConvRequest {  // what a launch branches on besides the shape
   bool sc = false;   // the block's 1x1 stride-2 shortcut in the same launch (conv_fwd_sc / conv_dgrad_sc)
   int dw_cols = 0, dw_ld = 0;  // WGRAD: a partial dw (0: whole rows)
   int nprob = 1;               // WGRAD: problems per launch (conv_wgrad_batch)
+  bool batch = false;          // WGRAD: conv_wgrad_batch's contract (the halo kernel or an error); conv_launch only
   size_t slab_bytes = SIZE_MAX;  // fp32 slab on hand (default: sizing -- whatever the route wants)
 };
 struct ConvRoute {
@@ -132,6 +139,15 @@ struct ConvRoute {
   bool sc_ok = false;       // 3x3 stride 2: the pass has a shortcut-fused launch (with req.sc: this route is it)
 };
 ConvRoute conv_route(const ConvShape& s, int pass, const ConvRequest& req = ConvRequest{});
+// What a launcher below does with a request: conv_route's answer for the slab on hand (req.sc: the shortcut-fused
+// launcher of the pass, which takes no slab for FWD / DGRAD), the fp32 slab bytes that launch writes, and why the
+// launcher returns an error instead (nullptr: it launches). The launchers and dtc_conv2d_route_query both ask here.
+struct ConvLaunch {
+  ConvRoute route;
+  size_t slab_used = 0;
+  const char* refused = nullptr;
+};
+ConvLaunch conv_launch(const ConvShape& s, int pass, const ConvRequest& req);
 
 // ---- launchers (conv_route.cpp): route, then the family's launch
 // y = conv(x, w) (bf16 NHWC out); optional BN statistics of the bf16 output into
@@ -161,6 +177,10 @@ int conv_dgrad_sc(const ConvShape& s, const u16* dy, const u16* w, u16* dx, cons
 // dw[k][0:dw_cols] (row stride dw_ld) = scale * sum_pixels dy (x) im2col(x); fp32
 int conv_wgrad(const ConvShape& s, const u16* x, const u16* dy, float* dw, int dw_cols, int dw_ld, float scale,
                float* slab, size_t slab_bytes, hipStream_t st, u64* ts = nullptr);
+// dw and the block's 1x1 stride-2 shortcut's dw_sc [K][C] (from dsc) in one conv_wgrad_s2 launch; DTC_EINVAL without
+// the stride-2 halo route or with a slab smaller than the splits that run need
+int conv_wgrad_sc(const ConvShape& s, const u16* x, const u16* dy, const u16* dsc, float* dw, float* dw_sc, float scale,
+                  float* slab, size_t slab_bytes, hipStream_t st, u64* ts = nullptr);
 // nprob (<= DTC_WG_BATCH) weight gradients of one 3x3 stride-1 geometry in one halo launch + one reduce launch: dw[i] =
 // scale * wgrad(x[i], dy[i]). DTC_EINVAL when there is no halo plan or the slab is too small (then: one by one).
 int conv_wgrad_batch(const ConvShape& s, int nprob, const u16* const* x, const u16* const* dy, float* const* dw,

@@ -450,6 +450,19 @@ int wgrad_halo_splits(const ConvShape& s, int nprob) {
   return splits;
 }
 
+// `splits` equal shares of nsteps, none empty: the splits that run
+static int splits_that_run(int64_t nsteps, int splits) {
+  const int64_t per = (nsteps + splits - 1) / splits;
+  return (int)((nsteps + per - 1) / per);
+}
+
+size_t conv_wgrad_halo_slab_used(const ConvShape& s, int nprob, int splits, bool dw_given) {
+  WgGeom g;
+  if (splits <= 0 || !wg_geometry(s, g)) return 0;
+  const int used = splits_that_run(g.nsteps, splits);
+  return used == 1 && dw_given && option_get(OPT_WGRAD_DIRECT) != 0 ? 0 : (size_t)nprob * used * s.K * 9 * s.C * 4;
+}
+
 int conv_wgrad_halo(const ConvShape& s, int nprob, const u16* const* x, const u16* const* dy, float* slab, int splits,
                     int* used_splits, hipStream_t st, u64* ts, float* const* dw, float scale) {
   WgGeom g;
@@ -485,7 +498,7 @@ int conv_wgrad_halo(const ConvShape& s, int nprob, const u16* const* x, const u1
   p.ts = ts;
   p.xcd = option_get(OPT_WGRAD_XCD);
   p.trim = option_get(OPT_WGRAD_TRIM);
-  const int used = (p.nsteps + p.steps_per_split - 1) / p.steps_per_split;
+  const int used = splits_that_run(p.nsteps, splits);
   p.slab_stride = (size_t)used * s.K * 9 * s.C;
   p.direct = used == 1 && dw != nullptr && option_get(OPT_WGRAD_DIRECT) != 0;
   dim3 grid((s.C / 64) * (s.K / 64), used, nprob);
@@ -586,6 +599,14 @@ size_t conv_wgrad_s2_slab_bytes(const ConvShape& s, int splits) {
   return (size_t)splits * s.K * 10 * s.C * 4;  // 9 taps + the shortcut's [K][C]
 }
 
+size_t conv_wgrad_s2_slab_used(const ConvShape& s, int splits) {
+  bool gen = false;
+  int64_t nsteps = 0;
+  if (splits <= 0 || !wgrad_s2_plan(s, gen, nsteps)) return 0;
+  const int used = splits_that_run(nsteps, splits);
+  return used == 1 && option_get(OPT_WGRAD_DIRECT) != 0 ? 0 : conv_wgrad_s2_slab_bytes(s, used);
+}
+
 int conv_wgrad_s2(const ConvShape& s, int splits, const u16* x, const u16* dy, const u16* dsc, float* dw, float* dw_sc,
                   float scale, float* slab, size_t slab_bytes, hipStream_t st, u64* ts) {
   int rs = 0, imgs = 0, pitch = 0, hb = 0, nh = 0;
@@ -630,9 +651,9 @@ int conv_wgrad_s2(const ConvShape& s, int splits, const u16* x, const u16* dy, c
   p.ts = ts;
   p.xcd = option_get(OPT_WGRAD_XCD);
   p.trim = option_get(OPT_WGRAD_TRIM);
-  const int used = (p.nsteps + p.steps_per_split - 1) / p.steps_per_split;
+  const int used = splits_that_run(p.nsteps, splits);
   p.direct = used == 1 && option_get(OPT_WGRAD_DIRECT) != 0;
-  DTC_CHECK_ARG(p.direct || (slab && slab_bytes >= (size_t)used * s.K * 10 * s.C * 4), "conv_wgrad_s2: slab too small");
+  DTC_CHECK_ARG(p.direct || (slab && slab_bytes >= conv_wgrad_s2_slab_used(s, splits)), "conv_wgrad_s2: slab too small");
   p.slab = slab;
   p.slab_stride = (size_t)used * s.K * 9 * s.C;
   p.slab_sc = slab + p.slab_stride;  // [used][K][C] after the taps

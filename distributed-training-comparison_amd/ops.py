@@ -11,8 +11,8 @@ import ctypes as C
 
 import torch
 
-from ._native import (SAM_MAX_KEEP, SEG_ADAPT, ConvDesc, EmaRange, NativeError, PsgdTensor, SamKeep, Seg, call, lib,
-                      ptr, require_cuda, stream_ptr)
+from ._native import (CONV_KERNELS, CONV_ROUTE_RES, CONV_ROUTE_SC, SAM_MAX_KEEP, SEG_ADAPT, ConvDesc, ConvRoute, EmaRange,
+                      NativeError, PsgdTensor, SamKeep, Seg, call, lib, ptr, require_cuda, stream_ptr)
 
 
 
@@ -22,6 +22,18 @@ def conv_desc(n, h, w, c, k, r, s, stride, pad) -> ConvDesc:
 
 def conv_out_hw(h, w, r, s, stride, pad):
     return (h + 2 * pad - r) // stride + 1, (w + 2 * pad - s) // stride + 1
+
+
+def conv_route_info(desc, mode, res=False, sc=False, nprob=1, ws=None, ws_bytes=0):
+    """dtc_conv2d_route_query as a dict: the kernel (a CONV_KERNELS name), tile, splits and slab bytes the entry point
+    named by (mode, res, sc, nprob) would run with for a workspace of `ws_bytes` at device address `ws` (an int; it is
+    never dereferenced; None: no workspace). Host code: nothing is launched."""
+    r = ConvRoute()
+    call("dtc_conv2d_route_query", desc, mode, (CONV_ROUTE_RES if res else 0) | (CONV_ROUTE_SC if sc else 0), nprob,
+         ws, ws_bytes, C.byref(r))
+    out = {n: getattr(r, n) for n, _ in ConvRoute._fields_ if n != "reserved"}
+    out["kernel"] = CONV_KERNELS[r.kernel]
+    return out
 
 
 def _ws(desc, mode, device, workspace=None):

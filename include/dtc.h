@@ -73,6 +73,40 @@ size_t dtc_conv2d_workspace_size(const dtc_conv_desc* d, int pass);
  * reference's cudnn.deterministic asks, src/ddp/utils.py:12-13); dtc_bn_stat_totals reads them. */
 int dtc_conv2d_fwd(const dtc_conv_desc* d, const uint16_t* x, const uint16_t* w, uint16_t* y, int64_t* stats,
                    void* ws, size_t ws_bytes, void* stream);
+/* Which kernel a conv entry point would launch for this descriptor, request and workspace, and what it would do
+ * with the workspace -- read-only: nothing is launched, `ws` is never dereferenced (its address only decides where
+ * the 256-byte-aligned arrival counters would sit) and may be NULL. The entry point is named by pass, flags and
+ * nprob: FWD -> dtc_conv2d_fwd, with DTC_CONV_ROUTE_SC dtc_conv2d_fwd_sc; DGRAD -> dtc_conv2d_dgrad (RES: a
+ * residual is passed), with SC dtc_conv2d_dgrad_sc; WGRAD -> dtc_conv2d_wgrad, with SC dtc_conv2d_wgrad_sc, with
+ * nprob 2..4 dtc_conv2d_wgrad_batch. The answer comes from the routing and workspace code those entry points run,
+ * under the options in force at the call. Returns non-zero for a descriptor the ABI rejects or a combination that
+ * names no entry point. */
+enum {
+  DTC_CONV_K_GEMM = 0,         /* implicit GEMM */
+  DTC_CONV_K_GEMM_CLASSES = 1, /* implicit GEMM, stride-2 DGRAD as four parity classes */
+  DTC_CONV_K_C64 = 2,          /* persistent 64 -> 64 channel 3x3 kernel */
+  DTC_CONV_K_HALO = 3,         /* halo-tiled 3x3 FWD / DGRAD */
+  DTC_CONV_K_DGRAD_S2 = 4,     /* stride-2 3x3 DGRAD as a halo sub-pixel conv */
+  DTC_CONV_K_WGRAD_HALO = 5,   /* halo-tiled 3x3 stride-1 WGRAD */
+  DTC_CONV_K_WGRAD_S2 = 6      /* halo-tiled 3x3 stride-2 WGRAD (+ shortcut) */
+};
+enum { DTC_CONV_ROUTE_RES = 1, DTC_CONV_ROUTE_SC = 2 };
+typedef struct {
+  int kernel;           /* DTC_CONV_K_* */
+  int gemm_bm, gemm_bn; /* the GEMM kernels' tile (0 elsewhere) */
+  int splits;           /* split-K count asked of the kernel that runs (1: none) */
+  int halo_cfg;         /* DTC_CONV_K_HALO: tile configuration (-1 elsewhere) */
+  int halo_gen;         /* ... 1: its general tile geometry */
+  int reduce_in_kernel; /* 1: a split-K DTC_CONV_K_HALO launch sums its slab itself (the arrival counters fit behind
+                           the slab and option splitk_ink is on); 0: no split-K, or a separate reduce launch */
+  int sc_ok;            /* the pass has a shortcut-fused launch for this descriptor */
+  int refused;          /* 1: the entry point returns an error for this workspace / request and launches nothing */
+  int reserved;
+  size_t slab_wanted;   /* fp32 slab bytes the pass wants (what the size queries are built on) */
+  size_t slab_used;     /* fp32 slab bytes the launch writes, from the start of ws (0: none, or refused) */
+} dtc_conv_route;
+int dtc_conv2d_route_query(const dtc_conv_desc* d, int pass, int flags, int nprob, const void* ws, size_t ws_bytes,
+                           dtc_conv_route* out);
 /* dx = conv^T(dy, w) (+ res if non-NULL): the input gradient of Conv2d */
 /* 3x3 stride-2 conv (desc) and its BasicBlock's 1x1 stride-2 projection shortcut (net.py:18-19, 29-36) of
  * the same input in one launch: y = conv(x, w), ysc = conv1x1_s2(x, wsc [K][C]); optional BN statistics of

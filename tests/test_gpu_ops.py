@@ -24,21 +24,24 @@ def _within(name, *checks):
     print(f"{name}: worst |err|/tol {worst:.3f}")
 
 CONV_CASES = [
-    # (N, H, W, C, K, R, stride)  -> pad = 1 for 3x3, 0 for 1x1
-    (2, 8, 8, 64, 64, 3, 1),      # layer1 conv
-    (2, 8, 8, 64, 128, 3, 2),     # layer2.0.conv1 (stride 2)
-    (2, 8, 8, 64, 128, 1, 2),     # layer2.0.shortcut (1x1 s2)
-    (2, 8, 8, 128, 128, 3, 1),    # layer2 conv
-    (3, 4, 4, 256, 512, 3, 2),    # layer4.0.conv1 (ragged pixel count, split-K)
-    (4, 4, 4, 512, 512, 3, 1),    # layer4 conv (deep reduction, split-K)
-    (2, 32, 32, 64, 64, 1, 1),    # stem GEMM over the 64-column im2col image
-    (1, 5, 7, 64, 64, 3, 1),      # odd spatial size, M not a tile multiple
-    (16, 16, 16, 256, 256, 3, 1),  # 64x64 tiles, no split (fused-stats epilogue)
-    (26, 32, 32, 128, 256, 3, 1),  # 128x128 tiles, no split, ragged last pixel tile
-    (100, 32, 32, 64, 64, 3, 1),   # 64x256 tiles (K=64 layers), no split
-    (64, 16, 16, 64, 128, 3, 2),   # stride-2 class GEMMs big enough for 64x256 tiles
-    (5, 8, 8, 256, 256, 3, 1),     # halo conv: 2 images per tile, ragged last tile
-    (9, 4, 4, 512, 256, 3, 1),     # halo conv: 8 images per tile, C != K
+    # (N, H, W, C, K, R, stride)  -> pad = 1 for 3x3, 0 for 1x1. After each case: the kernels FWD / DGRAD (with and
+    # without a residual) / WGRAD run on under the default options with the queried workspace, as
+    # dtc_conv2d_route_query reports them ("x n": n-way split-K). Coverage of a particular route, tile or fallback
+    # belongs to tests/test_gpu_conv_routes.py, which asserts the route before it launches.
+    (2, 8, 8, 64, 64, 3, 1),      # layer1 conv at a small batch: conv_halo cfg 7 / same / wgrad_halo
+    (2, 8, 8, 64, 128, 3, 2),     # layer2.0.conv1 (stride 2): conv_halo cfg 8 (column-split) / class GEMM 64x64 / GEMM 64x64
+    (2, 8, 8, 64, 128, 1, 2),     # layer2.0.shortcut (1x1 s2): GEMM 64x64 / class GEMM 64x64 / GEMM 64x64
+    (2, 8, 8, 128, 128, 3, 1),    # layer2 conv: conv_halo cfg 7 / same / wgrad_halo
+    (3, 4, 4, 256, 512, 3, 2),    # layer4.0.conv1 (ragged pixel count): GEMM 64x64 x 4 / class GEMM 64x64 / GEMM 128x128
+    (4, 4, 4, 512, 512, 3, 1),    # layer4 conv (deep reduction): conv_halo cfg 7 x 4 / same / wgrad_halo
+    (2, 32, 32, 64, 64, 1, 1),    # stem GEMM over the 64-column im2col image: GEMM 64x64 / same / GEMM 64x64 x 4
+    (1, 5, 7, 64, 64, 3, 1),      # odd spatial size, M not a tile multiple: GEMM 64x64, no split, every pass
+    (16, 16, 16, 256, 256, 3, 1),  # conv_halo cfg 7 x 2 (in-kernel reduce, fused-stats epilogue) / same / wgrad_halo x 2
+    (26, 32, 32, 128, 256, 3, 1),  # conv_halo cfg 2 (64x128 tiles), no split, ragged last tile / same / wgrad_halo x 17
+    (100, 32, 32, 64, 64, 3, 1),   # conv_c64 / same / wgrad_halo x 66
+    (64, 16, 16, 64, 128, 3, 2),   # conv_halo cfg 8 / class GEMM 64x64 / wgrad_s2 x 16
+    (5, 8, 8, 256, 256, 3, 1),     # conv_halo cfg 7 x 2: 2 images per tile, ragged last tile / same / wgrad_halo
+    (9, 4, 4, 512, 256, 3, 1),     # conv_halo cfg 7 x 4 (DGRAD x 2): 8 images per tile, C != K / GEMM 128x128
 ]
 
 
