@@ -16,7 +16,7 @@
 //     vmcnt that leaves the tile's stores in flight;
 //   * FWD accumulates the BN batch statistics of the bf16-rounded outputs in registers across
 //     all tiles of the workgroup and adds them to the fp64 slots once.
-// Halo layout, swizzle and DGRAD tap mirroring are those of conv_halo.hip.
+// Halo layout, swizzle and the 16-B epilogue are tile_common.h's; the DGRAD tap mirroring is conv_halo.hip's.
 //
 // General geometry (template flag GEN, option c64_gen; the 224x224 model's 224-wide layer1): rows whose
 // width does not divide 256 are cut into 32-pixel segments and a tile is 8 rows x one segment of one image
@@ -40,7 +40,6 @@ struct C64Params {
   int rows, imgs, hb, nh, tiles_y, ntiles;
   FastDiv fd_hb, fd_w2, fd_spx, fd_w;
   // GEN: tiles per image and 32-pixel segments per row (a tile = rows 8*yb.. x columns 32*sb.. of image n)
-  int tpi, spr;
   FastDiv fd_tpi, fd_spr;
   u64* ts;
   u64* phase;  // cycle-stamp buffer (DTC_PHASES builds; null otherwise)
@@ -111,10 +110,7 @@ __global__ void __launch_bounds__(256, 1) conv_c64_kernel(const C64Params p) {
   const int M = p.N * p.H * p.W;
   // GEN: tile -> (image, first row, first column) and the 64-bit element index of its first pixel
   auto gen_tile = [&](int tile, int& n0, int& y0, int& q0) {
-    n0 = (int)fdiv((uint32_t)tile, p.fd_tpi);
-    const int rem = tile - n0 * p.tpi, yb = (int)fdiv((uint32_t)rem, p.fd_spr);
-    y0 = yb * C64_GROWS;
-    q0 = (rem - yb * p.spr) * C64_SEG;
+    seg_tile_origin(tile, (int)p.fd_tpi.d, p.fd_tpi, (int)p.fd_spr.d, p.fd_spr, C64_GROWS, C64_SEG, n0, y0, q0);
   };
   auto gen_base = [&](int tile) -> int64_t {
     int n0, y0, q0;
@@ -143,9 +139,9 @@ __global__ void __launch_bounds__(256, 1) conv_c64_kernel(const C64Params p) {
     const int hbr = i * p.hb + y * W2 + x;
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
-      const int row = hbr + (t / 3) * W2 + (t % 3);
+      const int row = hbr + halo_tap_shift<1>(t, W2, 0);
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) boff[t][ks][j] = row * 128 + (((ks * 4 + (lane >> 4)) ^ hswz(row)) << 4);
+      for (int ks = 0; ks < 2; ++ks) boff[t][ks][j] = halo_frag_off(row, lane) ^ (uint32_t)(ks * 64);
     }
   }
   // ---- halo DMA: tile-invariant per-lane parts (row decomposition, x range, swizzled channel chunk)
@@ -179,7 +175,7 @@ __global__ void __launch_bounds__(256, 1) conv_c64_kernel(const C64Params p) {
         const int g = wave + 4 * q;
         if (g >= C64_HCAP / 8) break;
         const bool ok = hok[q] && (unsigned)(y0 + hyy[q]) < (unsigned)p.H && (unsigned)(q0 + hxx[q]) < (unsigned)p.W;
-        buf_lds16(box, 0x7ffffff0u, dst + g * 1024, ok ? (uint32_t)hrel[q] : 0x80000000u);
+        buf_lds16(box, 0x7ffffff0u, dst + g * 1024, ok ? (uint32_t)hrel[q] : DMA_OOB);
       }
       return;
     }
@@ -197,7 +193,7 @@ __global__ void __launch_bounds__(256, 1) conv_c64_kernel(const C64Params p) {
       const int g = wave + 4 * q;
       if (g >= C64_HCAP / 8) break;
       const bool ok = hok[q] && (unsigned)(y0 + hyy[q]) < (unsigned)p.H && n0 + hii[q] < p.N;
-      buf_lds16(p.src, p.src_bytes, dst + g * 1024, ok ? (uint32_t)(tbase + hrel[q]) : 0x80000000u);
+      buf_lds16(p.src, p.src_bytes, dst + g * 1024, ok ? (uint32_t)(tbase + hrel[q]) : DMA_OOB);
     }
   };
   // buffer descriptors of the output-side tensors; GEN: rebased at a tile's first pixel (tile_rsrc below)
@@ -224,21 +220,10 @@ __global__ void __launch_bounds__(256, 1) conv_c64_kernel(const C64Params p) {
   // epilogue (interleaved with the following tile's MFMAs) never waits on it. Loading it inside the
   // epilogue stalled the wave's only SIMD on a full HBM latency per pixel-column group (and on the
   // younger halo DMA: vmcnt retires in order): 74 -> 26 us per layer1 dgrad at B=256.
-  typedef int i32x2 __attribute__((ext_vector_type(2)));
   typedef int i32x4 __attribute__((ext_vector_type(4)));
-  // 16-B epilogue accesses (MI355X guide T21, for the 16x16 MFMA layout): lane l holds channels rq..rq+3 of
-  // fragment i, and lane l ^ 16 the next four. One v_permlane16_swap per dword of a fragment pair (2p, 2p+1)
-  // gives the lanes of rows 0 / 2 the 8 consecutive channels 32p + {0, 8}.. of fragment 2p and the lanes of rows
-  // 1 / 3 those of fragment 2p + 1 -- one dwordx4 store per pair instead of two dwordx2 (the stores were
-  // issue-bound: 8-B accesses move half the bytes per vector-memory instruction). The swap is an involution,
-  // so a 16-B residual load is turned back into the MFMA layout the same way.
-  const int r4 = lane >> 4;
-  const int wch = (r4 & 1) * 16 + (r4 >> 1) * 8;  // this lane's first channel within a fragment pair (16 B)
-  auto swap2 = [](uint32_t& x, uint32_t& y) {  // rows 1 / 3 of x <-> rows 0 / 2 of y
-    const auto r = __builtin_amdgcn_permlane16_swap(x, y, false, false);
-    x = r[0];
-    y = r[1];
-  };
+  // 16-B epilogue accesses (frag_pair_pack / frag_pair_unpack, tile_common.h): the stores were issue-bound, and
+  // 8-B accesses move half the bytes per vector-memory instruction
+  const int wch = frag_pair_channel(lane);  // this lane's first channel within a fragment pair (16 B)
   struct EpiOps {
     i32x4 r[FN][FM / 2];
   };
@@ -251,7 +236,7 @@ __global__ void __launch_bounds__(256, 1) conv_c64_kernel(const C64Params p) {
       return (uint32_t)((((l >> 5) * p.W + (l & 31)) * 64 + ch) * 2);
     }
     const int pix = tile * 256 + l;  // tiles are 256 consecutive pixels
-    return pix < M ? (uint32_t)((pix * 64 + ch) * 2) : 0x80000000u;
+    return pix < M ? (uint32_t)((pix * 64 + ch) * 2) : DMA_OOB;
   };
   auto epi_off = [&](int tile, int j, int i) { return epi_off_ch(tile, j, i * 16 + rq); };
   auto prefetch = [&](EpiOps& o, int tile) {
@@ -273,14 +258,7 @@ __global__ void __launch_bounds__(256, 1) conv_c64_kernel(const C64Params p) {
     uint32_t rres[FM][2];  // RES: the residual of each fragment in the MFMA layout (packed bf16 x 4)
     if constexpr (RES) {
 #pragma unroll
-      for (int q = 0; q < FM / 2; ++q) {
-        uint32_t x0 = (uint32_t)o.r[j][q].x, x1 = (uint32_t)o.r[j][q].y, y0 = (uint32_t)o.r[j][q].z,
-                 y1 = (uint32_t)o.r[j][q].w;
-        swap2(x0, y0);
-        swap2(x1, y1);
-        rres[2 * q][0] = x0; rres[2 * q][1] = x1;
-        rres[2 * q + 1][0] = y0; rres[2 * q + 1][1] = y1;
-      }
+      for (int q = 0; q < FM / 2; ++q) frag_pair_unpack(__builtin_bit_cast(uint4, o.r[j][q]), rres[2 * q], rres[2 * q + 1]);
     }
     uint32_t packed[FM][2];
 #pragma unroll
@@ -304,11 +282,9 @@ __global__ void __launch_bounds__(256, 1) conv_c64_kernel(const C64Params p) {
     }
 #pragma unroll
     for (int q = 0; q < FM / 2; ++q) {  // fragment pair (2q, 2q + 1) -> one 16-B store per lane
-      uint32_t x0 = packed[2 * q][0], x1 = packed[2 * q][1], y0 = packed[2 * q + 1][0], y1 = packed[2 * q + 1][1];
-      swap2(x0, y0);
-      swap2(x1, y1);
-      const uint32_t o16 = ok ? epi_off_ch(tile, j, q * 32 + wch) : 0x80000000u;
-      __builtin_amdgcn_raw_buffer_store_b128(i32x4{(int)x0, (int)x1, (int)y0, (int)y1}, ors, o16, 0, 0);
+      const uint4 v = frag_pair_pack(packed[2 * q], packed[2 * q + 1]);
+      const uint32_t o16 = ok ? epi_off_ch(tile, j, q * 32 + wch) : DMA_OOB;
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, v), ors, o16, 0, 0);
     }
   };
   auto epilogue = [&](const f32x4 (&a)[FM][FN], const EpiOps& o, int tile, bool have) {
@@ -400,16 +376,7 @@ __global__ void __launch_bounds__(256, 1) conv_c64_kernel(const C64Params p) {
             red[(wave * 64 + ch) * 2 + 1] = q;
           }
         }
-      __syncthreads();
-      if (threadIdx.x < 64) {
-        float s = 0.f, q = 0.f;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-          s += red[(w * 64 + threadIdx.x) * 2 + 0];
-          q += red[(w * 64 + threadIdx.x) * 2 + 1];
-        }
-        stat_add(sacc, 64, threadIdx.x, s, q);
-      }
+      stats_fold<4, 64>(red, sacc, 64, 0);
     }
   }
   C64_STAMP(15, false);
@@ -418,13 +385,27 @@ __global__ void __launch_bounds__(256, 1) conv_c64_kernel(const C64Params p) {
 }
 
 // ---------------------------------------------------------------- host side
-static bool c64_classic_ok(const ConvShape& s);
-// GEN geometry: 8 rows x 32-column segments (rows whose width does not divide 256, or tensors past 2 GB)
-static bool c64_gen_ok(const ConvShape& s) {
-  if (option_get(OPT_C64_GEN) == 0) return false;
+// Tile geometry: 256-pixel tiles, classic (whole rows / whole images, rows of 16+ pixels: a fragment's 16 pixels
+// are contiguous in one image row) or general (gen: 8 rows x 32-column segments where the row width does not
+// divide 256, 64-bit per-tile bases: tensors past 2 GB)
+struct C64Geom {
+  bool gen = false;
+  TileSplit t;
+  SegTile g;  // gen
+};
+static bool c64_geometry(const ConvShape& s, C64Geom& c) {
   if (!(conv3x3_ok(s, 1) && s.C == 64 && s.K == 64)) return false;
-  if (s.W % C64_SEG != 0 || s.H % C64_GROWS != 0) return false;
   const int64_t M = (int64_t)s.N * s.H * s.W;
+  c.gen = false;
+  if (s.W >= 16 && 256 % s.W == 0 && classic_tile(s.H, s.W, 256, c.t) &&
+      c.t.imgs * halo_box_s1(c.t.rows, s.W) <= C64_HCAP && M % 256 == 0 && M * 128 < (1ll << 31))
+    return true;
+  if (option_get(OPT_C64_GEN) == 0) return false;
+  if (s.W % C64_SEG != 0 || s.H % C64_GROWS != 0) return false;
+  c.gen = true;
+  c.t.rows = C64_GROWS;
+  c.t.imgs = 1;
+  c.g = seg_tile(s.H, s.W, C64_SEG, C64_GROWS);
   return M / 256 < (1ll << 31) && M < (1ll << 31) && (int64_t)C64_GROWS * s.W * 128 < (1ll << 31);
 }
 // option conv_c64: 0 off; 1 (auto) where every persistent workgroup gets at least one 256-pixel tile -- below
@@ -435,57 +416,30 @@ bool conv_c64_ok(const ConvShape& s) {
   const int o = option_get(OPT_CONV_C64);
   if (o == 0) return false;
   if (o == 1 && (int64_t)s.N * s.H * s.W / 256 < (int64_t)std::max(1, option_get(OPT_C64_WGS))) return false;
-  return c64_classic_ok(s) || c64_gen_ok(s);
-}
-static bool c64_classic_ok(const ConvShape& s) {
-  if (!(conv3x3_ok(s, 1) && s.C == 64 && s.K == 64)) return false;
-  if (s.W < 16 || 256 % s.W != 0) return false;  // fragments of 16 contiguous pixels in one image row
-  const int hw = s.H * s.W;
-  int rows, imgs;
-  if (hw >= 256) {
-    rows = 256 / s.W;
-    if (s.H % rows) return false;
-    imgs = 1;
-  } else {
-    if (256 % hw) return false;
-    imgs = 256 / hw;
-    rows = s.H;
-  }
-  const int nh = imgs * (rows + 2) * (s.W + 2);
-  const int64_t M = (int64_t)s.N * hw;
-  return nh <= C64_HCAP && M % 256 == 0 && M * 128 < (1ll << 31);
+  C64Geom c;
+  return c64_geometry(s, c);
 }
 
 int conv_c64(const ConvShape& s, int mode, const u16* src, const u16* w, u16* out, const u16* res, int64_t* stats,
              hipStream_t st, u64* ts) {
-  const bool gen = !c64_classic_ok(s);  // (whether to use the kernel at all is conv_route's question, not asked again)
-  DTC_CHECK_ARG((!gen || c64_gen_ok(s)) && (mode == CONV_FWD || mode == CONV_DGRAD), "conv_c64: unsupported shape");
+  C64Geom c;  // (whether to use the kernel at all is conv_route's question, not asked again)
+  DTC_CHECK_ARG(c64_geometry(s, c) && (mode == CONV_FWD || mode == CONV_DGRAD), "conv_c64: unsupported shape");
+  const bool gen = c.gen;
   C64Params p{};
   p.src = src; p.w = w; p.out = out; p.res = res; p.stats = stats;
   p.N = s.N; p.H = s.H; p.W = s.W;
-  const int64_t hw = (int64_t)s.H * s.W;
-  const int64_t M = s.N * hw;
+  const int64_t M = (int64_t)s.N * s.H * s.W;
   const int lw = gen ? C64_SEG : s.W;  // the LDS tile width
+  p.rows = c.t.rows;
+  p.imgs = c.t.imgs;
   if (gen) {
-    p.rows = C64_GROWS;
-    p.imgs = 1;
-    p.spr = s.W / C64_SEG;
-    p.tpi = (s.H / C64_GROWS) * p.spr;
-    p.fd_tpi = make_fastdiv(p.tpi);
-    p.fd_spr = make_fastdiv(p.spr);
+    p.fd_tpi = make_fastdiv(c.g.tpi);
+    p.fd_spr = make_fastdiv(c.g.spr);
     p.src_bytes = p.out_bytes = 0x7ffffff0u;  // unused: every access goes through a per-tile base
   } else {
-    if (hw >= 256) {
-      p.rows = 256 / s.W;
-      p.imgs = 1;
-    } else {
-      p.imgs = (int)(256 / hw);
-      p.rows = s.H;
-    }
-    p.src_bytes = (uint32_t)(M * 128);
-    p.out_bytes = (uint32_t)(M * 128);
+    p.src_bytes = p.out_bytes = (uint32_t)(M * 128);
   }
-  p.hb = (p.rows + 2) * (lw + 2);
+  p.hb = halo_box_s1(p.rows, lw);
   p.nh = p.imgs * p.hb;
   p.tiles_y = s.H / p.rows;
   p.ntiles = (int)(M / 256);

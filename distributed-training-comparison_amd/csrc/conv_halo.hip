@@ -19,10 +19,11 @@
 // Epilogues match igemm.hip: FWD rounds to bf16 and reduces the BN batch statistics of the
 // rounded output into fp64 slots; DGRAD optionally adds the residual-branch gradient.
 //
-// Pipeline: weights double-buffered; the halo is double-buffered (NHB = 2: the next chunk's halo
-// arrives in slices during the current chunk's first eight taps) or single (NHB = 1: reloaded
-// at chunk boundaries, a bubble other resident workgroups hide). One s_waitcnt vmcnt(0) +
-// s_barrier per step (the DMA for step it+1 overlaps the MFMAs of step it).
+// Pipeline: weights in a three-slot ring (two steps in flight); the halo is double-buffered (NHB = 2:
+// the next chunk's halo arrives in slices during the current chunk's first eight taps) or single
+// (NHB = 1: reloaded at chunk boundaries, a bubble other resident workgroups hide). One counted
+// s_waitcnt vmcnt + s_barrier per step.
+// Tile geometry, halo layout and swizzle, and the 16-B epilogue are tile_common.h's.
 #include "common.h"
 #include "kernels.h"
 #include "tile_common.h"
@@ -101,8 +102,7 @@ __device__ __forceinline__ void wait_vm_slices(int tap) {
 #undef DTC_VMW
 }
 
-template <int MODE, int BM, int BN, int WR, int WC, int NHB, int HCAP, int WS, int ST = 1, bool SC = false,
-          bool GEN = false>
+template <int MODE, int BM, int BN, int WR, int WC, int NHB, int HCAP, int ST = 1, bool SC = false, bool GEN = false>
 __global__ void __launch_bounds__(256, 2) conv_halo_kernel(const HConvParams p) {
   constexpr int FM = BM / (WR * 16);
   constexpr int FN = BN / (WC * 16);
@@ -111,9 +111,10 @@ __global__ void __launch_bounds__(256, 2) conv_halo_kernel(const HConvParams p) 
   constexpr int NIW = BM / 32;       // weight DMA instructions per wave per step
   constexpr int NHI = HCAP / 32;     // max halo DMA instructions per wave
   constexpr int SCBYTES = SC ? WBYTES : 0;
-  static_assert(WR * WC == 4 && HCAP % 32 == 0 && (WS == 2 || WS == 3), "shape");  // (launched with WS = 3)
+  constexpr int WS = 3;              // weight ring slots
+  static_assert(WR * WC == 4 && HCAP % 32 == 0, "shape");
   static_assert(ST == 1 || (ST == 2 && MODE == 0 && NHB == 1), "stride 2: forward, single halo buffer");
-  static_assert(!SC || (ST == 2 && WS == 3), "shortcut fusion: stride-2 forward, 3-slot weight ring");
+  static_assert(!SC || ST == 2, "shortcut fusion: stride-2 forward");
   static_assert(!GEN || ST == 1 || (MODE == 0 && NHB == 1), "general tile geometry: stride 2 is FWD only");
   __shared__ __attribute__((aligned(1024))) char smem[NHB * HBYTES + WS * WBYTES + SCBYTES];
   char* const wbase = smem + NHB * HBYTES;
@@ -123,15 +124,15 @@ __global__ void __launch_bounds__(256, 2) conv_halo_kernel(const HConvParams p) 
   phase_mark(p.phase, 0);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int bid = blockIdx.x;
-  if (p.xcd_remap && gridDim.x >= 16) {  // consecutive tile ids (same pixel tile) share an XCD's L2
-    const int nwg = gridDim.x, x8 = bid & 7, q = nwg >> 3, rr = nwg & 7;
-    bid = (x8 < rr ? x8 * (q + 1) : rr * (q + 1) + (x8 - rr) * q) + (bid >> 3);
-  }
+  // consecutive tile ids (same pixel tile) share an XCD's L2
+  if (p.xcd_remap && gridDim.x >= 16) bid = (int)xcd_grouped_id(blockIdx.x, gridDim.x);
   const int ta = bid % p.tiles_a, tb = bid / p.tiles_a;
   const int a0 = ta * BM;
   const int split = blockIdx.y, c0 = split * p.nchunk;  // first reduction chunk of this split
   int n0, y0, q0 = 0;
   if constexpr (GEN) {
+    // (seg_tile_origin written out: through the helper the 64 x 256 forward instance, which already spills,
+    // gains 34 instructions and changes its spill counts)
     n0 = (int)fdiv((uint32_t)tb, p.fd_gtpi);
     const int rem = tb - n0 * p.gtpi, yb = (int)fdiv((uint32_t)rem, p.fd_gspr);
     y0 = yb * p.grs;
@@ -187,25 +188,22 @@ __global__ void __launch_bounds__(256, 2) conv_halo_kernel(const HConvParams p) 
 #pragma unroll
   for (int q = 0; q < NHI; ++q) {
     const int hr = (wave + 4 * q) * 8 + lrow;
-    uint32_t off = 0x80000000u;  // out of the buffer: the DMA writes zeros
+    uint32_t off = DMA_OOB;  // out of the buffer: the DMA writes zeros
     if (q < p.nhi && hr < p.nh) {
       const int i = (int)fdiv((uint32_t)hr, p.fd_hb), rem = hr - i * p.hb;
       const int hy = (int)fdiv((uint32_t)rem, p.fd_w2), hx = rem - hy * W2;
       int y, x;
       if constexpr (GEN) {  // box row hy; box (padded-local) column lc: stride 2 column-split as below
-        const int lc = ST == 1 ? hx : (hx < p.hwh ? 2 * hx : (hx < 2 * p.hwh - 1 ? 2 * (hx - p.hwh) + 1 : -1));
+        const int lc = halo_box_col<ST>(hx, p.hwh);
         y = ST * y0 + hy - 1;
         x = ST * q0 + lc - 1;
         if (lc >= 0 && n0 < p.N && (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W)
           off = (uint32_t)(((hy * p.W + lc) * p.Cin + (pc ^ hswz(hr)) * 8) * 2);
         hoff[q] = off;
         continue;
-      } else if constexpr (ST == 1) {
-        y = y0 + hy - 1;
-        x = hx - 1;
-      } else {  // column-split halo: input row 2*y0 - 1 + hy, padded column 2*hx or 2*(hx - hwh) + 1
-        y = 2 * y0 + hy - 1;
-        x = hx < p.hwh ? 2 * hx - 1 : (hx < 2 * p.hwh ? 2 * (hx - p.hwh) : -1);
+      } else {  // input row ST y0 - 1 + hy, padded column hx (column-split at stride 2)
+        y = ST * y0 + hy - 1;
+        x = halo_box_col<ST>(hx, p.hwh) - 1;
       }
       const int n = n0 + i;
       if (n < p.N && (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W)
@@ -220,7 +218,7 @@ __global__ void __launch_bounds__(256, 2) conv_halo_kernel(const HConvParams p) 
 #pragma unroll
     for (int q = 0; q < NHI; ++q) {
       if (q >= q_lo && q < q_hi && (!all || q < p.nhi)) {
-        const uint32_t o = hoff[q] == 0x80000000u ? 0x80000000u : hoff[q] + (uint32_t)(cc * 128);
+        const uint32_t o = hoff[q] == DMA_OOB ? DMA_OOB : hoff[q] + (uint32_t)(cc * 128);
         buf_lds16(gsrc, GEN ? 0x7ffffff0u : p.src_bytes, dst + (wave + 4 * q) * 1024, o);
       }
     }
@@ -260,9 +258,7 @@ __global__ void __launch_bounds__(256, 2) conv_halo_kernel(const HConvParams p) 
   for (int t = 0; t < 9; ++t)
 #pragma unroll
     for (int j = 0; j < FN; ++j) {
-      const int ts = t % 3;
-      const int row = hbr[j] + (t / 3) * W2 + (ST == 1 ? ts : (ts & 1) * p.hwh + (ts >> 1));
-      boff[t][j] = (uint32_t)(row * 128 + (((lane >> 4) ^ hswz(row)) << 4));
+      boff[t][j] = halo_frag_off(hbr[j] + halo_tap_shift<ST>(t, W2, p.hwh), lane);
     }
   typedef __attribute__((address_space(3))) bf16x8 lds_bf16x8;
 
@@ -341,21 +337,17 @@ __global__ void __launch_bounds__(256, 2) conv_halo_kernel(const HConvParams p) 
     }
   };
 
-  // ---- main loop: chunk pairs x 9 unrolled taps. Weights: a WS-slot ring; step (c, tap) reads slot
-  // (c + tap) & 1 (WS = 2; 9 is odd) or tap % 3 (WS = 3; 9 = 3 x 3) -- static after the unrolling.
-  // WS = 2: the next step's weights are issued right before this step's MFMAs and waited for with
-  // vmcnt(0) at the next step. WS = 3: two steps of weights in flight; a step waits only until its
-  // own weights (and any older halo DMA) landed: vmcnt(NIW) leaves the next step's NIW weight DMAs
-  // outstanding, vmcnt(0) where nothing younger exists (the last step) or where the NHB = 1 halo
+  // ---- main loop: chunk pairs x 9 unrolled taps. Weights: a 3-slot ring; step (c, tap) reads slot
+  // tap % 3 (9 = 3 x 3) -- static after the unrolling. Two steps of weights in flight; a step waits only
+  // until its own weights (and any older halo DMA) landed: vmcnt(NIW) leaves the next step's NIW weight
+  // DMAs outstanding, vmcnt(0) where nothing younger exists (the last step) or where the NHB = 1 halo
   // reload is the youngest DMA (a chunk's first step).
   // Halo: NHB = 2 double-buffers it (the next chunk's halo arrives in slices during the current
   // chunk's first eight taps; buffer c & 1), NHB = 1 reloads it at chunk boundaries.
   const int nsteps = p.nchunk * 9;
   stage_h(smem, c0, 0, NHI);
   stage_w(wbase, c0, 0);
-  if constexpr (WS == 3) {
-    if (nsteps > 1) stage_w(wbase + WBYTES, c0, 1);
-  }
+  if (nsteps > 1) stage_w(wbase + WBYTES, c0, 1);
   for (int cc = 0; cc < p.nchunk; cc += 2) {
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
@@ -365,15 +357,11 @@ __global__ void __launch_bounds__(256, 2) conv_halo_kernel(const HConvParams p) 
 #pragma unroll
       for (int tap = 0; tap < 9; ++tap) {
         const int step = c * 9 + tap;
-        if constexpr (WS == 3) {
-          // NHB = 2: the next chunk's halo slices of the two previous steps may stay in flight as well (issued after
-          // their step's weights, so younger than this step's weights; the chunk's first step needs them all)
-          if (step + 1 < nsteps && !(NHB == 1 && tap == 0 && c > 0)) {
-            if (NHB == 2 && tap >= 1 && c + 1 < p.nchunk) wait_vm_slices<NIW, NHI>(tap);
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NIW) : "memory");
-          } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          }
+        // NHB = 2: the next chunk's halo slices of the two previous steps may stay in flight as well (issued after
+        // their step's weights, so younger than this step's weights; the chunk's first step needs them all)
+        if (step + 1 < nsteps && !(NHB == 1 && tap == 0 && c > 0)) {
+          if (NHB == 2 && tap >= 1 && c + 1 < p.nchunk) wait_vm_slices<NIW, NHI>(tap);
+          else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NIW) : "memory");
         } else {
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
@@ -381,27 +369,21 @@ __global__ void __launch_bounds__(256, 2) conv_halo_kernel(const HConvParams p) 
         asm volatile("" ::: "memory");
         if (step == 0) phase_mark(p.phase, 1);
         if (c == 1 && tap == 0) phase_mark(p.phase, 2);
-        if constexpr (WS == 3) {  // weights of step + 2 into the slot step - 1 used
-          if (tap + 2 <= 8) stage_w(wbase + ((tap + 2) % 3) * WBYTES, c0 + c, tap + 2);
-          else if (c + 1 < p.nchunk) stage_w(wbase + ((tap + 2) % 3) * WBYTES, c0 + c + 1, tap + 2 - 9);
-          // SC: W_sc chunk c issued right after the centre tap's weights (step + 2 = (c, 4)): it is older
-          // than the step-(c, 5) weights, so the centre step's counted vmcnt(NIW) covers it
-          if constexpr (SC) {
-            if (tap == 2) stage_sc(c0 + c);
-          }
-        } else {
-          const int par = (half + tap) & 1;
-          if (tap < 8) stage_w(wbase + (par ^ 1) * WBYTES, c0 + c, tap + 1);
-          else if (c + 1 < p.nchunk) stage_w(wbase + (par ^ 1) * WBYTES, c0 + c + 1, 0);
+        // weights of step + 2 into the slot step - 1 used
+        if (tap + 2 <= 8) stage_w(wbase + ((tap + 2) % 3) * WBYTES, c0 + c, tap + 2);
+        else if (c + 1 < p.nchunk) stage_w(wbase + ((tap + 2) % 3) * WBYTES, c0 + c + 1, tap + 2 - 9);
+        // SC: W_sc chunk c issued right after the centre tap's weights (step + 2 = (c, 4)): it is older
+        // than the step-(c, 5) weights, so the centre step's counted vmcnt(NIW) covers it
+        if constexpr (SC) {
+          if (tap == 2) stage_sc(c0 + c);
         }
         if constexpr (NHB == 2) {
           if (c + 1 < p.nchunk && tap < 8) {  // next chunk's halo, slice `tap` of 8
-            // static slices of the NHI instructions (WS = 3: counted in the waits above; rows past the halo zeroed)
-            if constexpr (WS == 3) stage_h(smem + (half ^ 1) * HBYTES, c0 + c + 1, (tap * NHI) >> 3, ((tap + 1) * NHI) >> 3, false);
-            else stage_h(smem + (half ^ 1) * HBYTES, c0 + c + 1, (tap * p.nhi) >> 3, ((tap + 1) * p.nhi) >> 3);
+            // static slices of the NHI instructions (counted in the waits above; rows past the halo zeroed)
+            stage_h(smem + (half ^ 1) * HBYTES, c0 + c + 1, (tap * NHI) >> 3, ((tap + 1) * NHI) >> 3, false);
           }
         }
-        compute(hbuf, wbase + (WS == 3 ? (tap % 3) : ((half + tap) & 1)) * WBYTES, tap);
+        compute(hbuf, wbase + (tap % 3) * WBYTES, tap);
         if constexpr (SC) {
           if (tap == 4) compute_sc(hbuf);
         }
@@ -453,14 +435,14 @@ __global__ void __launch_bounds__(256, 2) conv_halo_kernel(const HConvParams p) 
       const int pix = slot_pix(bcol0 + j * 16 + cl);
 #pragma unroll
       for (int i = 0; i < FM; ++i)
-        eoff[i][j] = pix < M ? (uint32_t)(((size_t)pix * p.Cout + a0 + arow0 + i * 16 + rq) * 4) : 0x80000000u;
+        eoff[i][j] = pix < M ? (uint32_t)(((size_t)pix * p.Cout + a0 + arow0 + i * 16 + rq) * 4) : DMA_OOB;
     }
     const uint32_t own = (uint32_t)((size_t)split * plane * 4);
 #pragma unroll
     for (int i = 0; i < FM; ++i)
 #pragma unroll
       for (int j = 0; j < FN; ++j)
-        if (eoff[i][j] != 0x80000000u)
+        if (eoff[i][j] != DMA_OOB)
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[i][j]), rs, own + eoff[i][j], 0, 16);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -500,7 +482,7 @@ __global__ void __launch_bounds__(256, 2) conv_halo_kernel(const HConvParams p) 
         for (int i = 0; i < FM; ++i)
 #pragma unroll
           for (int j = 0; j < FN; ++j)
-            part[u][i][j] = ld && eoff[i][j] != 0x80000000u
+            part[u][i][j] = ld && eoff[i][j] != DMA_OOB
                                 ? __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, base + eoff[i][j], 0, 16))
                                 : f32x4{0.f, 0.f, 0.f, 0.f};
       }
@@ -519,21 +501,13 @@ __global__ void __launch_bounds__(256, 2) conv_halo_kernel(const HConvParams p) 
 #pragma unroll
       for (int j = 0; j < FN; ++j) acc[i][j] = sum[i][j];
   }
-  // 16-B epilogue accesses (MI355X guide T21 for the 16x16 MFMA layout; as conv_c64.hip): lanes l and l ^ 16 hold
-  // channels rq.. and rq + 4.. of the same pixel, so one v_permlane16_swap per dword of a fragment pair (2q, 2q+1)
-  // leaves 8 consecutive channels per lane -- one dwordx4 store instead of two dwordx2 (issue-bound epilogues).
-  // Both lanes of a swap pair hold the same pixel, so a pixel's validity is uniform across each swap.
+  // 16-B epilogue accesses (frag_pair_pack / frag_pair_unpack, tile_common.h): both lanes of a swap pair hold the
+  // same pixel, so a pixel's validity is uniform across each swap.
   // (the lane id through an opaque move: the epilogue's lane-dependent offsets are computed here, not hoisted
   // before the main loop and held across it -- the 64 x 256 kernels run at the 2-waves-per-SIMD register limit)
   int ln;
   asm volatile("v_mov_b32 %0, %1" : "=v"(ln) : "v"(lane));
-  const int r4 = ln >> 4;
-  const int wch = (r4 & 1) * 16 + (r4 >> 1) * 8;  // this lane's first channel within a fragment pair (16 B)
-  auto swap2 = [](uint32_t& x, uint32_t& y) {  // rows 1 / 3 of x <-> rows 0 / 2 of y
-    const auto r = __builtin_amdgcn_permlane16_swap(x, y, false, false);
-    x = r[0];
-    y = r[1];
-  };
+  const int wch = frag_pair_channel(ln);  // this lane's first channel within a fragment pair (16 B)
   static_assert(FM % 2 == 0, "fragment pairs");
   if constexpr (MODE == 0) {
     float* red = (float*)smem;  // [WC][BM][2]
@@ -566,10 +540,8 @@ __global__ void __launch_bounds__(256, 2) conv_halo_kernel(const HConvParams p) 
         }
 #pragma unroll
         for (int q = 0; q < FM / 2; ++q) {
-          uint32_t x0 = pk[2 * q][0], x1 = pk[2 * q][1], y0 = pk[2 * q + 1][0], y1 = pk[2 * q + 1][1];
-          swap2(x0, y0);
-          swap2(x1, y1);
-          if (pix < M) *(uint4*)(outp + (size_t)pix * p.Cout + a0 + arow0 + q * 32 + wch) = uint4{x0, x1, y0, y1};
+          const uint4 v = frag_pair_pack(pk[2 * q], pk[2 * q + 1]);
+          if (pix < M) *(uint4*)(outp + (size_t)pix * p.Cout + a0 + arow0 + q * 32 + wch) = v;
         }
       }
       if (want_stats) {
@@ -583,22 +555,13 @@ __global__ void __launch_bounds__(256, 2) conv_halo_kernel(const HConvParams p) 
           }
           if ((lane & 15) == 0) {
 #pragma unroll
-            for (int t = 0; t < 4; ++t) {
+            for (int t = 0; t < 4; ++t) {  // the [WC][BM][2] staging stats_fold reads
               red[(wc * BM + chl + t) * 2 + 0] = s4[i][t];
               red[(wc * BM + chl + t) * 2 + 1] = q4[i][t];
             }
           }
         }
-        __syncthreads();
-        if ((int)threadIdx.x < BM) {
-          float s = 0.f, q = 0.f;
-#pragma unroll
-          for (int w = 0; w < WC; ++w) {
-            s += red[(w * BM + threadIdx.x) * 2 + 0];
-            q += red[(w * BM + threadIdx.x) * 2 + 1];
-          }
-          stat_add(stp, p.Cout, a0 + threadIdx.x, s, q);
-        }
+        stats_fold<WC, BM>(red, stp, p.Cout, a0);
       }
     };
     epi_fwd(acc2, acc, false, p.out, p.stats);
@@ -617,10 +580,11 @@ __global__ void __launch_bounds__(256, 2) conv_halo_kernel(const HConvParams p) 
       for (int q = 0; q < FM / 2; ++q) rr[q] = p.res && ok ? *(const uint4*)(p.res + o + q * 32) : uint4{0u, 0u, 0u, 0u};
       uint32_t res2[FM][2];
 #pragma unroll
-      for (int q = 0; q < FM / 2; ++q) {  // back to the MFMA layout (the swap is an involution)
+      for (int q = 0; q < FM / 2; ++q) {  // frag_pair_unpack written out: through the helper the 128-row DGRAD
+        // instances take 4 more VGPRs (128 x 128) / spill 2 more (128 x 256)
         uint32_t x0 = rr[q].x, x1 = rr[q].y, y0 = rr[q].z, y1 = rr[q].w;
-        swap2(x0, y0);
-        swap2(x1, y1);
+        swap16(x0, y0);
+        swap16(x1, y1);
         res2[2 * q][0] = x0; res2[2 * q][1] = x1;
         res2[2 * q + 1][0] = y0; res2[2 * q + 1][1] = y1;
       }
@@ -636,10 +600,8 @@ __global__ void __launch_bounds__(256, 2) conv_halo_kernel(const HConvParams p) 
       }
 #pragma unroll
       for (int q = 0; q < FM / 2; ++q) {
-        uint32_t x0 = pk[2 * q][0], x1 = pk[2 * q][1], y0 = pk[2 * q + 1][0], y1 = pk[2 * q + 1][1];
-        swap2(x0, y0);
-        swap2(x1, y1);
-        if (ok) *(uint4*)(p.out + o + q * 32) = uint4{x0, x1, y0, y1};
+        const uint4 v = frag_pair_pack(pk[2 * q], pk[2 * q + 1]);
+        if (ok) *(uint4*)(p.out + o + q * 32) = v;
       }
     }
   }
@@ -651,7 +613,7 @@ __global__ void __launch_bounds__(256, 2) conv_halo_kernel(const HConvParams p) 
 struct HaloCfg {
   int bm, bn, nhb, hcap, st;
 };
-// Template instances (launch_halo_ws below). LDS: NHB * HCAP * 128 + WS * BM * 128 (+ BM * 128 with SC).
+// Template instances (launch_halo below). LDS: NHB * HCAP * 128 + 3 * BM * 128 (+ BM * 128 with SC).
 static const HaloCfg kHaloCfgs[] = {
     {64, 256, 1, 416, 1},   // 0: 70 KB, 2 WG/CU: big images / many tiles
     {64, 128, 2, 288, 1},   // 1: 90 KB: double-buffered halo, no chunk bubbles
@@ -669,39 +631,28 @@ static const HaloCfg kHaloCfgs[] = {
 constexpr int kNumHaloCfgs = (int)(sizeof(kHaloCfgs) / sizeof(kHaloCfgs[0]));
 constexpr int kFirstS2Cfg = 8;
 
-// Halo row pitch of the column-split stride-2 layout: 2 (Wo + 1) input columns, +2 where a 16-pixel
-// fragment spans output rows of width Wo = 8 mod 16 (the +1-output-row offset 2 * pitch must be 8 mod
-// 16 rows there for the ds_read_b128 lane groups to hit distinct bank slots; tools/halo_banks.py).
-
 // Output tile geometry: `rows` output rows of one image slice or `imgs` whole images per tile, the
 // halo rows per slice (hb) and per tile (nh), the halo row pitch and (stride 2) the split point hwh.
+// General geometry: rows x seg.seg columns of one image per tile (seg; cols = the columns of a slice either way).
 struct HaloGeom {
-  int rows, imgs, hb, nh, pitch, hwh, ho, wo;
+  int rows, imgs, hb, nh, pitch, hwh, ho, wo, cols;
+  SegTile seg;
 };
+// halo box of rows x cols output pixels of one image slice at stride st
+static void halo_box(int st, HaloGeom& g) {
+  g.pitch = st == 1 ? g.cols + 2 : s2_pitch(g.cols);
+  g.hwh = st == 1 ? 0 : g.cols + 1;
+  g.hb = st == 1 ? halo_box_s1(g.rows, g.cols) : halo_box_s2(g.rows, g.cols);
+  g.nh = g.imgs * g.hb;
+}
 static bool halo_geometry(const ConvShape& s, int st, int bn, int hcap, HaloGeom& g) {
   g.ho = s.H / st;
-  g.wo = s.W / st;
-  const int hw = g.ho * g.wo;
-  if (hw >= bn) {
-    if (bn % g.wo) return false;
-    g.rows = bn / g.wo;
-    if (g.ho % g.rows) return false;
-    g.imgs = 1;
-  } else {
-    if (bn % hw) return false;
-    g.imgs = bn / hw;
-    g.rows = g.ho;
-  }
-  if (st == 1) {
-    g.pitch = s.W + 2;
-    g.hwh = 0;
-    g.hb = (g.rows + 2) * g.pitch;
-  } else {
-    g.pitch = s2_pitch(g.wo);
-    g.hwh = g.wo + 1;
-    g.hb = (2 * g.rows + 1) * g.pitch;
-  }
-  g.nh = g.imgs * g.hb;
+  g.cols = g.wo = s.W / st;
+  TileSplit t;
+  if (!classic_tile(g.ho, g.wo, bn, t)) return false;
+  g.rows = t.rows;
+  g.imgs = t.imgs;
+  halo_box(st, g);
   return g.nh <= hcap;
 }
 
@@ -715,41 +666,26 @@ static int halo_tiles_b(const ConvShape& s, const HaloGeom& g) {
   return g.imgs == 1 ? s.N * (g.ho / g.rows) : (s.N + g.imgs - 1) / g.imgs;
 }
 
-// General tile geometry (stride 1, option halo_gen): gseg columns per row segment (the row if it has at most
-// 64 pixels, else a 64- / 56- / 32-pixel piece of it), grs rows of segments per tile (the most that fit BN
-// slots and divide H). Used where the classic whole-row / whole-image tiles do not fit (the 224x224 model).
-struct HaloGen {
-  int seg = 0, rs = 0, spr = 0, tpi = 0, nh = 0;
-};
-static bool halo_gen_geometry(const ConvShape& s, int bn, int hcap, HaloGen& g) {
+// General tile geometry (option halo_gen; stride 1, or the stride-2 forward's output grid with its column-split
+// input box): seg columns per row segment (the row if it has at most 64 pixels, else a 64- / 56- / 32-pixel
+// piece of it), as many rows of segments per tile as fit BN slots and divide the grid's height. Used where the
+// classic whole-row / whole-image tiles do not fit (the 224x224 model).
+static bool halo_gen_geometry(const ConvShape& s, int st, int bn, int hcap, HaloGeom& g) {
   if (option_get(OPT_HALO_GEN) == 0) return false;
-  if (!conv3x3_ok(s, 1)) return false;
-  g.seg = row_segment(s.W);
-  if (g.seg == 0 || g.seg > bn) return false;
-  g.rs = std::min(bn / g.seg, s.H);
-  while (g.rs > 1 && s.H % g.rs != 0) --g.rs;
-  g.spr = s.W / g.seg;
-  g.tpi = (s.H / g.rs) * g.spr;
-  g.nh = (g.rs + 2) * (g.seg + 2);
+  if (!conv3x3_ok(s, st) || s.H % st || s.W % st) return false;
+  g.ho = s.H / st;
+  g.wo = s.W / st;
+  const int seg = row_segment(g.wo);
+  if (seg == 0 || seg > bn) return false;
+  g.seg = seg_tile(g.ho, g.wo, seg, rows_dividing(g.ho, std::min(bn / seg, g.ho)));
+  g.rows = g.seg.rs;
+  g.cols = seg;
+  g.imgs = 1;
+  halo_box(st, g);
+  const int box_rows = st == 1 ? g.rows + 2 : 2 * g.rows + 1;
   // at least half the slots real; 32-bit per-tile offsets and pixel indices
-  return g.nh <= hcap && 2 * g.rs * g.seg >= bn && (int64_t)s.N * g.tpi < (1ll << 31) &&
-         (int64_t)s.N * s.H * s.W < (1ll << 31) && (int64_t)(g.rs + 2) * s.W * std::max(s.C, s.K) * 2 < (1ll << 31);
-}
-
-// the same for the stride-2 forward (output grid Ho x Wo, column-split input box (2 rs + 1) x pitch)
-static bool halo_gen_geometry_s2(const ConvShape& s, int bn, int hcap, HaloGen& g) {
-  if (option_get(OPT_HALO_GEN) == 0) return false;
-  if (!conv3x3_ok(s, 2) || s.H % 2 || s.W % 2) return false;
-  const int ho = s.H / 2, wo = s.W / 2;
-  g.seg = row_segment(wo);
-  if (g.seg == 0 || g.seg > bn) return false;
-  g.rs = std::min(bn / g.seg, ho);
-  while (g.rs > 1 && ho % g.rs != 0) --g.rs;
-  g.spr = wo / g.seg;
-  g.tpi = (ho / g.rs) * g.spr;
-  g.nh = (2 * g.rs + 1) * s2_pitch(g.seg);
-  return g.nh <= hcap && 2 * g.rs * g.seg >= bn && (int64_t)s.N * g.tpi < (1ll << 31) &&
-         (int64_t)s.N * ho * wo < (1ll << 31) && (int64_t)(2 * g.rs + 1) * s.W * std::max(s.C, s.K) * 2 < (1ll << 31);
+  return g.nh <= hcap && 2 * g.rows * seg >= bn && (int64_t)s.N * g.seg.tpi < (1ll << 31) &&
+         (int64_t)s.N * g.ho * g.wo < (1ll << 31) && (int64_t)box_rows * s.W * std::max(s.C, s.K) * 2 < (1ll << 31);
 }
 
 static bool cfg_fits(const ConvShape& s, int cfg, int cout) {
@@ -769,8 +705,8 @@ HaloPlan conv_halo_plan(const ConvShape& s, int mode) {
       // general geometry (the 224x224 model): forced settings only (halo_s2 >= 2) -- at 224x224 the 64 x 64
       // column-split tiles (56 real slots, a 3 x 116-row input halo each) measured 1.3-1.8x the implicit GEMM's
       // 128 x 128 tiles (l2.0.conv1 419 vs 233 us at batch 64; -2% in-step), so auto keeps the GEMM
-      HaloGen g;
-      if (o2 >= 2 && s.K % 64 == 0 && halo_gen_geometry_s2(s, 64, 384, g)) {
+      HaloGeom g;
+      if (o2 >= 2 && s.K % 64 == 0 && halo_gen_geometry(s, 2, 64, 384, g)) {
         hp.cfg = kFirstS2Cfg;
         hp.gen = 1;
       }
@@ -795,10 +731,10 @@ HaloPlan conv_halo_plan(const ConvShape& s, int mode) {
   if (!halo_shape_ok(s, 1) || (opt == 1 && !cfg_fits(s, 0, cout) && !cfg_fits(s, 2, cout))) {
     // the general tile geometry: 64 x 256 tiles (4 rows of a 56-pixel segment at 224 / 112 / 56 wide rows), or
     // 64 x 128 where the tile count would leave CUs idle; no split-K (these layers have >= 1024 tiles)
-    HaloGen g0, g2;
-    const bool f0 = cout % 64 == 0 && halo_gen_geometry(s, 256, 416, g0);
-    const bool f2 = cout % 64 == 0 && halo_gen_geometry(s, 128, 288, g2);
-    if (f0 && (int64_t)s.N * g0.tpi * (cout / 64) >= 512) hp.cfg = 0;
+    HaloGeom g0, g2;
+    const bool f0 = cout % 64 == 0 && halo_gen_geometry(s, 1, 256, 416, g0);
+    const bool f2 = cout % 64 == 0 && halo_gen_geometry(s, 1, 128, 288, g2);
+    if (f0 && (int64_t)s.N * g0.seg.tpi * (cout / 64) >= 512) hp.cfg = 0;
     else if (f2) hp.cfg = 2;
     else if (f0) hp.cfg = 0;
     else return hp;
@@ -847,17 +783,17 @@ size_t conv_halo_slab_bytes(const ConvShape& s, int mode, const HaloPlan& hp) {
   return (size_t)hp.split * s.N * s.H * s.W * cout * 4;
 }
 
-template <int MODE, int WS>
-static int launch_halo_ws(const HConvParams& p, int cfg, dim3 grid, hipStream_t st) {
+template <int MODE>
+static int launch_halo(const HConvParams& p, int cfg, dim3 grid, hipStream_t st) {
   switch (cfg) {
-    case 0: DTC_KLAUNCH((conv_halo_kernel<MODE, 64, 256, 1, 4, 1, 416, WS>), grid, dim3(256), 0, st, p); break;
-    case 1: DTC_KLAUNCH((conv_halo_kernel<MODE, 64, 128, 1, 4, 2, 288, WS>), grid, dim3(256), 0, st, p); break;
-    case 2: DTC_KLAUNCH((conv_halo_kernel<MODE, 64, 128, 1, 4, 1, 288, WS>), grid, dim3(256), 0, st, p); break;
-    case 3: DTC_KLAUNCH((conv_halo_kernel<MODE, 128, 256, 2, 2, 1, 416, WS>), grid, dim3(256), 0, st, p); break;
-    case 4: DTC_KLAUNCH((conv_halo_kernel<MODE, 128, 128, 2, 2, 1, 288, WS>), grid, dim3(256), 0, st, p); break;
-    case 5: DTC_KLAUNCH((conv_halo_kernel<MODE, 128, 128, 2, 2, 2, 288, WS>), grid, dim3(256), 0, st, p); break;
-    case 6: DTC_KLAUNCH((conv_halo_kernel<MODE, 64, 128, 1, 4, 2, 224, WS>), grid, dim3(256), 0, st, p); break;
-    default: DTC_KLAUNCH((conv_halo_kernel<MODE, 64, 64, 2, 2, 2, 160, WS>), grid, dim3(256), 0, st, p); break;
+    case 0: DTC_KLAUNCH((conv_halo_kernel<MODE, 64, 256, 1, 4, 1, 416>), grid, dim3(256), 0, st, p); break;
+    case 1: DTC_KLAUNCH((conv_halo_kernel<MODE, 64, 128, 1, 4, 2, 288>), grid, dim3(256), 0, st, p); break;
+    case 2: DTC_KLAUNCH((conv_halo_kernel<MODE, 64, 128, 1, 4, 1, 288>), grid, dim3(256), 0, st, p); break;
+    case 3: DTC_KLAUNCH((conv_halo_kernel<MODE, 128, 256, 2, 2, 1, 416>), grid, dim3(256), 0, st, p); break;
+    case 4: DTC_KLAUNCH((conv_halo_kernel<MODE, 128, 128, 2, 2, 1, 288>), grid, dim3(256), 0, st, p); break;
+    case 5: DTC_KLAUNCH((conv_halo_kernel<MODE, 128, 128, 2, 2, 2, 288>), grid, dim3(256), 0, st, p); break;
+    case 6: DTC_KLAUNCH((conv_halo_kernel<MODE, 64, 128, 1, 4, 2, 224>), grid, dim3(256), 0, st, p); break;
+    default: DTC_KLAUNCH((conv_halo_kernel<MODE, 64, 64, 2, 2, 2, 160>), grid, dim3(256), 0, st, p); break;
   }
   DTC_LAUNCH_CHECK();
   return 0;
@@ -866,76 +802,33 @@ static int launch_halo_ws(const HConvParams& p, int cfg, dim3 grid, hipStream_t 
 // (The two-slot weight ring, option halo_wstages=2, is removed: 441 vs 451 us isolated in round 5 but -6.5% in the
 // step at the round-6 kernels, 0 of 10 in-process rounds faster: profiles/r06bc_b256_misc.txt.)
 
-// general tile geometry instances (3-slot weight ring): configurations 0 (64 x 256) and 2 (64 x 128); the
+// general tile geometry instances: configurations 0 (64 x 256) and 2 (64 x 128); the
 // stride-2 forward in configuration 8 (64 x 64), with or without the fused shortcut
 template <int MODE>
 static int launch_halo_gen(const HConvParams& p, int cfg, dim3 grid, hipStream_t st) {
   if (cfg == kFirstS2Cfg) {
     if (p.wsc)
-      DTC_KLAUNCH((conv_halo_kernel<0, 64, 64, 2, 2, 1, 384, 3, 2, true, true>), grid, dim3(256), 0, st, p);
+      DTC_KLAUNCH((conv_halo_kernel<0, 64, 64, 2, 2, 1, 384, 2, true, true>), grid, dim3(256), 0, st, p);
     else
-      DTC_KLAUNCH((conv_halo_kernel<0, 64, 64, 2, 2, 1, 384, 3, 2, false, true>), grid, dim3(256), 0, st, p);
+      DTC_KLAUNCH((conv_halo_kernel<0, 64, 64, 2, 2, 1, 384, 2, false, true>), grid, dim3(256), 0, st, p);
   } else if (cfg == 0)
-    DTC_KLAUNCH((conv_halo_kernel<MODE, 64, 256, 1, 4, 1, 416, 3, 1, false, true>), grid, dim3(256), 0, st, p);
+    DTC_KLAUNCH((conv_halo_kernel<MODE, 64, 256, 1, 4, 1, 416, 1, false, true>), grid, dim3(256), 0, st, p);
   else
-    DTC_KLAUNCH((conv_halo_kernel<MODE, 64, 128, 1, 4, 1, 288, 3, 1, false, true>), grid, dim3(256), 0, st, p);
+    DTC_KLAUNCH((conv_halo_kernel<MODE, 64, 128, 1, 4, 1, 288, 1, false, true>), grid, dim3(256), 0, st, p);
   DTC_LAUNCH_CHECK();
   return 0;
 }
 
-// stride-2 forward instances (3-slot weight ring), with or without the fused shortcut
+// stride-2 forward instances, with or without the fused shortcut
 template <bool SC>
 static int launch_halo_s2(const HConvParams& p, int cfg, dim3 grid, hipStream_t st) {
   switch (cfg) {
-    case 8: DTC_KLAUNCH((conv_halo_kernel<0, 64, 64, 2, 2, 1, 384, 3, 2, SC>), grid, dim3(256), 0, st, p); break;
-    case 9: DTC_KLAUNCH((conv_halo_kernel<0, 64, 128, 1, 4, 1, 768, 3, 2, SC>), grid, dim3(256), 0, st, p); break;
-    default: DTC_KLAUNCH((conv_halo_kernel<0, 128, 64, 2, 2, 1, 384, 3, 2, SC>), grid, dim3(256), 0, st, p); break;
+    case 8: DTC_KLAUNCH((conv_halo_kernel<0, 64, 64, 2, 2, 1, 384, 2, SC>), grid, dim3(256), 0, st, p); break;
+    case 9: DTC_KLAUNCH((conv_halo_kernel<0, 64, 128, 1, 4, 1, 768, 2, SC>), grid, dim3(256), 0, st, p); break;
+    default: DTC_KLAUNCH((conv_halo_kernel<0, 128, 64, 2, 2, 1, 384, 2, SC>), grid, dim3(256), 0, st, p); break;
   }
   DTC_LAUNCH_CHECK();
   return 0;
-}
-
-static int conv_halo_general(const ConvShape& s, int mode, const HaloPlan& hp, const u16* src, const u16* w, u16* out,
-                             const u16* res, int64_t* stats, hipStream_t st, u64* ts, const u16* wsc, u16* out2,
-                             int64_t* stats2) {
-  DTC_CHECK_ARG(hp.cfg == 0 || hp.cfg == 2 || hp.cfg == kFirstS2Cfg, "conv_halo: general geometry configuration");
-  const HaloCfg& c = kHaloCfgs[hp.cfg];
-  const int ST = c.st;
-  DTC_CHECK_ARG(ST == 1 || (mode == CONV_FWD && res == nullptr), "conv_halo: general stride 2 is FWD only");
-  DTC_CHECK_ARG(wsc == nullptr || (ST == 2 && out2 != nullptr), "conv_halo: the shortcut fusion is stride-2 FWD");
-  HaloGen g;
-  DTC_CHECK_ARG(ST == 1 ? halo_gen_geometry(s, c.bn, c.hcap, g) : halo_gen_geometry_s2(s, c.bn, c.hcap, g),
-                "conv_halo: general geometry does not fit config %d", hp.cfg);
-  HConvParams p{};
-  p.src = src; p.w = w; p.out = out; p.res = res; p.stats = stats;
-  p.wsc = wsc; p.out2 = out2; p.stats2 = stats2;
-  p.N = s.N; p.H = s.H; p.W = s.W; p.C = s.C;
-  p.Cin = mode == CONV_FWD ? s.C : s.K;
-  p.Cout = mode == CONV_FWD ? s.K : s.C;
-  DTC_CHECK_ARG(p.Cout % c.bm == 0, "conv_halo: output channels %d not a multiple of %d", p.Cout, c.bm);
-  p.rows = g.rs; p.imgs = 1; p.nh = g.nh; p.hb = g.nh;
-  p.Ho = s.H / ST; p.Wo = s.W / ST;
-  p.pitch = ST == 1 ? g.seg + 2 : s2_pitch(g.seg);
-  p.hwh = ST == 1 ? 0 : g.seg + 1;
-  p.gseg = g.seg; p.grs = g.rs; p.gtpi = g.tpi; p.gspr = g.spr;
-  p.fd_gtpi = make_fastdiv(g.tpi);
-  p.fd_gspr = make_fastdiv(g.spr);
-  p.slab = nullptr;  // (no split-K: >= 1024 tiles at the sizes this geometry serves)
-  p.src_bytes = 0;
-  p.nhi = (p.nh + 31) / 32;
-  p.tiles_y = p.Ho / g.rs;
-  p.tiles_a = p.Cout / c.bm;
-  p.nchunk = p.Cin / 64;
-  p.xcd_remap = option_get(OPT_XCD_REMAP);
-  p.fd_hb = make_fastdiv(p.hb);
-  p.fd_w2 = make_fastdiv(p.pitch);
-  p.fd_spx = make_fastdiv(g.rs * g.seg);
-  p.fd_w = make_fastdiv(p.Wo);
-  p.ts = ts;
-  const int64_t ntiles = (int64_t)s.N * g.tpi * p.tiles_a;
-  DTC_CHECK_ARG(ntiles < (1ll << 31), "conv_halo: too many tiles");
-  const dim3 grid((unsigned)ntiles, 1);
-  return mode == CONV_FWD ? launch_halo_gen<0>(p, hp.cfg, grid, st) : launch_halo_gen<1>(p, hp.cfg, grid, st);
 }
 
 #ifdef DTC_PHASES
@@ -952,8 +845,13 @@ int conv_halo(const ConvShape& s, int mode, const HaloPlan& hp, const u16* src, 
   DTC_CHECK_ARG(hp.cfg >= 0 && hp.cfg < kNumHaloCfgs && (mode == CONV_FWD || mode == CONV_DGRAD),
                 "conv_halo: unsupported configuration");
   const HaloCfg& c = kHaloCfgs[hp.cfg];
-  if (hp.gen) return conv_halo_general(s, mode, hp, src, w, out, res, stats, st, ts, wsc, out2, stats2);
-  DTC_CHECK_ARG(halo_shape_ok(s, c.st) && (c.st == 1 || mode == CONV_FWD), "conv_halo: unsupported shape / pass");
+  const bool gen = hp.gen != 0;
+  if (gen) {
+    DTC_CHECK_ARG(hp.cfg == 0 || hp.cfg == 2 || hp.cfg == kFirstS2Cfg, "conv_halo: general geometry configuration");
+    DTC_CHECK_ARG(c.st == 1 || (mode == CONV_FWD && res == nullptr), "conv_halo: general stride 2 is FWD only");
+  } else {
+    DTC_CHECK_ARG(halo_shape_ok(s, c.st) && (c.st == 1 || mode == CONV_FWD), "conv_halo: unsupported shape / pass");
+  }
   DTC_CHECK_ARG(wsc == nullptr || (c.st == 2 && out2 != nullptr), "conv_halo: the shortcut fusion is stride-2 FWD");
   HConvParams p{};
   p.src = src; p.w = w; p.out = out; p.res = res; p.stats = stats;
@@ -963,16 +861,18 @@ int conv_halo(const ConvShape& s, int mode, const HaloPlan& hp, const u16* src, 
   p.Cout = mode == CONV_FWD ? s.K : s.C;
   DTC_CHECK_ARG(p.Cout % c.bm == 0, "conv_halo: output channels %d not a multiple of %d", p.Cout, c.bm);
   HaloGeom g;
-  DTC_CHECK_ARG(halo_geometry(s, c.st, c.bn, c.hcap, g), "conv_halo: geometry does not fit config %d", hp.cfg);
+  DTC_CHECK_ARG(gen ? halo_gen_geometry(s, c.st, c.bn, c.hcap, g) : halo_geometry(s, c.st, c.bn, c.hcap, g),
+                "conv_halo: %sgeometry does not fit config %d", gen ? "general " : "", hp.cfg);
   p.rows = g.rows; p.imgs = g.imgs; p.nh = g.nh; p.hb = g.hb;
   p.Ho = g.ho; p.Wo = g.wo; p.pitch = g.pitch; p.hwh = g.hwh;
   const int M = s.N * g.ho * g.wo;
-  const int split = hp.split;  // (conv_route planned one split where the slab on hand is too small)
+  // general geometry: no split-K (>= 1024 tiles at the sizes it serves), every access from a 64-bit per-tile base
+  const int split = gen ? 1 : hp.split;  // (conv_route planned one split where the slab on hand is too small)
   DTC_CHECK_ARG(split == 1 || slab != nullptr, "conv_halo: split-K needs the slab");
   DTC_CHECK_ARG((p.Cin / 64) % split == 0, "conv_halo: split %d does not divide the reduction", split);
   DTC_CHECK_ARG(split == 1 || c.st == 1, "conv_halo: stride 2 has no split-K");
   p.slab = split > 1 ? slab : nullptr;
-  p.src_bytes = (uint32_t)((uint64_t)s.N * s.H * s.W * p.Cin * 2);
+  p.src_bytes = gen ? 0u : (uint32_t)((uint64_t)s.N * s.H * s.W * p.Cin * 2);
   p.nhi = (p.nh + 31) / 32;
   p.tiles_y = g.ho / p.rows;
   p.tiles_a = p.Cout / c.bm;
@@ -980,12 +880,21 @@ int conv_halo(const ConvShape& s, int mode, const HaloPlan& hp, const u16* src, 
   p.xcd_remap = option_get(OPT_XCD_REMAP);
   p.fd_hb = make_fastdiv(p.hb);
   p.fd_w2 = make_fastdiv(p.pitch);
-  p.fd_spx = make_fastdiv(p.rows * g.wo);
+  p.fd_spx = make_fastdiv(p.rows * g.cols);
   p.fd_w = make_fastdiv(g.wo);
   p.ts = ts;
 #ifdef DTC_PHASES
   p.phase = g_phase;
 #endif
+  if (gen) {
+    p.gseg = g.seg.seg; p.grs = g.seg.rs; p.gtpi = g.seg.tpi; p.gspr = g.seg.spr;
+    p.fd_gtpi = make_fastdiv(g.seg.tpi);
+    p.fd_gspr = make_fastdiv(g.seg.spr);
+    const int64_t ntiles = (int64_t)s.N * g.seg.tpi * p.tiles_a;
+    DTC_CHECK_ARG(ntiles < (1ll << 31), "conv_halo: too many tiles");
+    const dim3 grid((unsigned)ntiles, 1);
+    return mode == CONV_FWD ? launch_halo_gen<0>(p, hp.cfg, grid, st) : launch_halo_gen<1>(p, hp.cfg, grid, st);
+  }
   const dim3 grid(halo_tiles_b(s, g) * p.tiles_a, split);
   // split-K reduced in the kernel (the last workgroup of each tile) when the caller gave arrival counters
   // for the grid (tick: >= DTC_TICKS zeroed words, reserved for this stream) and option splitk_ink is on
@@ -994,7 +903,7 @@ int conv_halo(const ConvShape& s, int mode, const HaloPlan& hp, const u16* src, 
   if (c.st == 2) {
     return wsc ? launch_halo_s2<true>(p, hp.cfg, grid, st) : launch_halo_s2<false>(p, hp.cfg, grid, st);
   }
-  DTC_TRY(mode == CONV_FWD ? (launch_halo_ws<0, 3>(p, hp.cfg, grid, st)) : (launch_halo_ws<1, 3>(p, hp.cfg, grid, st)));
+  DTC_TRY(mode == CONV_FWD ? launch_halo<0>(p, hp.cfg, grid, st) : launch_halo<1>(p, hp.cfg, grid, st));
   if (split > 1 && !ink) return splitk_reduce(slab, split, M, p.Cout, out, res, stats, st, ts);
   return 0;
 }

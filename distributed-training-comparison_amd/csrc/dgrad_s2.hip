@@ -12,7 +12,7 @@
 // implicit-GEMM parity classes (igemm.hip) do: the nine (offset, class, tap) steps read it at four offsets,
 // each offset's B fragments read once for all the classes that use it. Weights: one W^T tap image [k][c] per
 // step (3-slot LDS ring, read with ds_read_b64_tr_b16), the shortcut's Wsc^T as a tenth step against a dsc
-// tile of the positions (class (0, 0) only). Epilogue: 16-B stores (permlane16 pair swap, conv_halo.hip).
+// tile of the positions (class (0, 0) only). Epilogue: 16-B stores (frag_pair_pack, tile_common.h).
 #include "common.h"
 #include "kernels.h"
 #include "tile_common.h"
@@ -98,7 +98,7 @@ __global__ void __launch_bounds__(256, 2) dgrad_s2_kernel(const S2dParams p) {
       for (int j = 0; j < 2; ++j) glds16(p.wsc + (size_t)cc * 64 * p.C + offSc[j], dst + (wave + 4 * j) * 1024);
       return;
     }
-    const int tap = t == 0 ? 4 : t == 1 ? 5 : t == 2 ? 7 : t == 3 ? 8 : t == 4 ? 3 : t == 5 ? 6 : t == 6 ? 1 : t == 7 ? 2 : 0;
+    const int tap = s2_tap(t);
 #pragma unroll
     for (int j = 0; j < 2; ++j)
       glds16(p.w + (size_t)cc * 64 * RSC + tap * p.C + offW[j], dst + (wave + 4 * j) * 1024);
@@ -109,13 +109,13 @@ __global__ void __launch_bounds__(256, 2) dgrad_s2_kernel(const S2dParams p) {
 #pragma unroll
   for (int q = 0; q < NHI; ++q) {
     const int hr = (wave + 4 * q) * 8 + lrow;
-    uint32_t off = 0x80000000u;
+    uint32_t off = DMA_OOB;
     if (hr < p.nh) {
       const int i = (int)fdiv((uint32_t)hr, p.fd_hb), rem = hr - i * p.hb;
       const int ry = (int)fdiv((uint32_t)rem, p.fd_w2), rx = rem - ry * W2;
       const int n = n0 + i, a = a0 + ry;
       if (n < p.N && a < p.Ho && rx < p.Wo)
-        off = (uint32_t)((((n * p.Ho + a) * p.Wo + rx) * p.K + (pc ^ ((((hr >> 1) & 3) << 1))) * 8) * 2);
+        off = (uint32_t)((((n * p.Ho + a) * p.Wo + rx) * p.K + (pc ^ hswz(hr)) * 8) * 2);
     }
     hoff[q] = off;
   }
@@ -125,16 +125,16 @@ __global__ void __launch_bounds__(256, 2) dgrad_s2_kernel(const S2dParams p) {
 #pragma unroll
   for (int q = 0; q < NDI; ++q) {
     const int l = (wave + 4 * q) * 8 + lrow;
-    doff[q] = p0 + l < p.npos ? (uint32_t)(((p0 + l) * p.K + (pc ^ rowswz(l)) * 8) * 2) : 0x80000000u;
+    doff[q] = p0 + l < p.npos ? (uint32_t)(((p0 + l) * p.K + (pc ^ rowswz(l)) * 8) * 2) : DMA_OOB;
   }
   auto stage_halo = [&](int cc) {
 #pragma unroll
     for (int q = 0; q < NHI; ++q)
-      buf_lds16(p.dy, p.dy_bytes, halo + (wave + 4 * q) * 1024, hoff[q] == 0x80000000u ? hoff[q] : hoff[q] + cc * 128);
+      buf_lds16(p.dy, p.dy_bytes, halo + (wave + 4 * q) * 1024, hoff[q] == DMA_OOB ? hoff[q] : hoff[q] + cc * 128);
     if constexpr (SC) {
 #pragma unroll
       for (int q = 0; q < NDI; ++q)
-        buf_lds16(p.dsc, p.dy_bytes, dtile + (wave + 4 * q) * 1024, doff[q] == 0x80000000u ? doff[q] : doff[q] + cc * 128);
+        buf_lds16(p.dsc, p.dy_bytes, dtile + (wave + 4 * q) * 1024, doff[q] == DMA_OOB ? doff[q] : doff[q] + cc * 128);
     }
   };
 
@@ -152,7 +152,7 @@ __global__ void __launch_bounds__(256, 2) dgrad_s2_kernel(const S2dParams p) {
   }
   auto boff = [&](int j, int da, int db) -> uint32_t {
     const int row = hbr[j] + da * W2 + db;
-    return (uint32_t)(row * 128 + (((lane >> 4) ^ ((((row >> 1) & 3) << 1))) << 4));
+    return halo_frag_off(row, lane);
   };
   typedef __attribute__((address_space(3))) bf16x8 lds_bf16x8;
 
@@ -210,8 +210,6 @@ __global__ void __launch_bounds__(256, 2) dgrad_s2_kernel(const S2dParams p) {
             for (int ks = 0; ks < 2; ++ks) bfr[ks][j] = *(const lds_bf16x8*)(halo + (o ^ (uint32_t)(ks * 64)));
           }
         }
-        constexpr int dummy = 0;
-        (void)dummy;
         const int cls = s2_cls(tt);
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
@@ -238,8 +236,7 @@ __global__ void __launch_bounds__(256, 2) dgrad_s2_kernel(const S2dParams p) {
   // ---- epilogue: class (py, px) of position (n, a, b) -> dx pixel (n, 2a + py, 2b + px); 16-B stores
   int ln;
   asm volatile("v_mov_b32 %0, %1" : "=v"(ln) : "v"(lane));
-  const int r4 = ln >> 4;
-  const int wch = (r4 & 1) * 16 + (r4 >> 1) * 8;
+  const int wch = frag_pair_channel(ln);
   const int H = 2 * p.Ho, W = 2 * p.Wo;
 #pragma unroll
   for (int j = 0; j < FN; ++j) {
@@ -257,18 +254,10 @@ __global__ void __launch_bounds__(256, 2) dgrad_s2_kernel(const S2dParams p) {
         pk[i][0] = pack_bf2(acc[c][i][j][0], acc[c][i][j][1]);
         pk[i][1] = pack_bf2(acc[c][i][j][2], acc[c][i][j][3]);
       }
-      uint32_t x0 = pk[0][0], x1 = pk[0][1], y0 = pk[1][0], y1 = pk[1][1];
-      {
-        const auto r0 = __builtin_amdgcn_permlane16_swap(x0, y0, false, false);
-        x0 = r0[0];
-        y0 = r0[1];
-        const auto r1 = __builtin_amdgcn_permlane16_swap(x1, y1, false, false);
-        x1 = r1[0];
-        y1 = r1[1];
-      }
+      const uint4 v = frag_pair_pack(pk[0], pk[1]);
       if (ok) {
         const size_t o = ((size_t)(n * H + 2 * a + py) * W + 2 * b + px) * p.C + c0 + arow0 + wch;
-        *(uint4*)(p.dx + o) = uint4{x0, x1, y0, y1};
+        *(uint4*)(p.dx + o) = v;
       }
     }
   }
@@ -280,16 +269,11 @@ __global__ void __launch_bounds__(256, 2) dgrad_s2_kernel(const S2dParams p) {
 static bool s2d_geometry(const ConvShape& s, int bn, int hcap, int& rows, int& imgs, int& hb, int& nh) {
   if (!conv3x3_ok(s, 2) || s.H % 2 || s.W % 2) return false;
   const int ho = s.H / 2, wo = s.W / 2, hw = ho * wo;
-  if (hw >= bn) {
-    if (bn % wo || ho % (bn / wo)) return false;
-    rows = bn / wo;
-    imgs = 1;
-  } else {
-    if (bn % hw) return false;
-    imgs = bn / hw;
-    rows = ho;
-  }
-  hb = (rows + 1) * (wo + 1);
+  TileSplit t;
+  if (!classic_tile(ho, wo, bn, t)) return false;
+  rows = t.rows;
+  imgs = t.imgs;
+  hb = halo_box_subpixel(rows, wo);
   nh = imgs * hb;
   return nh <= hcap && (uint64_t)s.N * hw * s.K * 2 < (1ull << 31) && (uint64_t)s.N * s.H * s.W * s.C * 2 < (1ull << 31);
 }

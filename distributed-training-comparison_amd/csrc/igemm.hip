@@ -65,7 +65,7 @@ struct IGemmParams {
   int sc_kt;
 };
 
-template <int MODE, int BM, int BN, int WR, int WC, bool SLAB, int NSTAGE, bool SC = false>
+template <int MODE, int BM, int BN, int WR, int WC, bool SLAB, bool SC = false>
 __global__ void __launch_bounds__(256, 2) igemm_kernel(const IGemmParams p) {
   constexpr int FM = BM / (WR * 16);
   constexpr int FN = BN / (WC * 16);
@@ -80,7 +80,9 @@ __global__ void __launch_bounds__(256, 2) igemm_kernel(const IGemmParams p) {
   static_assert(BM % 32 == 0 && BN % 32 == 0, "tile");
   static_assert(!SC || (MODE == MODE_FWD && !SLAB), "shortcut fusion: forward, no split-K");
 
-  static_assert(NSTAGE == 2 || NSTAGE == 3, "stages");
+  // LDS ring depth (a constant: the loop below keeps its ring form -- written out for two buffers, the generated
+  // code of half the instances changes)
+  constexpr int NSTAGE = 2;
   __shared__ __attribute__((aligned(1024))) char smem[NSTAGE * STAGE];
 
   stamp_start(p.ts);
@@ -89,10 +91,7 @@ __global__ void __launch_bounds__(256, 2) igemm_kernel(const IGemmParams p) {
   // XCD-aware remap (guide T1): blocks b and b+8 share an XCD's L2; give each XCD a contiguous
   // run of tile ids so the tiles that share a pixel tile (consecutive ids) share an L2.
   int bid = blockIdx.x;
-  if (p.xcd_remap && gridDim.x >= 16) {
-    const int nwg = gridDim.x, x8 = bid & 7, q = nwg >> 3, rr = nwg & 7;
-    bid = (x8 < rr ? x8 * (q + 1) : rr * (q + 1) + (x8 - rr) * q) + (bid >> 3);
-  }
+  if (p.xcd_remap && gridDim.x >= 16) bid = (int)xcd_grouped_id(blockIdx.x, gridDim.x);
   const int ta = bid % p.tiles_a;
   const int tb = bid / p.tiles_a;
   const int a0 = ta * BM, b0 = tb * BN;
@@ -308,8 +307,8 @@ __global__ void __launch_bounds__(256, 2) igemm_kernel(const IGemmParams p) {
         const bool okd = pix < p.M;
         const int ih = p0 * p.stride + wl_ih[h];
         const bool okx = okd && wl_iwok[h] && ((unsigned)ih < (unsigned)p.H);
-        xoff[h] = okx ? ubase + wl_x[h] : 0x80000000u;
-        doff[h] = okd ? (uint32_t)pix * (uint32_t)(p.K * 2) : 0x80000000u;
+        xoff[h] = okx ? ubase + wl_x[h] : DMA_OOB;
+        doff[h] = okd ? (uint32_t)pix * (uint32_t)(p.K * 2) : DMA_OOB;
       }
 #pragma unroll
       for (int j = 0; j < NIA; ++j)
@@ -407,10 +406,10 @@ __global__ void __launch_bounds__(256, 2) igemm_kernel(const IGemmParams p) {
     }
   };
 
-  // K loop over an NSTAGE-deep LDS ring filled by LDS-DMA. Iteration `it`: wait (counted
-  // vmcnt: each wave issues NIA+NIB DMAs per stage) until stage `it` has landed for this wave,
-  // barrier (then every wave's DMAs for `it` have landed and every wave finished reading the
-  // buffer of stage it-1), refill that buffer with stage it+NSTAGE-1, compute stage `it`.
+  // K loop over an NSTAGE-deep LDS ring filled by LDS-DMA. Iteration `it`: wait until stage `it` has
+  // landed for this wave (vmcnt(0): with two stages nothing younger is in flight), barrier (then every
+  // wave's DMAs for `it` have landed and every wave finished reading the buffer of stage it-1), refill
+  // that buffer with stage it+NSTAGE-1, compute stage `it`.
   // A raw s_barrier is used: __syncthreads() would also drain vmcnt to 0 (guide §5).
   if (kt_begin < kt_end) {
     const int nk = kt_end - kt_begin;
@@ -424,12 +423,7 @@ __global__ void __launch_bounds__(256, 2) igemm_kernel(const IGemmParams p) {
     }
     int cur = 0;
     for (int it = 0; it < nk; ++it) {
-      if constexpr (NSTAGE == 3) {
-        if (it + 1 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NIA + NIB) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
       const int nxt = it + NSTAGE - 1;
@@ -512,25 +506,14 @@ __global__ void __launch_bounds__(256, 2) igemm_kernel(const IGemmParams p) {
         }
         if (cl == 0) {
 #pragma unroll
-          for (int t = 0; t < 4; ++t) {
+          for (int t = 0; t < 4; ++t) {  // the [WC][BM][2] staging stats_fold reads
             red[(wc * BM + chl + t) * 2 + 0] = s4[t];
             red[(wc * BM + chl + t) * 2 + 1] = q4[t];
           }
         }
       }
     }
-    if (want_stats) {
-      __syncthreads();
-      if ((int)threadIdx.x < BM) {
-        float s = 0.f, q = 0.f;
-#pragma unroll
-        for (int w = 0; w < WC; ++w) {
-          s += red[(w * BM + threadIdx.x) * 2 + 0];
-          q += red[(w * BM + threadIdx.x) * 2 + 1];
-        }
-        stat_add(stats, p.K, a0 + threadIdx.x, s, q);
-      }
-    }
+    if (want_stats) stats_fold<WC, BM>(red, stats, p.K, a0);
     };
     epi(acc, p.out, p.stats);
     if constexpr (SC) {
@@ -813,7 +796,7 @@ static int launch_igemm(IGemmParams& p, int splits, int gz, hipStream_t st) {
   p.tiles_a = (MODE == MODE_FWD ? p.K : MODE == MODE_DGRAD ? p.C : p.RSC) / BM;
   dim3 grid(p.tiles_a * tiles_b, splits, gz);
   p.xcd_remap = option_get(OPT_XCD_REMAP);
-  DTC_KLAUNCH((igemm_kernel<MODE, BM, BN, WR, WC, SLAB, 2, SC>), grid, dim3(256), 0, st, p);
+  DTC_KLAUNCH((igemm_kernel<MODE, BM, BN, WR, WC, SLAB, SC>), grid, dim3(256), 0, st, p);
   DTC_LAUNCH_CHECK();
   return 0;
 }

@@ -281,16 +281,7 @@ __global__ void __launch_bounds__(256, 4) stem_fwd_kernel(const float* __restric
           red[wave][ch][1] = q;
         }
       }
-    __syncthreads();
-    if (t < 64) {
-      float s = 0.f, q = 0.f;
-#pragma unroll
-      for (int w = 0; w < 4; ++w) {
-        s += red[w][t][0];
-        q += red[w][t][1];
-      }
-      stat_add(stats, 64, t, s, q);
-    }
+    stats_fold<4, 64>(&red[0][0][0], stats, 64, 0);
   }
   stamp_end(ts);
 }

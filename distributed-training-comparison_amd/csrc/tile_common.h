@@ -1,6 +1,9 @@
-// Shared by the conv kernels: the host-side tile geometry rules of the halo planners, and (HIP translation
-// units only) the device helpers -- LDS-DMA loaders, the LDS swizzles, MFMA fragment readers and the
-// call-timing stamps.
+// Shared by the conv kernels, the one home of the halo family's geometry and layout rules. Host side: the
+// classic (whole rows / whole images) and general (row segment) tilings and the halo box sizes; each kernel
+// keeps its own limits (halo capacity, 32-bit offsets, its rule for the rows of a general tile) as checks on
+// these. Device side (HIP translation units only): LDS-DMA loaders, the LDS swizzles and halo fragment offsets,
+// the column-split stride-2 halo, tap shifts, the XCD-grouped workgroup id, the tile origin of the general
+// geometry, MFMA fragment readers, the 16-byte epilogue, the BN statistics fold and the call-timing stamps.
 #pragma once
 #include "common.h"
 #include "kernels.h"
@@ -17,6 +20,41 @@ inline int row_segment(int w) { return w <= 64 ? w : w % 64 == 0 ? 64 : w % 56 =
 // column-split stride-2 halo: LDS row pitch for wo output columns, 2 (wo + 1) [+ 2 where 2 * pitch must be
 // 8 mod 16 rows for the tr reads of a 64-pixel step spanning output rows]
 inline int s2_pitch(int wo) { return 2 * (wo + 1) + ((wo % 16) == 8 ? 2 : 0); }
+
+// Classic tile: `slots` consecutive positions of an ho x wo grid are slots / wo whole rows of one image
+// (imgs = 1), or slots / (ho wo) whole images (rows = ho). False where neither divides.
+struct TileSplit {
+  int rows = 0, imgs = 0;
+};
+inline bool classic_tile(int ho, int wo, int slots, TileSplit& t) {
+  const int hw = ho * wo;
+  if (hw >= slots) {
+    if (slots % wo || ho % (slots / wo)) return false;
+    t.rows = slots / wo;
+    t.imgs = 1;
+  } else {
+    if (slots % hw) return false;
+    t.rows = ho;
+    t.imgs = slots / hw;
+  }
+  return true;
+}
+// General geometry: a tile is rs rows x one seg-column segment of one image of an ho x wo grid (seg divides wo,
+// rs divides ho): spr segments per row, tpi tiles per image. Each kernel chooses seg and rs by its own rule.
+struct SegTile {
+  int seg = 0, rs = 0, spr = 0, tpi = 0;
+};
+inline SegTile seg_tile(int ho, int wo, int seg, int rs) { return SegTile{seg, rs, wo / seg, (ho / rs) * (wo / seg)}; }
+// the largest row count <= rs that divides h
+inline int rows_dividing(int h, int rs) {
+  while (rs > 1 && h % rs != 0) --rs;
+  return rs;
+}
+// Halo rows (pixels) of a rows x cols block of positions: the stride-1 box with its one-pixel border, the
+// column-split stride-2 input box, and the stride-2 sub-pixel dgrad's dy box (bottom / right neighbours)
+inline int halo_box_s1(int rows, int cols) { return (rows + 2) * (cols + 2); }
+inline int halo_box_s2(int rows, int cols) { return (2 * rows + 1) * s2_pitch(cols); }
+inline int halo_box_subpixel(int rows, int cols) { return (rows + 1) * (cols + 1); }
 
 #ifdef __HIP__
 // ------------------------------------------------------------------ device
@@ -81,7 +119,7 @@ __device__ __forceinline__ void phase_mark(u64* buf, int k) {
 __device__ __forceinline__ void phase_mark(u64*, int) {}
 #endif
 
-// Halo LDS swizzle (conv_halo.hip, conv_c64.hip): 16-B chunk c of halo row r is stored at chunk c ^ hswz(r).
+// Halo LDS swizzle (conv_halo.hip, conv_c64.hip, dgrad_s2.hip): 16-B chunk c of halo row r is stored at chunk c ^ hswz(r).
 // Every 8 B-fragment lanes that share a reduction chunk read 8 halo rows that are distinct mod 8 (the per-lane
 // pixel order of those kernels guarantees it for W = 4 and 8 too), so (row parity, chunk ^ hswz) spreads them
 // over 8 different 16-B bank slots, and the chunk pair (q, q+1) read by one ds_read_b128 lane group lands on
@@ -89,6 +127,89 @@ __device__ __forceinline__ void phase_mark(u64*, int) {}
 __device__ __forceinline__ int hswz(int r) { return ((r >> 1) & 3) << 1; }
 __device__ __forceinline__ int rowswz(int row) { return (row >> 1) & 7; }
 __device__ __forceinline__ int trswz(int row) { return (((row >> 1) & 1) << 1) | (((row >> 3) & 1) << 2); }
+// byte offset, within a halo buffer, of the B-fragment chunk (lane >> 4) of halo row `row` (k-step 1: ^ 64)
+__device__ __forceinline__ uint32_t halo_frag_off(int row, int lane) {
+  return (uint32_t)(row * 128 + (((lane >> 4) ^ hswz(row)) << 4));
+}
+
+// A buffer offset no descriptor here covers: the LDS-DMA of it writes zeros, a buffer store of it is dropped.
+constexpr uint32_t DMA_OOB = 0x80000000u;
+
+// Column-split stride-2 halo (ST = 2): halo column hx holds column 2 hx of the padded input box (hx < hwh) or
+// column 2 (hx - hwh) + 1; -1 past the box's 2 hwh - 1 columns. ST = 1: the halo column itself.
+template <int ST>
+__device__ __forceinline__ int halo_box_col(int hx, int hwh) {
+  return ST == 1 ? hx : (hx < hwh ? 2 * hx : (hx < 2 * hwh - 1 ? 2 * (hx - hwh) + 1 : -1));
+}
+// halo rows from tap (0, 0) to tap (r, s) = (tap / 3, tap % 3): r row pitches and s columns (column-split: s = 1
+// is the first odd column, hwh rows on; s = 2 the next even one)
+template <int ST>
+__device__ __forceinline__ int halo_tap_shift(int tap, int pitch, int hwh) {
+  const int ts = tap % 3;
+  return (tap / 3) * pitch + (ST == 1 ? ts : (ts & 1) * hwh + (ts >> 1));
+}
+
+// Workgroups go to the 8 XCDs round-robin by linear id: renumber id (of n) so that every XCD owns a contiguous
+// range of the new ids, whose neighbours then share an L2.
+__device__ __forceinline__ unsigned xcd_grouped_id(unsigned id, unsigned n) {
+  const unsigned x8 = id & 7, q = n >> 3, rr = n & 7;  // XCD x8 starts after x8 * q + min(x8, rr) ids
+  return x8 * q + min(x8, rr) + (id >> 3);
+}
+
+// General geometry (SegTile): image, first row and first column of tile `tile`
+__device__ __forceinline__ void seg_tile_origin(int tile, int tpi, const FastDiv& fd_tpi, int spr, const FastDiv& fd_spr,
+                                                int rs, int seg, int& n0, int& y0, int& q0) {
+  n0 = (int)fdiv((uint32_t)tile, fd_tpi);
+  const int rem = tile - n0 * tpi, yb = (int)fdiv((uint32_t)rem, fd_spr);
+  y0 = yb * rs;
+  q0 = (rem - yb * spr) * seg;
+}
+
+// 16-byte epilogue accesses of the 16x16 MFMA layout: lane l holds 4 consecutive channels of a fragment and lane
+// l ^ 16 the next four, so one v_permlane16_swap per dword of a fragment pair (2q, 2q + 1) leaves every lane 8
+// consecutive channels of one pixel -- one 16-B access per pair instead of two 8-B ones. Both lanes of a swap
+// hold the same pixel. The swap is an involution: a 16-B load goes back to the MFMA layout the same way.
+__device__ __forceinline__ void swap16(uint32_t& x, uint32_t& y) {  // rows 1 / 3 of x <-> rows 0 / 2 of y
+  const auto r = __builtin_amdgcn_permlane16_swap(x, y, false, false);
+  x = r[0];
+  y = r[1];
+}
+// this lane's first channel within the 32 channels of a fragment pair
+__device__ __forceinline__ int frag_pair_channel(int lane) {
+  const int r4 = lane >> 4;
+  return (r4 & 1) * 16 + (r4 >> 1) * 8;
+}
+// the packed bf16 words a[2], b[2] (4 channels each) of fragments 2q, 2q + 1 -> this lane's 8 channels
+__device__ __forceinline__ uint4 frag_pair_pack(const uint32_t (&a)[2], const uint32_t (&b)[2]) {
+  uint32_t x0 = a[0], x1 = a[1], y0 = b[0], y1 = b[1];
+  swap16(x0, y0);
+  swap16(x1, y1);
+  return uint4{x0, x1, y0, y1};
+}
+__device__ __forceinline__ void frag_pair_unpack(uint4 v, uint32_t (&a)[2], uint32_t (&b)[2]) {
+  uint32_t x0 = v.x, x1 = v.y, y0 = v.z, y1 = v.w;
+  swap16(x0, y0);
+  swap16(x1, y1);
+  a[0] = x0; a[1] = x1;
+  b[0] = y0; b[1] = y1;
+}
+
+// BN statistics of a forward tile. After its own lane reduction each kernel stages, per wave column w and channel
+// ch, the sum at red[(w * BM + ch) * 2] and the sum of squares behind it ([WC][BM][2]); stats_fold then publishes
+// the staging (barrier), and thread ch < BM adds the WC partials in wave order into the fp64 slots.
+template <int WC, int BM>
+__device__ __forceinline__ void stats_fold(const float* red, int64_t* stats, int C, int c0) {
+  __syncthreads();
+  if ((int)threadIdx.x < BM) {
+    float s = 0.f, q = 0.f;
+#pragma unroll
+    for (int w = 0; w < WC; ++w) {
+      s += red[(w * BM + threadIdx.x) * 2 + 0];
+      q += red[(w * BM + threadIdx.x) * 2 + 1];
+    }
+    stat_add(stats, C, c0 + threadIdx.x, s, q);
+  }
+}
 
 // 16-byte LDS-DMA from a per-lane global address (global_load_lds_dwordx4).
 __device__ __forceinline__ void glds16(const void* g, char* lds_wave_base) {

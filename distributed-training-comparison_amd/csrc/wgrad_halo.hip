@@ -45,7 +45,7 @@ struct HaloParams {
   int xcd;         // 1: XCD-grouped decode of the workgroup id (wg_coords)
   u64* ts;
   // halo row pitch (stride 1: W + 2) and output dims (stride 1: H, W); stride 2 (ST = 2): the x halo is
-  // column-split as in conv_halo.hip (padded column 2j at j, 2j + 1 at hwh + j), so the 64 output pixels
+  // column-split (halo_box_col, tile_common.h: padded column 2j at j, 2j + 1 at hwh + j), so the 64 output pixels
   // of a step read consecutive halo rows for every tap and the tr-read swizzle stays conflict-free
   int pitch, hwh, ho, wo;
   // SC (stride 2): the block's 1x1 stride-2 projection shortcut's weight gradient in the same launch --
@@ -86,8 +86,7 @@ __device__ __forceinline__ void wg_coords(const HaloParams& p, int& tile, int& s
   }
   const unsigned T = gridDim.x * gridDim.y * gridDim.z;
   const unsigned L = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-  const unsigned r = L & 7, q = T >> 3, rem = T & 7;
-  const unsigned Lp = r * q + min(r, rem) + (L >> 3);
+  const unsigned Lp = xcd_grouped_id(L, T);
   tile = (int)(Lp % gridDim.x);
   const unsigned g = Lp / gridDim.x;
   split = (int)(g % gridDim.y);
@@ -153,7 +152,7 @@ __global__ void __launch_bounds__(512) wgrad_halo_kernel(const HaloParams p) {
       // columns stored column-split (box column 2j at halo column j, 2j + 1 at hwh + j; pitch p.pitch)
       const int hr = (int)fdiv((uint32_t)hrow, p.fd_seg2), hc = hrow - hr * (int)p.fd_seg2.d;
       const int src_chunk = (lane & 7) ^ trswz(hrow);
-      const int lc = ST == 1 ? hc : (hc < p.hwh ? 2 * hc : (hc < 2 * p.hwh - 1 ? 2 * (hc - p.hwh) + 1 : -1000000));
+      const int lc = halo_box_col<ST>(hc, p.hwh);
       hcol[j] = hrow < p.nh && lc >= 0;
       hrow_in[j] = hr - 1;
       hcc[j] = lc - 1;
@@ -165,7 +164,7 @@ __global__ void __launch_bounds__(512) wgrad_halo_kernel(const HaloParams p) {
     const int hr = rem / W2, wc = rem - hr * W2;
     const int src_chunk = (lane & 7) ^ trswz(hrow);
     // input column of this halo column (stride 2: column-split layout), -1 = padding / out of range
-    const int col = ST == 1 ? wc - 1 : (wc < p.hwh ? 2 * wc - 1 : (wc < 2 * p.hwh ? 2 * (wc - p.hwh) : -1));
+    const int col = halo_box_col<ST>(wc, p.hwh) - 1;
     hcol[j] = hrow < p.nh && col >= 0 && col < p.W;
     hrow_in[j] = hr - 1;  // input row relative to the step's first input row (ST x its first output row)
     hrel[j] = (((ii * p.H + hr - 1) * p.W + col) * p.C + c0 + src_chunk * 8) * 2;
@@ -174,7 +173,7 @@ __global__ void __launch_bounds__(512) wgrad_halo_kernel(const HaloParams p) {
   const int trow = wave * 8 + (lane >> 3);
   const int dcol = k0 + (((lane & 7) ^ trswz(trow)) * 8);
   // GEN: this lane's dy row of the step (pixel trow = (row, column) of the rs x seg segment; padded -> zero)
-  uint32_t drel = 0x80000000u;
+  uint32_t drel = DMA_OOB;
   if constexpr (GEN) {  // (output grid: wo columns; stride 1 wo = W)
     const int tr = (int)fdiv((uint32_t)trow, p.fd_seg), tc = trow - tr * p.seg;
     if (trow < p.rs * p.seg) drel = (uint32_t)(((tr * p.wo + tc) * p.K + dcol) * 2);
@@ -182,9 +181,8 @@ __global__ void __launch_bounds__(512) wgrad_halo_kernel(const HaloParams p) {
 
   const bool trim = p.trim && (NR - 1) * 64 + wave * 8 >= p.nh;  // (wave-uniform)
   auto stage_gen = [&](char* sb, int step) {  // GEN: per-step 64-bit bases, zero-fill out of the image
-    const int img = (int)fdiv((uint32_t)step, p.fd_spimg), r = step - img * p.spimg;
-    const int yb = (int)fdiv((uint32_t)r, p.fd_spr), qs = r - yb * (int)p.fd_spr.d;
-    const int y0 = yb * p.rs, q0 = qs * p.seg;  // first OUTPUT row / column of the step
+    int img, y0, q0;  // image, first OUTPUT row / column of the step
+    seg_tile_origin(step, p.spimg, p.fd_spimg, (int)p.fd_spr.d, p.fd_spr, p.rs, p.seg, img, y0, q0);
     const int iy0 = ST * y0, iq0 = ST * q0;       // ... and the input pixel of its (0, 0) tap centre
     const u16* xb = px + ((int64_t)(img * p.H + iy0 - 1) * p.W + (iq0 - 1)) * p.C;  // the halo box corner
     const int64_t dro = ((int64_t)(img * p.ho + y0) * p.wo + q0) * p.K;
@@ -192,7 +190,7 @@ __global__ void __launch_bounds__(512) wgrad_halo_kernel(const HaloParams p) {
     for (int j = 0; j < NR; ++j) {
       if (j == NR - 1 && trim) break;
       const bool ok = hcol[j] && (unsigned)(iy0 + hrow_in[j]) < (unsigned)p.H && (unsigned)(iq0 + hcc[j]) < (unsigned)p.W;
-      buf_lds16(xb, 0x7ffffff0u, sb + (j * 64 + wave * 8) * 128, ok ? (uint32_t)hrel[j] : 0x80000000u);
+      buf_lds16(xb, 0x7ffffff0u, sb + (j * 64 + wave * 8) * 128, ok ? (uint32_t)hrel[j] : DMA_OOB);
     }
     buf_lds16(pdy + dro, 0x7ffffff0u, sb + SG::HALO_BYTES + wave * 1024, drel);
     if constexpr (SC) buf_lds16(p.dsc + dro, 0x7ffffff0u, sb + SG::HALO_BYTES + 8192 + wave * 1024, drel);
@@ -210,7 +208,7 @@ __global__ void __launch_bounds__(512) wgrad_halo_kernel(const HaloParams p) {
     for (int j = 0; j < NR; ++j) {
       if (j == NR - 1 && trim) break;
       const bool ok = hcol[j] && (unsigned)(p0 + hrow_in[j]) < (unsigned)p.H;
-      buf_lds16(px, p.x_bytes, sb + (j * 64 + wave * 8) * 128, ok ? (uint32_t)(base + hrel[j]) : 0x80000000u);
+      buf_lds16(px, p.x_bytes, sb + (j * 64 + wave * 8) * 128, ok ? (uint32_t)(base + hrel[j]) : DMA_OOB);
     }
     glds16(pdy + (size_t)(m0 + trow) * p.K + dcol, sb + SG::HALO_BYTES + wave * 1024);
     if constexpr (SC) glds16(p.dsc + (size_t)(m0 + trow) * p.K + dcol, sb + SG::HALO_BYTES + 8192 + wave * 1024);
@@ -232,11 +230,7 @@ __global__ void __launch_bounds__(512) wgrad_halo_kernel(const HaloParams p) {
       const int pr = rem / p.wo, q = rem - pr * p.wo;
       hm[ks][h] = ii * p.hb + pr * (ST * W2) + q;
     }
-  // halo row offset of tap t (stride 2: row r*pitch, column-split column shift)
-  auto tap_off = [&](int tap) {
-    const int ts = tap % 3;
-    return (tap / 3) * W2 + (ST == 1 ? ts : (ts & 1) * p.hwh + (ts >> 1));
-  };
+  auto tap_off = [&](int tap) { return halo_tap_shift<ST>(tap, W2, p.hwh); };
 
   const int wm = wave >> 1, wn = wave & 1;  // wave row (144 of the 576 GEMM rows) and column half (32 channels)
   constexpr int NJ = 2;  // B fragments (16 output channels each) per wave
@@ -288,8 +282,7 @@ __global__ void __launch_bounds__(512) wgrad_halo_kernel(const HaloParams p) {
     for (int h = 0; h < 2; ++h) {
       const int ra = hm[ks][h] + tap_off(4);
       const int unit = ((wm * 16) >> 2) + (lane & 3);
-      const int f = (((ra >> 1) & 1) << 2) | (((ra >> 3) & 1) << 3);
-      aoff_sc[ks][h] = (uint32_t)(ra * 128 + ((unit ^ f) << 3));
+      aoff_sc[ks][h] = (uint32_t)(ra * 128 + ((unit ^ wg_uswz(ra)) << 3));
     }
   f32x4 acc_sc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
   typedef __attribute__((address_space(3))) bf16x4_t lds_v4;
@@ -402,16 +395,12 @@ struct WgGeom {
 static bool wg_geometry(const ConvShape& s, WgGeom& g) {
   if (!conv3x3_ok(s, 1)) return false;
   const int hw = s.H * s.W;
-  if (s.W <= 64 && 64 % s.W == 0 && (hw % 64 == 0 || 64 % hw == 0)) {
+  TileSplit t;
+  if (classic_tile(s.H, s.W, 64, t)) {
     g.gen = 0;
-    if (hw % 64 == 0) {
-      g.rs = 64 / s.W;
-      g.imgs = 1;
-    } else {
-      g.rs = s.H;
-      g.imgs = 64 / hw;
-    }
-    g.hb = (g.rs + 2) * (s.W + 2);
+    g.rs = t.rows;
+    g.imgs = t.imgs;
+    g.hb = halo_box_s1(g.rs, s.W);
     g.nh = g.imgs * g.hb;
     g.nsteps = (int64_t)s.N * hw / 64;
     // whole 64-pixel steps only (multi-image steps need N a multiple of the images per step)
@@ -422,11 +411,12 @@ static bool wg_geometry(const ConvShape& s, WgGeom& g) {
   g.gen = 1;
   g.seg = row_segment(s.W);
   if (g.seg == 0) return false;
-  g.rs = s.W <= 64 ? 64 / s.W : 1;
+  g.rs = s.W <= 64 ? 64 / s.W : 1;  // (not shrunk to a divisor of H: a 96-wide row runs one row of 32 per step)
   if (s.H % g.rs != 0) return false;
-  g.spr = s.W / g.seg;
-  g.spimg = (s.H / g.rs) * g.spr;
-  g.hb = g.nh = (g.rs + 2) * (g.seg + 2);
+  const SegTile sg = seg_tile(s.H, s.W, g.seg, g.rs);
+  g.spr = sg.spr;
+  g.spimg = sg.tpi;
+  g.hb = g.nh = halo_box_s1(g.rs, g.seg);
   g.nsteps = (int64_t)s.N * g.spimg;
   return g.nh <= 192 && g.rs * g.seg <= 64 && g.nsteps < (1ll << 31) &&
          (int64_t)(g.rs + 2) * s.W * std::max(s.C, s.K) * 2 < (1ll << 31);
@@ -523,23 +513,17 @@ int conv_wgrad_halo(const ConvShape& s, int nprob, const u16* const* x, const u1
 
 // ---------------------------------------------------------------- stride 2 (+ shortcut)
 // conv1 of a projection block (3x3, stride 2, pad 1) and, optionally, its 1x1 stride-2 shortcut: one
-// halo launch over the OUTPUT pixels, the x halo column-split (conv_halo.hip's s2 layout, row pitch s2_pitch);
+// halo launch over the OUTPUT pixels, the x halo column-split (tile_common.h: halo_box_col, row pitch s2_pitch);
 // 9 taps + the shortcut from one x halo per step instead of one im2col gather per tap.
 static bool halo_geometry_s2(const ConvShape& s, int& rs, int& imgs, int& pitch, int& hb, int& nh) {
   if (!conv3x3_ok(s, 2) || s.H % 2 || s.W % 2) return false;
   const int ho = s.H / 2, wo = s.W / 2, hw = ho * wo;
-  if (wo > 64 || 64 % wo != 0) return false;
-  if (hw % 64 == 0) {
-    rs = 64 / wo;
-    imgs = 1;
-  } else if (64 % hw == 0) {
-    rs = ho;
-    imgs = 64 / hw;
-  } else {
-    return false;
-  }
+  TileSplit t;
+  if (!classic_tile(ho, wo, 64, t)) return false;
+  rs = t.rows;
+  imgs = t.imgs;
   pitch = s2_pitch(wo);
-  hb = (2 * rs + 1) * pitch;
+  hb = halo_box_s2(rs, wo);
   nh = imgs * hb;
   return nh <= 384 && ((int64_t)s.N * hw) % 64 == 0 && (uint64_t)s.N * s.H * s.W * s.C * 2 < (1ull << 31) &&
          (uint64_t)s.N * hw * s.K * 2 < (1ull << 31);
@@ -557,12 +541,12 @@ static bool wg_geometry_s2_gen(const ConvShape& s, WgGeomS2& g) {
   const int ho = s.H / 2, wo = s.W / 2;
   g.seg = row_segment(wo);
   if (g.seg == 0) return false;
-  g.rs = 64 / g.seg;
-  while (g.rs > 1 && ho % g.rs != 0) --g.rs;
+  g.rs = rows_dividing(ho, 64 / g.seg);
   g.pitch = s2_pitch(g.seg);
-  g.nh = (2 * g.rs + 1) * g.pitch;
-  g.spr = wo / g.seg;
-  g.spimg = (ho / g.rs) * g.spr;
+  g.nh = halo_box_s2(g.rs, g.seg);
+  const SegTile sg = seg_tile(ho, wo, g.seg, g.rs);
+  g.spr = sg.spr;
+  g.spimg = sg.tpi;
   g.nsteps = (int64_t)s.N * g.spimg;
   return g.nh <= 384 && 2 * g.rs * g.seg >= 64 && g.nsteps < (1ll << 31) &&
          (int64_t)(2 * g.rs + 2) * s.W * std::max(s.C, s.K) * 2 < (1ll << 31);

@@ -3,6 +3,7 @@
 
     python tools/conv_digest.py [--out FILE]           on the GPU: one line per (entry point, shape, option set)
     python tools/conv_digest.py --sizes [--out FILE]   no GPU needed: the workspace-size queries over the same grid
+    python tools/conv_digest.py --routes [--out FILE]  no GPU needed: the router's answers (below)
     DTC_LIB=/path/to/other/libdtc_amd.so python tools/conv_digest.py ...    the other build; then cmp the files
 
 A GPU line holds the dtc:: kernel names in launch order (tools/step_digest.py's kernels_of; one profiler session per
@@ -16,7 +17,10 @@ the defaults; that test's S1_FORCED on the stride-1 3x3 shapes and S2_FORCED on 
 32x32 and odd groups; the routing options (OTHER below) on the 32x32 and split-K groups.
 --sizes prints dtc_conv2d_workspace_size (three passes), dtc_conv2d_wgrad_sc_workspace_size,
 dtc_conv2d_wgrad_batch_workspace_size (1..4) for every shape (also at batch 32 / 256 on 32x32, batch 8 on 224x224,
-and the descriptors the ABI rejects) under EVERY option set, and dtc_rn18_workspace_bytes of four networks."""
+and the descriptors the ABI rejects) under EVERY option set, and dtc_rn18_workspace_bytes of four networks.
+--routes prints one line per dtc_conv2d_route_query answer (workspace unlimited) over the whole GRID of
+tests/test_conv_route.py, under every option set of that test, for every (pass, flags, nprob) of its _requests:
+kernel, tile, splits, halo_cfg, halo_gen, sc_ok, refused, slab_wanted and slab_used."""
 import argparse
 import ctypes as C
 import hashlib
@@ -102,6 +106,28 @@ def sizes(emit):
                 dtc._native.call("dtc_rn18_create", C.byref(net), b, h, w, 100, 25.0)
                 emit(f"{oid(o)} | rn18 {(b, h, w)} | workspace={lib.dtc_rn18_workspace_bytes(net)}")
                 lib.dtc_rn18_destroy(net)
+
+
+# ---------------------------------------------------------------------------------------------- routes (CPU)
+def routes(emit):
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("test_conv_route", os.path.join(ROOT, "tests", "test_conv_route.py"))
+    t = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(t)
+    N = dtc._native
+    q, r, unlimited = lib.dtc_conv2d_route_query, N.ConvRoute(), C.c_size_t(-1).value >> 1
+    for o in t.OPTION_SETS:
+        with Options(o):
+            for shape in t.GRID:
+                d = N.ConvDesc(*shape)
+                for mode, flags, nprob in t._requests(shape):
+                    if q(d, mode, flags, nprob, t.WS, unlimited, C.byref(r)) != 0:
+                        emit(f"{oid(o)} | {shape} | {mode} {flags} {nprob} | error: {N.last_error()}")
+                        continue
+                    emit(f"{oid(o)} | {shape} | {mode} {flags} {nprob} | {N.CONV_KERNELS[r.kernel]} {r.gemm_bm}x{r.gemm_bn} "
+                         f"splits={r.splits} halo_cfg={r.halo_cfg} halo_gen={r.halo_gen} sc_ok={r.sc_ok} "
+                         f"refused={r.refused} slab_wanted={r.slab_wanted} slab_used={r.slab_used}")
 
 
 # ---------------------------------------------------------------------------------------------- launches (GPU)
@@ -229,17 +255,19 @@ def run_gpu(emit):
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--sizes", action="store_true")
+    ap.add_argument("--routes", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     f = open(a.out, "w") if a.out else None
 
     def emit(line):
-        print(line, flush=True)
+        print(line, flush=not a.routes)  # (--routes prints over a million lines)
         if f:
             f.write(line + "\n")
-            f.flush()
+            if not a.routes:
+                f.flush()
 
-    (sizes if a.sizes else run_gpu)(emit)
+    (sizes if a.sizes else routes if a.routes else run_gpu)(emit)
 
 
 if __name__ == "__main__":
