@@ -173,7 +173,7 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(const T* __restrict__ x, 
     }
     if constexpr (MODE != APPLY_PLAIN) {
 #pragma unroll
-      for (int k = 0; k < 8; ++k) o[k] = fmaxf(o[k], 0.f);
+      for (int k = 0; k < 8; ++k) o[k] = relu_nan(o[k]);
     }
     E::st(y + v * 8, E::pack(o));
   }
@@ -280,7 +280,7 @@ __global__ void __launch_bounds__(256) bn_fin_apply_kernel(const T* __restrict__
         // torch rounds each BN output to bf16 before the residual add (autocast)
         if constexpr (MODE == APPLY_ADD_RELU) v[k] = E::round(v[k]) + r[k];
         if constexpr (MODE == APPLY_DUAL_RELU) v[k] = E::round(v[k]) + E::round(r[k] * sc2[k] + sh2[k]);
-        v[k] = fmaxf(v[k], 0.f);
+        v[k] = relu_nan(v[k]);
       }
       const typename E::V pk = E::pack(v);
       E::st(y + o, pk);
@@ -815,7 +815,9 @@ __global__ void __launch_bounds__(256) bn_bwd_finalize_kernel(
   if (dgamma) dgamma[c] = (float)(sx * gscale);
   if (dbeta) dbeta[c] = (float)(sd * gscale);
   const double is = invstd[c];
-  const double A = (double)gamma[c] * is;
+  // a flagged accumulator (sd is NaN only then: stat_total) makes EVERY coefficient NaN, also the one that does
+  // not depend on the sums
+  const double A = sd != sd ? sd : (double)gamma[c] * is;
   const double B = -A * is * sx / count;
   const double Cc = -A * sd / count - B * (double)mean[c];
   coef[c] = (float)A;

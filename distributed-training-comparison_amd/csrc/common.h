@@ -78,6 +78,10 @@ __device__ __forceinline__ uint32_t pack_bf2(float lo, float hi) {
   return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2_t{lo, hi}, bf16x2_t));
 }
 __device__ __forceinline__ float round_bf(float f) { return bf2f(f2bf(f)); }
+// ReLU as torch.relu computes it: a NaN stays a NaN (fmaxf(v, 0.f) is IEEE maxNum, v_max_f32, and returns 0
+// for a NaN -- a flagged BN's NaN coefficients would then leave finite activations behind). Compare + select;
+// -0 becomes +0 as before.
+__device__ __forceinline__ float relu_nan(float v) { return v <= 0.f ? 0.f : v; }
 
 // unpack 8 bf16 held in a uint4 into floats
 __device__ __forceinline__ void unpack8(const uint4& v, float* f) {

@@ -196,7 +196,8 @@ __device__ __forceinline__ void frag_pair_unpack(uint4 v, uint32_t (&a)[2], uint
 
 // BN statistics of a forward tile. After its own lane reduction each kernel stages, per wave column w and channel
 // ch, the sum at red[(w * BM + ch) * 2] and the sum of squares behind it ([WC][BM][2]); stats_fold then publishes
-// the staging (barrier), and thread ch < BM adds the WC partials in wave order into the fp64 slots.
+// the staging (barrier), and thread ch < BM adds the WC partials in wave order (fp32) and
+// adds that one partial into the fixed-point slots (common.h: stat_add; exact, flagged if out of range).
 template <int WC, int BM>
 __device__ __forceinline__ void stats_fold(const float* red, int64_t* stats, int C, int c0) {
   __syncthreads();

@@ -154,7 +154,14 @@ int dtc_conv2d_wgrad_batch(const dtc_conv_desc* d, int n, const uint16_t* const*
  * residual add of BasicBlock.forward (net.py:41-44) and ResNet.forward (net.py:108) fused.
  * x is NHWC bf16 with m = n*h*w pixels and c channels (c % 8 == 0). */
 /* Size of one statistics accumulator for c channels, in int64 words (a header word holding the
- * non-finite flag, then 8 slots x 2 statistics x (hi, lo) x c). Zero it before its first producer. */
+ * non-finite flag, then 8 slots x 2 statistics x (hi, lo) x c). Zero it before its first producer.
+ * Range: a producer's fp32 partial loses its bits below 2^-52 (floor) and must be finite and below 2^40 in
+ * magnitude; a partial that is NaN, infinite or FINITE AT OR ABOVE 2^40 (one conv output of 2^20 does that to
+ * the sum of squares) is not added and sets the flag instead. A flagged BN yields NaN in every channel: totals,
+ * mean / invstd, scale / shift, backward coefficients, dgamma / dbeta and every output element (the fused ReLU
+ * keeps NaN). Under AMP the GradScaler skips such a step; in fp32 mode, where there is no GradScaler, the step
+ * is not skipped and the loss is NaN. The running statistics of a flagged BN become NaN. Totals stay below
+ * 2^55; at most 2^15 partials per slot and channel. */
 size_t dtc_bn_stat_words(int c);
 /* Host-side read of an accumulator copied to host memory: totals[0][c] = first statistic (sum x / sum dz),
  * totals[1][c] = second (sum x^2 / sum dz*xhat), exactly as the BN kernels form them (NaN if flagged).

@@ -252,3 +252,37 @@ def test_bn_stat_accumulator_host_decode(dtc):
     np.testing.assert_array_equal(tot2, tot)
     spread[0] = 1  # a non-finite partial was seen
     assert np.isnan(dtc.ops.stat_totals(torch.from_numpy(spread), c).numpy()).all()
+
+
+def test_bn_stat_accumulator_host_decode_adversarial_words(dtc):
+    """dtc_bn_stat_totals (stat_total, common.h; host code, no GPU) on words no test producer writes but the
+    format allows (tests/stat_words.py: the largest lo of one add in every slot, lo at the per-slot maximum with a
+    negative hi, hi < 0 with lo > 0, +-2^62 hi words that cancel), totals of either sign up to 2^53: every encoding
+    within 2^-52 relative of the exact (Fraction) value -- one rounding of hi to 53 bits and one of the final add,
+    2^-53 each -- every encoding of a target bit-identical to the others, and NaN in every channel once the header
+    word is 1 or 2 (2: what a two-rank SyncBatchNorm sum of flags leaves)."""
+    from fractions import Fraction
+
+    import numpy as np
+    import torch
+
+    from tests import stat_words as W
+
+    lib = dtc._native.lib
+    c = 64
+    for s, q in (W.forward_targets(c), W.backward_targets(c)):
+        seen = None
+        for name in W.ENCODINGS:
+            words = W.encoded(lib, name, s, q)
+            assert W.exact_totals(lib, words, c) == [s, q], name  # the helper writes what it claims
+            tot = dtc.ops.stat_totals(torch.from_numpy(words), c).numpy()
+            for j, target in enumerate((s, q)):
+                for ch, exact in enumerate(target):
+                    err = abs(Fraction(float(tot[j, ch])) - exact)
+                    assert err <= abs(exact) * Fraction(1, 1 << 52), (name, j, ch, float(err), float(exact))
+            if seen is not None:
+                np.testing.assert_array_equal(tot, seen, err_msg=name)
+            seen = tot
+            for flag in (1, 2):
+                words[0] = flag
+                assert np.isnan(dtc.ops.stat_totals(torch.from_numpy(words), c).numpy()).all(), (name, flag)
