@@ -52,13 +52,6 @@ __device__ __forceinline__ void fold_sums(const SlotFold& f, int64_t* part, doub
   }
 }
 
-__device__ __forceinline__ void fa_slot_sums(const int64_t* __restrict__ st, int C, int cg, int64_t* part, double& s,
-                                             double& q) {
-  SlotFold f;
-  fold_issue(st, C, cg, f);
-  fold_sums(f, part, s, q);
-}
-
 // backward: dx = A*dz + B*x + Cc with the coefficients computed per workgroup from the slots of
 // sum(dz), sum(dz*xhat); the first pixel block writes dgamma / dbeta (x gscale).
 __device__ __forceinline__ void fold_issue_bwd(const BnBwdArgs& A, int C, int cg, SlotFold& f) {
@@ -89,13 +82,6 @@ __device__ __forceinline__ void fa_bwd_coef_from(const BnBwdArgs& A, const SlotF
     }
   }
   lds_barrier();
-}
-
-__device__ __forceinline__ void fa_bwd_coef(const BnBwdArgs& A, int C, int cg, int64_t* part, float* ca, float* cb,
-                                            float* cc) {
-  SlotFold f;
-  fold_issue_bwd(A, C, cg, f);
-  fa_bwd_coef_from(A, f, C, cg, part, ca, cb, cc);
 }
 
 // forward: scale / shift from the slots of sum(x), sum(x^2); the first pixel block writes the saved
@@ -150,12 +136,6 @@ __device__ __forceinline__ void bn_eval_coef_channel(int c, const float* __restr
   const float a = gamma[c] * is;
   scale[c] = a;
   shift[c] = beta[c] - rm[c] * a;
-}
-
-__device__ __forceinline__ void fa_fwd_coef(const BnFwdArgs& A, int C, int cg, int64_t* part, float* sc, float* sh) {
-  SlotFold f;
-  fold_issue_fwd(A, C, cg, f);
-  fa_fwd_coef_from(A, f, C, cg, part, sc, sh);
 }
 
 }  // namespace dtc

@@ -7,8 +7,12 @@ A kernel's digest is the SHA-256 of its disassembly with the instruction encodin
 addresses), so equal digests mean equal bytes. Moving host code inside a translation unit can move a device global
 such as a zero page relative to the kernels that address it pc-relatively; such a kernel differs in the literal of
 the s_add_u32 / s_addc_u32 that follows s_getpc_b64 and in nothing else. The comparison accepts exactly that: it
-diffs the disassembly without encodings and reports every other changed line as a difference."""
+diffs the disassembly without encodings and reports every other changed line as a difference. For each kernel that
+is not byte-identical it also says whether the multiset of mnemonics is equal (a different schedule or register
+assignment of the same instructions), ignoring the _e32 / _e64 encoding suffix, s_nop and the padding past the last
+s_endpgm, and lists the mnemonics whose counts differ. The exit status does not depend on that."""
 import argparse
+import collections
 import difflib
 import hashlib
 import os
@@ -53,6 +57,16 @@ def disassembly(lib, raw, sizes=None):
     return out
 
 
+def mnemonics(lines):
+    """Multiset of a kernel's mnemonics, without the _e32 / _e64 encoding suffix and without s_nop."""
+    names = [re.sub(r"_e(32|64)$", "", l.split()[0]) for l in lines]
+    while names and names[-1] != "s_endpgm":  # padding past the end disassembles as instructions
+        names.pop()
+    c = collections.Counter(names)
+    del c["s_nop"]
+    return c
+
+
 def digests(lib):
     res = kernel_resources(lib)
     sizes = {}
@@ -86,16 +100,22 @@ def main():
     diff = sorted(k for k in new if k in old and new[k] != old[k])
     if diff:
         dn, do = disassembly(a.lib, raw=False), disassembly(a.against, raw=False)
-        print("| kernel | code bytes | VGPRs | private B | changed lines | all pc-relative literals |")
-        print("|---|---|---|---|---|---|")
+        print("| kernel | code bytes | VGPRs | private B | changed lines | all pc-relative literals | mnemonics |")
+        print("|---|---|---|---|---|---|---|")
+        moved = {}
         for k in diff:
+            mo, mn = mnemonics(do[k]), mnemonics(dn[k])
+            moved[k] = [f"{m} {mo[m]} -> {mn[m]}" for m in sorted(set(mo) | set(mn)) if mo[m] != mn[m]]
             res_same = new[k][:3] == old[k][:3]
             lines = [l for l in difflib.unified_diff(do[k], dn[k], lineterm="", n=0) if l[:1] in "+-" and l[:3] not in
                      ("+++", "---")]
             ok = res_same and len(do[k]) == len(dn[k]) and all(PCREL.match(l[1:]) for l in lines)
             bad += 0 if ok else 1
             print(f"| `{k}` | {old[k][0]} -> {new[k][0]} | {old[k][1]} -> {new[k][1]} | {old[k][2]} -> {new[k][2]} | "
-                  f"{len(lines) // 2} | {'yes' if ok else 'NO'} |")
+                  f"{len(lines) // 2} | {'yes' if ok else 'NO'} | {'differ' if moved[k] else 'equal'} |")
+        for k in diff:
+            if moved[k]:
+                print(f"\n`{k}` mnemonic counts: " + "; ".join(moved[k]))
     print(f"\nresult: {'equal device code' if bad == 0 else f'{bad} DIFFERENCES'}")
     return 1 if bad else 0
 
