@@ -117,6 +117,10 @@ _SIGS = {
     "dtc_conv2d_fwd": (i32, [PConv, vp, vp, vp, vp, vp, sz, vp]),
     "dtc_conv2d_route_query": (i32, [PConv, i32, i32, i32, vp, sz, C.POINTER(ConvRoute)]),
     "dtc_conv2d_dgrad": (i32, [PConv, vp, vp, vp, vp, vp, sz, vp]),
+    "dtc_f32_split3": (i32, [vp, vp, i64, vp]),
+    "dtc_conv2d_f32_route_query": (i32, [PConv, i32, i32]),
+    "dtc_conv2d_f32_fwd": (i32, [PConv, vp, vp, vp, vp, i32, vp, sz, vp]),
+    "dtc_conv2d_f32_dgrad": (i32, [PConv, vp, vp, vp, vp, i32, vp, sz, vp]),
     "dtc_conv2d_fwd_sc": (i32, [PConv, vp, vp, vp, vp, vp, vp, vp, vp]),
     "dtc_conv2d_dgrad_sc": (i32, [PConv, vp, vp, vp, vp, vp, vp]),
     "dtc_conv2d_wgrad_sc_workspace_size": (sz, [PConv]),

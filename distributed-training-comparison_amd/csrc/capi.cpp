@@ -294,6 +294,53 @@ int dtc_conv2d_fwd(const dtc_conv_desc* d, const uint16_t* x, const uint16_t* w,
   GUARD(return conv_fwd(shape_of(d), x, w, y, stats, (float*)ws, c.slab_bytes, S(stream), nullptr, c.tick);)
 }
 
+// ---- fp32 convolutions: conv_f32 (exact) or the split-bf16 kernel (conv_f32x), chosen by conv_f32_route
+// what conv_f32 takes: C and K multiples of 16, stride 1 / 2, tensors whose pixel index fits 31 bits
+static bool desc_ok_f32(const dtc_conv_desc* d) {
+  if (!d || d->n <= 0 || d->h <= 0 || d->w <= 0 || d->c <= 0 || d->k <= 0 || d->r <= 0 || d->s <= 0) return false;
+  if (d->c % 16 != 0 || d->k % 16 != 0 || (d->stride != 1 && d->stride != 2) || d->pad < 0) return false;
+  const int64_t p = (d->h + 2 * d->pad - d->r) / d->stride + 1, q = (d->w + 2 * d->pad - d->s) / d->stride + 1;
+  return d->h + 2 * d->pad >= d->r && d->w + 2 * d->pad >= d->s && p > 0 && q > 0 &&
+         (int64_t)d->n * d->h * d->w < (1ll << 31);
+}
+
+static_assert(DTC_CONV_F32_EXACT == CONV_F32_EXACT && DTC_CONV_F32_SPLIT == CONV_F32_SPLIT, "DTC_CONV_F32_* mirror");
+
+int dtc_f32_split3(const float* src, uint16_t* planes, int64_t n, void* stream) {
+  DTC_CHECK_ARG(src && planes && n > 0, "dtc_f32_split3: bad argument");
+  GUARD(return f32_split3(src, planes, n, n, S(stream));)
+}
+
+int dtc_conv2d_f32_route_query(const dtc_conv_desc* d, int pass, int algo) {
+  DTC_CHECK_ARG(desc_ok_f32(d), "dtc_conv2d_f32_route_query: unsupported convolution descriptor");
+  DTC_CHECK_ARG((pass == CONV_FWD || pass == CONV_DGRAD) && (algo == 0 || algo == 1),
+                "dtc_conv2d_f32_route_query: pass %d algo %d name no entry point", pass, algo);
+  return conv_f32_route(shape_of(d), pass, algo != 0, true);
+}
+
+static int conv2d_f32(const char* fn, const dtc_conv_desc* d, int pass, const float* a, const void* w, float* out,
+                      const float* res, int64_t* stats, int algo, hipStream_t st) {
+  if (!(d && a && w && out)) return set_error(DTC_EINVAL, "%s: null argument", fn);
+  if (!desc_ok_f32(d)) return set_error(DTC_EINVAL, "%s: unsupported convolution descriptor", fn);
+  if (algo != 0 && algo != 1) return set_error(DTC_EINVAL, "%s: algo %d (0 exact, 1 split)", fn, algo);
+  const ConvShape s = shape_of(d);
+  if (conv_f32_route(s, pass, algo != 0, true) == CONV_F32_SPLIT)
+    return conv_f32x(s, pass, a, (const u16*)w, (int64_t)s.K * s.R * s.S * s.C, out, res, stats, st);
+  return conv_f32(s, pass, a, (const float*)w, out, res, stats, nullptr, 0, 0, 0.f, nullptr, 0, st);
+}
+
+int dtc_conv2d_f32_fwd(const dtc_conv_desc* d, const float* x, const void* w, float* y, int64_t* stats, int algo,
+                       void* ws, size_t ws_bytes, void* stream) {
+  (void)ws, (void)ws_bytes;  // neither kernel's forward splits its reduction today
+  GUARD(return conv2d_f32("dtc_conv2d_f32_fwd", d, CONV_FWD, x, w, y, nullptr, stats, algo, S(stream));)
+}
+
+int dtc_conv2d_f32_dgrad(const dtc_conv_desc* d, const float* dy, const void* w, float* dx, const float* res, int algo,
+                         void* ws, size_t ws_bytes, void* stream) {
+  (void)ws, (void)ws_bytes;
+  GUARD(return conv2d_f32("dtc_conv2d_f32_dgrad", d, CONV_DGRAD, dy, w, dx, res, nullptr, algo, S(stream));)
+}
+
 int dtc_conv2d_fwd_sc(const dtc_conv_desc* d, const uint16_t* x, const uint16_t* w, uint16_t* y, int64_t* stats,
                       const uint16_t* wsc, uint16_t* ysc, int64_t* stats_sc, void* stream) {
   DTC_CHECK_ARG(d && x && w && y && wsc && ysc, "dtc_conv2d_fwd_sc: null argument");

@@ -64,7 +64,8 @@ namespace dtc {
   X(COMM_PRIO, comm_prio, 0)            /* (communicator creation) its own stream: 0 normal, 1 most urgent */ \
   X(COMM_TAIL_INLINE, comm_tail_inline, 1) /* the last bucket's all-reduce on the compute stream (no fork / join) */ \
   X(DGRAD_S2H, dgrad_s2h, 1)            /* stride-2 3x3 dgrad (+ shortcut) as a halo sub-pixel conv: 1 K <= 256, 2 all */ \
-  X(HALO_SMALL, halo_small, 1)          /* halo FWD/DGRAD: 64x64 double-buffered tiles where they give <= 512 workgroups */
+  X(HALO_SMALL, halo_small, 1)          /* halo FWD/DGRAD: 64x64 double-buffered tiles where they give <= 512 workgroups */ \
+  X(F32_SPLIT, f32_split, 0)            /* (plan time) fp32 executor: 3x3 s1 FWD/DGRAD on the split-bf16 kernel (conv_f32x) */
 
 enum {
 #define DTC_OPT_ENUM(id, name, def) OPT_##id,
@@ -231,6 +232,21 @@ int conv_f32(const ConvShape& s, int mode, const float* a, const float* b, float
              int64_t* stats, float* dw, int dw_cols, int dw_ld, float scale, float* slab, size_t slab_bytes,
              hipStream_t st, u64* ts = nullptr);
 size_t f32_conv_workspace(const ConvShape& s, int mode);  // fp32 slab bytes the pass wants
+// Split-bf16 fp32 conv (conv_f32x.hip): 3x3 stride-1 FWD / DGRAD on the bf16 MFMA from three bf16 planes per fp32
+// operand (six plane products, fp32 accumulation): fp32-grade results. src fp32 NHWC (x / dy), wplanes three bf16
+// KRSC planes wstride elements apart (f32_split3 of the fp32 weight), out fp32 (y / dx); FWD: optional BN
+// statistics as conv_f32's; DGRAD: optional fp32 residual. conv_f32x_ok: rows of 4 / 8 / 16 / 32 pixels whose 128-
+// pixel tiles are whole rows or whole images, C and K multiples of 64, tensors below 2 GiB.
+bool conv_f32x_ok(const ConvShape& s);
+int conv_f32x(const ConvShape& s, int mode, const float* src, const u16* wplanes, int64_t wstride, float* out,
+              const float* res, int64_t* stats, hipStream_t st, u64* ts = nullptr);
+// planes[p * stride + i] = plane p of src[i], i < n: p0 = bf16(a), p1 = bf16(a - p0), p2 = bf16(a - p0 - p1)
+int f32_split3(const float* src, u16* planes, int64_t n, int64_t stride, hipStream_t st);
+// Which kernel an fp32 FWD / DGRAD runs on (conv_route.cpp): CONV_F32_SPLIT when the split is asked for (the
+// executor: option f32_split; the C ABI: algo), conv_f32x_ok holds and the weight planes exist; else CONV_F32_EXACT
+// (conv_f32). WGRAD is always exact.
+enum { CONV_F32_EXACT = 0, CONV_F32_SPLIT = 1 };
+int conv_f32_route(const ConvShape& s, int pass, bool want_split, bool planes);
 int f32_stem_im2col(const float* x, float* cols, int N, int H, int W, hipStream_t st);  // [N*H*W][32]
 int f32_stem_pack_weight(const float* w27, float* w32, int K, hipStream_t st);          // [K][27] -> [K][32]
 

@@ -65,6 +65,10 @@ struct Plan {
   size_t MA0 = 0;  // ReLU mask bits of A0
   size_t XIN = 0;  // executor-owned copy of the fp32 NCHW input (direct stem conv, bf16 mode)
   bool stem_direct = false;  // planned with option stem_direct (bf16): stem.hip instead of im2col + GEMM
+  // fp32 executor planned with option f32_split: three bf16 planes [3][wpl_n] of the flat parameters [wpl_lo,
+  // wpl_lo + wpl_n), the range of the 3x3 stride-1 conv weights conv_f32x serves (wpl_n 0: not planned)
+  size_t WPL = 0;
+  int64_t wpl_lo = 0, wpl_n = 0;
   size_t HEADWS = 0, HEADWS_bytes = 0;
   size_t DC0 = 0, SLABW = 0;  // stem conv-output gradient; split-K slab of the side-stream wgrads
   size_t TICK = 0;            // split-K arrival counters of the compute stream's convs (the only in-kernel split-K)
@@ -212,6 +216,7 @@ struct Net {
   const u16* wbf(int pidx) const { return mem.pb + params[pidx].offset; }
   float* pf(int pidx) const { return mem.p + params[pidx].offset; }
   float* gf(int pidx) const { return mem.g + params[pidx].offset; }
+  const u16* wpl(int pidx) const { return at<u16>(plan.WPL) + (params[pidx].offset - plan.wpl_lo); }  // plane 0
   unsigned* tick(int i) { return (unsigned*)(mem.ws + plan.TICK) + (size_t)i * DTC_TICKS; }
 };
 

@@ -228,6 +228,23 @@ static void plan_workspace(Net& n, float bucket_cap_mb) {
   p.SLAB = take(slab);
   p.SLABW = take(slab);
   p.TICK = take((size_t)DTC_TICKS * 4);  // zeroed at bind; every in-kernel split-K leaves its counters zero
+  // option f32_split (fp32): the bf16 weight planes of the convs the split kernel serves, rewritten by every forward
+  p.WPL = 0;
+  p.wpl_lo = p.wpl_n = 0;
+  if (n.f32 && option_get(OPT_F32_SPLIT) != 0) {
+    int64_t lo = INT64_MAX, hi = 0;
+    for (auto& b : n.blocks)
+      for (const ConvL* c : {&b.c1, &b.c2})
+        if (conv_f32x_ok(c->s)) {
+          lo = std::min(lo, n.params[c->pidx].offset);
+          hi = std::max(hi, align_up(n.params[c->pidx].offset + n.params[c->pidx].numel, 64));
+        }
+    if (hi > lo) {
+      p.wpl_lo = lo;
+      p.wpl_n = hi - lo;
+      p.WPL = take((size_t)3 * p.wpl_n * 2);
+    }
+  }
   if (n.capture) {
     auto cap = [&](const std::string& nm, int h, int w, int c) {
       p.caps.push_back({nm, take((size_t)B * h * w * c * E), (int)B, h, w, c});

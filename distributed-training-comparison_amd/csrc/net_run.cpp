@@ -212,18 +212,33 @@ static int64_t* stats_if(Net& n, const BNL& b, bool train) { return train ? n.at
 // One timed fp32 conv pass (conv_f32.hip) on the compute stream's slab (a pass's profiling kind is its conv mode;
 // flops < 0: the conv's own): y = conv(x, w) (+ BN statistics), dx = conv_transpose(dy, w) (+ res),
 // dw[k][0:cols] = gs * sum dy (x) im2col(x)
+// wpl (FWD / DGRAD of a block's conv): plane 0 of the weight's bf16 planes where they are planned (option f32_split);
+// conv_f32_route then sends the shapes conv_f32x serves to it (the same algorithmic FLOPs: the six plane products
+// are the kernel's business)
 static int f32_conv(Net& n, int mode, const ConvShape& s, const float* a, const float* b, float* out, const float* res,
-                    int64_t* stats, float* dw, int cols, float gs, hipStream_t st, double flops) {
+                    int64_t* stats, float* dw, int cols, float gs, hipStream_t st, double flops,
+                    const u16* wpl = nullptr) {
+  if (conv_f32_route(s, mode, option_get(OPT_F32_SPLIT) != 0, wpl != nullptr) == CONV_F32_SPLIT) {
+    PROF(mode, flops < 0 ? conv_flops(s) : flops, conv_f32x(s, mode, a, wpl, n.plan.wpl_n, out, res, stats, st, ts));
+    return 0;
+  }
   PROF(mode, flops < 0 ? conv_flops(s) : flops,
        conv_f32(s, mode, a, b, out, res, stats, dw, cols, cols, gs, n.at<float>(n.plan.SLAB), n.plan.slab_bytes, st, ts));
   return 0;
 }
-static int f32_fwd(Net& n, const ConvShape& s, const float* x, const float* w, float* y, int64_t* stats, hipStream_t st,
-                   double flops = -1) {
-  return f32_conv(n, CONV_FWD, s, x, w, y, nullptr, stats, nullptr, 0, 0.f, st, flops);
+// the bf16 planes of conv c's weight, or null where none are planned for it
+static const u16* f32_planes(const Net& n, const ConvL& c) {
+  const Plan& p = n.plan;
+  const int64_t off = n.params[c.pidx].offset;
+  return p.wpl_n > 0 && off >= p.wpl_lo && off + n.params[c.pidx].numel <= p.wpl_lo + p.wpl_n ? n.wpl(c.pidx) : nullptr;
 }
-static int f32_dgrad(Net& n, const ConvShape& s, const float* dy, const float* w, float* dx, const float* res, hipStream_t st) {
-  return f32_conv(n, CONV_DGRAD, s, dy, w, dx, res, nullptr, nullptr, 0, 0.f, st, -1);
+static int f32_fwd(Net& n, const ConvShape& s, const float* x, const float* w, float* y, int64_t* stats, hipStream_t st,
+                   double flops = -1, const u16* wpl = nullptr) {
+  return f32_conv(n, CONV_FWD, s, x, w, y, nullptr, stats, nullptr, 0, 0.f, st, flops, wpl);
+}
+static int f32_dgrad(Net& n, const ConvShape& s, const float* dy, const float* w, float* dx, const float* res, hipStream_t st,
+                     const u16* wpl = nullptr) {
+  return f32_conv(n, CONV_DGRAD, s, dy, w, dx, res, nullptr, nullptr, 0, 0.f, st, -1, wpl);
 }
 static int f32_wgrad(Net& n, const ConvShape& s, const float* x, const float* dy, float* dw, float gs, hipStream_t st,
                      int cols = 0, double flops = -1) {
@@ -239,6 +254,8 @@ static int forward_body_f32(Net& n, float* logits, bool train, hipStream_t st) {
   const int64_t M0 = (int64_t)n.B * n.H * n.W;
   n.prof.next = train ? 0 : ProfState::SLOTS;
   DTC_TRY(f32_stem_pack_weight(n.pf(n.stem.pidx), n.at<float>(p.WSTEM), 64, st));
+  if (p.wpl_n > 0)  // option f32_split: this step's weights as three bf16 planes (the backward reads them too)
+    DTC_TRY(f32_split3(n.mem.p + p.wpl_lo, n.at<u16>(p.WPL), p.wpl_n, p.wpl_n, st));
   if (train) DTC_TRY(zero_bytes(n.mem.ws + p.stats_lo, p.stats_hi - p.stats_lo, st));  // + the backward sums
   DTC_TRY(f32_fwd(n, f32_stem_shape(n), n.at<float>(p.X0), n.at<float>(p.WSTEM), n.at<float>(p.C0),
                   stats_if(n, n.bn0, train), st, 2.0 * M0 * 64 * 27));
@@ -246,9 +263,10 @@ static int forward_body_f32(Net& n, float* logits, bool train, hipStream_t st) {
   const float* in = n.at<float>(p.A0);
   for (auto& b : n.blocks) {
     const int64_t M = (int64_t)n.B * b.Hout * b.Wout;
-    DTC_TRY(f32_fwd(n, b.c1.s, in, n.pf(b.c1.pidx), n.at<float>(b.C1), stats_if(n, b.b1, train), st));
+    DTC_TRY(f32_fwd(n, b.c1.s, in, n.pf(b.c1.pidx), n.at<float>(b.C1), stats_if(n, b.b1, train), st, -1, f32_planes(n, b.c1)));
     DTC_TRY(bn_act(n, 1, b.b1, n.at<float>(b.C1), nullptr, nullptr, n.at<float>(b.A1), M, train, st));
-    DTC_TRY(f32_fwd(n, b.c2.s, n.at<float>(b.A1), n.pf(b.c2.pidx), n.at<float>(b.C2), stats_if(n, b.b2, train), st));
+    DTC_TRY(f32_fwd(n, b.c2.s, n.at<float>(b.A1), n.pf(b.c2.pidx), n.at<float>(b.C2), stats_if(n, b.b2, train), st, -1,
+                    f32_planes(n, b.c2)));
     if (b.proj) {
       DTC_TRY(f32_fwd(n, b.sc.s, in, n.pf(b.sc.pidx), n.at<float>(b.S), stats_if(n, b.bsc, train), st));
       DTC_TRY(bn_act(n, 3, b.b2, n.at<float>(b.C2), &b.bsc, n.at<float>(b.S), n.at<float>(b.OUT), M, train, st));
@@ -829,7 +847,7 @@ static int backward_body_f32(Net& n, const float* dlogits, float gs, const BwdCt
     DTC_TRY(cap(n, cp + ".dc2", dc2, st));
     if (b.proj) DTC_TRY(cap(n, cp + ".ds", dsc, st));
     DTC_TRY(f32_wgrad(n, b.c2.s, n.at<float>(b.A1), dc2, n.gf(b.c2.pidx), gs, st));
-    DTC_TRY(f32_dgrad(n, b.c2.s, dc2, n.pf(b.c2.pidx), G[4], nullptr, st));
+    DTC_TRY(f32_dgrad(n, b.c2.s, dc2, n.pf(b.c2.pidx), G[4], nullptr, st, f32_planes(n, b.c2)));
     DTC_TRY(cap(n, cp + ".da1", G[4], st));
     // a1 = relu(bn1(c1)): dz1 = da1 * [a1 > 0] (in place) and bn1's sums
     DTC_TRY(bn_reduce(bnb_of_f32(n, b.A1, b.C1, b.b1), G[4], G[4], M, b.Cout, st));
@@ -841,9 +859,9 @@ static int backward_body_f32(Net& n, const float* dlogits, float gs, const BwdCt
       DTC_TRY(f32_wgrad(n, b.sc.s, in, dsc, n.gf(b.sc.pidx), gs, st));
       DTC_TRY(f32_dgrad(n, b.sc.s, dsc, n.pf(b.sc.pidx), G[5], nullptr, st));
       DTC_TRY(cap(n, cp + ".dxs", G[5], st));
-      DTC_TRY(f32_dgrad(n, b.c1.s, dc1, n.pf(b.c1.pidx), G[0], G[5], st));
+      DTC_TRY(f32_dgrad(n, b.c1.s, dc1, n.pf(b.c1.pidx), G[0], G[5], st, f32_planes(n, b.c1)));
     } else {  // dx = dgrad + dz2 (the identity shortcut's gradient)
-      DTC_TRY(f32_dgrad(n, b.c1.s, dc1, n.pf(b.c1.pidx), G[0], dz2, st));
+      DTC_TRY(f32_dgrad(n, b.c1.s, dc1, n.pf(b.c1.pidx), G[0], dz2, st, f32_planes(n, b.c1)));
     }
     DTC_TRY(cap(n, cp + ".dx", G[0], st));
     DTC_TRY(maybe_bucket(n, bi, cx, st));

@@ -105,6 +105,67 @@ def conv2d_dgrad(dy, w, in_hw, stride, pad, res=None, out=None, workspace=None):
     return dx
 
 
+CONV_F32_KERNELS = ("exact", "split")  # DTC_CONV_F32_*: conv_f32 (f32-input MFMA), conv_f32x (split bf16)
+
+
+def conv2d_f32_route(desc, mode, algo):
+    """dtc_conv2d_f32_route_query: which fp32 kernel ("exact" / "split") the FWD (0) / DGRAD (1) entry point runs for
+    `desc` with algo 0 (exact) / 1 (split where its predicate accepts the shape). Host code: nothing is launched."""
+    rc = lib.dtc_conv2d_f32_route_query(desc, mode, algo)
+    if rc < 0:
+        call("dtc_conv2d_f32_route_query", desc, mode, algo)  # raises with the library's message
+    return CONV_F32_KERNELS[rc]
+
+
+def f32_split3(src, out=None):
+    """fp32 tensor -> its three bf16 planes [3, *src.shape]: p0 = bf16(a), p1 = bf16(a - p0), p2 = bf16(a - p0 - p1)
+    (dtc_f32_split3; (p2 + p1) + p0 == a in fp32)."""
+    require_cuda(src)
+    if src.dtype != torch.float32 or not src.is_contiguous():
+        raise ValueError("f32_split3: src must be a contiguous float32 tensor")
+    planes = _out(out, (3, *src.shape), torch.bfloat16, src.device, "f32_split3")
+    call("dtc_f32_split3", ptr(src), ptr(planes), src.numel(), stream_ptr())
+    return planes
+
+
+def _f32_weight(d, mode, w, algo):
+    """The weight operand the fp32 entry point takes for (desc, mode, algo): the fp32 filter for the exact kernel, its
+    planes for the split one (split here from an fp32 `w`; a [3, K, R, S, C] bf16 `w` is taken as the planes)."""
+    split = conv2d_f32_route(d, mode, algo) == "split"
+    if w.dtype == torch.bfloat16:
+        if not split:
+            raise ValueError("conv2d_f32: weight planes given, but the exact kernel runs for this shape / algo")
+        return w
+    return f32_split3(w) if split else w
+
+
+def conv2d_f32(x, w, stride, pad, algo=0, stats=None, out=None):
+    """x [N,H,W,C] fp32, w [K,R,S,C] fp32 (or its planes [3,K,R,S,C] bf16 where the split kernel runs) -> y [N,P,Q,K]
+    fp32 (nn.Conv2d forward without autocast). algo 0: conv_f32; 1: the split-bf16 kernel where it serves the shape."""
+    require_cuda(x, w)
+    N, H, W, Cc = x.shape
+    K, R, S, _ = w.shape[-4:]
+    d = conv_desc(N, H, W, Cc, K, R, S, stride, pad)
+    P, Q = conv_out_hw(H, W, R, S, stride, pad)
+    wk = _f32_weight(d, 0, w, algo)
+    y = _out(out, (N, P, Q, K), torch.float32, x.device, "conv2d_f32")
+    call("dtc_conv2d_f32_fwd", d, ptr(x), ptr(wk), ptr(y), ptr(stats), algo, None, 0, stream_ptr())
+    return y
+
+
+def conv2d_dgrad_f32(dy, w, in_hw, stride, pad, algo=0, res=None, out=None):
+    """dy [N,P,Q,K] fp32, w as conv2d_f32's -> dx [N,H,W,C] fp32 (+ res)."""
+    require_cuda(dy, w)
+    N = dy.shape[0]
+    K, R, S, Cc = w.shape[-4:]
+    H, W = in_hw
+    d = conv_desc(N, H, W, Cc, K, R, S, stride, pad)
+    wk = _f32_weight(d, 1, w, algo)
+    dx = _out(out, (N, H, W, Cc), torch.float32, dy.device, "conv2d_dgrad_f32")
+    call("dtc_conv2d_f32_dgrad", d, ptr(dy), ptr(wk), ptr(dx), ptr(res), algo, None, 0, stream_ptr())
+    return dx
+
+
 def conv2d_dgrad_bn(dy, w, in_hw, stride, pad, ymask, x1, mean1, invstd1, x2=None, mean2=None, invstd2=None,
                     res=None, out=None):
     """conv2d_dgrad fused with bn_bwd_reduce (dtc_conv2d_dgrad_bn): returns (dz, acc1, acc2) where

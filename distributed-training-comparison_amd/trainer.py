@@ -21,7 +21,7 @@ from typing import Tuple
 import torch
 import torch.distributed as dist
 
-from . import checkpoint
+from . import _native, checkpoint
 from . import data as D
 from .amp import GradScaler, autocast
 from .ema import ModelEma
@@ -39,6 +39,10 @@ def load_config(argv=None, mode: str = "ddp"):
     p.add_argument("--workers", type=int, default=4)
     p.add_argument("--eval-step", type=int, default=300)
     p.add_argument("--amp", action="store_true", default=False, help="PyTorch(>=1.6.x) AMP")
+    # not in the reference: which kernel the fp32 (no --amp) 3x3 stride-1 convs run on
+    p.add_argument("--fp32-conv", choices=("exact", "split"), default="exact",
+                   help="without --amp: exact = the f32-input MFMA convs; split = forward and data-gradient convs on "
+                        "the bf16 MFMA from three bf16 planes per fp32 operand (fp32-grade results, option f32_split)")
     p.add_argument("--contain-test", action="store_true", default=False)
     if mode == "ddp":
         p.add_argument("--world-size", type=int, default=1, help="Total number of processes to run")
@@ -140,6 +144,8 @@ def load_config(argv=None, mode: str = "ddp"):
     h = p.parse_args(argv)
     if not 0.0 <= h.label_smoothing <= 1.0:
         p.error("--label-smoothing must be in [0, 1]")
+    if h.fp32_conv != "exact" and h.amp:
+        p.error("--fp32-conv applies to fp32 training: not with --amp")
     if h.mixup_alpha < 0 or h.cutmix_alpha < 0 or not 0.0 <= h.mix_prob <= 1.0:
         p.error("--mixup-alpha / --cutmix-alpha must be >= 0 and --mix-prob in [0, 1]")
     if mode == "ddp" and h.powersgd_start_iter < 2:
@@ -677,6 +683,8 @@ class Trainer:
 def _run(hparams, rank, ngpus, distributed, data_parallel=False):
     D.fix_seed(hparams.seed)
     scaler = GradScaler() if hparams.amp else None
+    # plan-time option: set before the model's executors exist
+    _native.call("dtc_set_option", b"f32_split", 1 if getattr(hparams, "fp32_conv", "exact") == "split" else 0)
     model = ResNet18()
     if getattr(hparams, "sync_bn", False):
         model = SyncBatchNorm.convert_sync_batchnorm(model)

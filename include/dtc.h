@@ -43,7 +43,8 @@ int dtc_install_crash_handler(void);
  * default 4 = auto: the executor captures on first use and replays; any option change invalidates
  * captured graphs), "splitk_ink" (split-K slabs summed in-kernel by the last workgroup of each tile,
  * default 1), "dgrad_s2h" (stride-2 data gradient as a halo sub-pixel conv, default 1), "stem_direct"
- * (plan time: direct 3x3 stem conv, default 1; 0 = im2col + GEMM). */
+ * (plan time: direct 3x3 stem conv, default 1; 0 = im2col + GEMM), "f32_split" (plan time: the fp32 executor's 3x3
+ * stride-1 forward and data-gradient convs on the split-bf16 kernel, default 0). */
 int dtc_set_option(const char* name, int value);
 int dtc_get_option(const char* name);
 
@@ -148,6 +149,28 @@ int dtc_conv2d_wgrad_sc(const dtc_conv_desc* d, const uint16_t* x, const uint16_
 size_t dtc_conv2d_wgrad_batch_workspace_size(const dtc_conv_desc* d, int n);
 int dtc_conv2d_wgrad_batch(const dtc_conv_desc* d, int n, const uint16_t* const* x, const uint16_t* const* dy,
                            float* const* dw, float scale, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------ fp32 convolution (the reference without --amp)
+ * nn.Conv2d(bias=False) forward / input gradient on fp32 NHWC activations and KRSC filters, fp32 out, fp32-grade
+ * results (c % 16 == 0, k % 16 == 0, stride 1 / 2). Two kernels, chosen by `algo`:
+ *   DTC_CONV_F32_EXACT (0)  the f32-input MFMA implicit GEMM: w is the fp32 filter [k][r][s][c];
+ *   DTC_CONV_F32_SPLIT (1)  3x3 / stride 1 / pad 1 with rows of 4 / 8 / 16 / 32 pixels and c, k multiples of 64: the
+ *     bf16 MFMA on three bf16 planes per fp32 operand, six plane products, fp32 accumulation (element-wise error
+ *     below 2^-22 of sum |x||w|); w is the filter's three planes [3][k*r*s*c] as dtc_f32_split3 writes them. For any
+ *     other descriptor algo 1 runs the exact kernel, and w is the fp32 filter.
+ * dtc_conv2d_f32_route_query (host only) returns which of the two a descriptor, pass (DTC_CONV_FWD / DTC_CONV_DGRAD)
+ * and algo run -- and so which form of w the call takes -- or a negative value for a descriptor or pass neither
+ * serves. stats (FWD, optional): the BN statistics of the fp32 output, as dtc_conv2d_fwd's. res (DGRAD, optional):
+ * an fp32 tensor of dx's shape added to it. ws may be NULL (neither kernel splits its reduction).
+ * dtc_f32_split3: planes[p * n + i], p < 3 = bf16(a), bf16(a - p0), bf16(a - p0 - p1) of a = src[i], round to nearest
+ * even; (p2 + p1) + p0 == a bit for bit for every finite a whose last bit is at or above 2^-133; NaN stays NaN. */
+enum { DTC_CONV_F32_EXACT = 0, DTC_CONV_F32_SPLIT = 1 };
+int dtc_f32_split3(const float* src, uint16_t* planes, int64_t n, void* stream);
+int dtc_conv2d_f32_route_query(const dtc_conv_desc* d, int pass, int algo);
+int dtc_conv2d_f32_fwd(const dtc_conv_desc* d, const float* x, const void* w, float* y, int64_t* stats, int algo,
+                       void* ws, size_t ws_bytes, void* stream);
+int dtc_conv2d_f32_dgrad(const dtc_conv_desc* d, const float* dy, const void* w, float* dx, const float* res,
+                         int algo, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------ batch norm (training)
  * Replaces nn.BatchNorm2d train-mode forward/backward (net.py:21,25,37,92) with the F.relu and

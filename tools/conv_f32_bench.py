@@ -1,0 +1,79 @@
+"""Time the fp32 3x3 stride-1 convs of ResNet-18 (forward and data gradient) on the exact kernel (conv_f32, algo 0)
+and on the split-bf16 kernel (conv_f32x, algo 1), interleaved in one process.
+
+As tools/conv_bench.py: each (layer, pass, algo) is captured ITERS times into a graph on preallocated buffers (raw
+C-ABI calls), so a replay measures device time only; ROUNDS interleaved rounds per case. Prints the median us, the
+spread over the rounds (min .. max), TF/s of the algorithmic 2 N H W C 9 K FLOPs and the exact / split ratio."""
+import argparse
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+
+import dtc_import  # noqa: E402
+
+LAYERS = [("l1", 32, 64), ("l2", 16, 128), ("l3", 8, 256), ("l4", 4, 512)]  # (name, H = W, C = K)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cases", default="l1:256,l2:256,l3:256,l4:256,l3:32,l4:32", help="layer:batch, ...")
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=5)
+    args = ap.parse_args()
+    dtc = dtc_import.load()
+    ops, nat = dtc.ops, dtc._native
+    dev = torch.device("cuda:0")
+    geo = {n: (h, c) for n, h, c in LAYERS}
+    print(f"{'case':10s} {'pass':6s} {'exact us (min..max)':>26s} {'TF/s':>6s} {'split us (min..max)':>26s} {'TF/s':>6s} "
+          f"{'exact/split':>11s}")
+    for case in args.cases.split(","):
+        name, B = case.split(":")[0], int(case.split(":")[1])
+        H, C = geo[name]
+        x = torch.randn(B, H, H, C, device=dev)
+        w = torch.randn(C, 3, 3, C, device=dev) * 0.05
+        wpl = ops.f32_split3(w)
+        out = torch.empty(B, H, H, C, device=dev)
+        stats = ops.new_stats(C, dev)
+        d = ops.conv_desc(B, H, H, C, C, 3, 3, 1, 1)
+        flops = 2.0 * B * H * H * C * 9 * C
+        P_ = nat.ptr
+        for pname, mode in (("fwd", 0), ("dgrad", 1)):
+            assert ops.conv2d_f32_route(d, mode, 1) == "split", case
+            fns = {}
+            for algo, wt in ((0, w), (1, wpl)):
+                if mode == 0:
+                    fns[algo] = lambda algo=algo, wt=wt: nat.call("dtc_conv2d_f32_fwd", d, P_(x), P_(wt), P_(out),
+                                                                  P_(stats), algo, None, 0, nat.stream_ptr())
+                else:
+                    fns[algo] = lambda algo=algo, wt=wt: nat.call("dtc_conv2d_f32_dgrad", d, P_(x), P_(wt), P_(out),
+                                                                  None, algo, None, 0, nat.stream_ptr())
+            us = {0: [], 1: []}
+            for _ in range(args.rounds):
+                for algo, fn in fns.items():
+                    fn()
+                    torch.cuda.synchronize()
+                    g, s = torch.cuda.CUDAGraph(), torch.cuda.Stream()
+                    with torch.cuda.stream(s):
+                        with torch.cuda.graph(g, stream=s):
+                            for _ in range(args.iters):
+                                fn()
+                    g.replay()
+                    torch.cuda.synchronize()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    g.replay()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    us[algo].append(e0.elapsed_time(e1) * 1e3 / args.iters)
+                    del g
+            m = {a: statistics.median(v) for a, v in us.items()}
+            cell = {a: f"{m[a]:8.1f} ({min(us[a]):.1f}..{max(us[a]):.1f})" for a in us}
+            print(f"{name + ' B=' + str(B):10s} {pname:6s} {cell[0]:>26s} {flops / m[0] / 1e6:6.1f} {cell[1]:>26s} "
+                  f"{flops / m[1] / 1e6:6.1f} {m[0] / m[1]:11.2f}", flush=True)
+
+
+if __name__ == "__main__":
+    main()
