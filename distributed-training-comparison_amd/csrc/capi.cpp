@@ -341,6 +341,37 @@ int dtc_conv2d_f32_dgrad(const dtc_conv_desc* d, const float* dy, const void* w,
   GUARD(return conv2d_f32("dtc_conv2d_f32_dgrad", d, CONV_DGRAD, dy, w, dx, res, nullptr, algo, S(stream));)
 }
 
+// The fp32 weight gradient: conv_f32's WGRAD (algo 0, or a shape the split kernel refuses) or conv_f32x_wgrad
+int dtc_conv2d_f32_wgrad_route_query(const dtc_conv_desc* d, int algo) {
+  DTC_CHECK_ARG(desc_ok_f32(d), "dtc_conv2d_f32_wgrad_route_query: unsupported convolution descriptor");
+  DTC_CHECK_ARG(algo == 0 || algo == 1, "dtc_conv2d_f32_wgrad_route_query: algo %d (0 exact, 1 split)", algo);
+  return conv_f32_route(shape_of(d), CONV_WGRAD, algo != 0, false);
+}
+
+size_t dtc_conv2d_f32_wgrad_workspace_size(const dtc_conv_desc* d, int algo) {
+  if (!desc_ok_f32(d) || (algo != 0 && algo != 1)) return 0;
+  const ConvShape s = shape_of(d);
+  return conv_f32_route(s, CONV_WGRAD, algo != 0, false) == CONV_F32_SPLIT ? conv_f32x_wgrad_workspace(s)
+                                                                          : f32_conv_workspace(s, CONV_WGRAD);
+}
+
+int dtc_conv2d_f32_wgrad(const dtc_conv_desc* d, const float* x, const float* dy, float* dw, float scale, int algo,
+                         void* ws, size_t ws_bytes, void* stream) {
+  DTC_CHECK_ARG(d && x && dy && dw, "dtc_conv2d_f32_wgrad: null argument");
+  DTC_CHECK_ARG(desc_ok_f32(d), "dtc_conv2d_f32_wgrad: unsupported convolution descriptor");
+  DTC_CHECK_ARG(algo == 0 || algo == 1, "dtc_conv2d_f32_wgrad: algo %d (0 exact, 1 split)", algo);
+  const ConvShape s = shape_of(d);
+  if (!ws) ws_bytes = 0;
+  if (conv_f32_route(s, CONV_WGRAD, algo != 0, false) == CONV_F32_SPLIT) {
+    GUARD(return conv_f32x_wgrad(s, x, dy, dw, scale, (float*)ws, ws_bytes, S(stream));)
+  }
+  DTC_CHECK_ARG(ws_bytes >= (size_t)s.K * s.R * s.S * s.C * 4,
+                "dtc_conv2d_f32_wgrad: the exact kernel needs a workspace of at least one slab, %zu bytes (given %zu)",
+                (size_t)s.K * s.R * s.S * s.C * 4, ws_bytes);
+  GUARD(return conv_f32(s, CONV_WGRAD, x, dy, nullptr, nullptr, nullptr, dw, 0, 0, scale, (float*)ws, ws_bytes,
+                        S(stream));)
+}
+
 int dtc_conv2d_fwd_sc(const dtc_conv_desc* d, const uint16_t* x, const uint16_t* w, uint16_t* y, int64_t* stats,
                       const uint16_t* wsc, uint16_t* ysc, int64_t* stats_sc, void* stream) {
   DTC_CHECK_ARG(d && x && w && y && wsc && ysc, "dtc_conv2d_fwd_sc: null argument");

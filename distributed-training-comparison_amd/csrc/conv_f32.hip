@@ -329,6 +329,14 @@ static int f32_fill(F32ConvParams& p, const ConvShape& s) {
 
 static int ceil_div_f(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
+int f32_wgrad_reduce(const float* slab, int splits, int K, int RSC, int ncols, int ld_out, float scale, float* dw,
+                     hipStream_t st, u64* ts) {
+  DTC_KLAUNCH(f32_wgrad_reduce_kernel, dim3(ceil_div_f((int64_t)K * ncols, 256)), dim3(256), 0, st, slab, splits, K,
+              RSC, ncols, ld_out, scale, dw, ts);
+  DTC_LAUNCH_CHECK();
+  return 0;
+}
+
 int f32_wgrad_splits(const ConvShape& s) {
   const int P = (s.H + 2 * s.pad - s.R) / s.stride + 1, Q = (s.W + 2 * s.pad - s.S) / s.stride + 1;
   const int64_t nsteps = ((int64_t)s.N * P * Q + F32_KS - 1) / F32_KS;
@@ -392,10 +400,7 @@ int conv_f32(const ConvShape& s, int mode, const float* a, const float* b, float
   DTC_LAUNCH_CHECK();
   const int ncols = dw_cols > 0 ? dw_cols : p.RSC;
   const int ldo = dw_ld > 0 ? dw_ld : p.RSC;
-  DTC_KLAUNCH(f32_wgrad_reduce_kernel, dim3(ceil_div_f((int64_t)s.K * ncols, 256)), dim3(256), 0, st, slab,
-                     splits, s.K, p.RSC, ncols, ldo, scale, dw_ld_or_null, ts);
-  DTC_LAUNCH_CHECK();
-  return 0;
+  return f32_wgrad_reduce(slab, splits, s.K, p.RSC, ncols, ldo, scale, dw_ld_or_null, st, ts);
 }
 
 }  // namespace dtc

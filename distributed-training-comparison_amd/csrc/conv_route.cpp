@@ -86,11 +86,12 @@ ConvRoute conv_route(const ConvShape& s, int pass, const ConvRequest& rq) {
   return r;
 }
 
-// The fp32 convs' router: the split-bf16 kernel serves FWD / DGRAD of the shapes its predicate accepts, when the
-// caller asks for it and has the weight planes; everything else is conv_f32
+// The fp32 convs' router: the split-bf16 kernels serve the shapes their predicates accept when the caller asks for
+// them (FWD / DGRAD: and has the weight planes; WGRAD splits both operands itself); everything else is conv_f32
 int conv_f32_route(const ConvShape& s, int pass, bool want_split, bool planes) {
-  return want_split && planes && (pass == CONV_FWD || pass == CONV_DGRAD) && conv_f32x_ok(s) ? CONV_F32_SPLIT
-                                                                                               : CONV_F32_EXACT;
+  if (!want_split) return CONV_F32_EXACT;
+  if (pass == CONV_WGRAD) return conv_f32x_wgrad_ok(s) ? CONV_F32_SPLIT : CONV_F32_EXACT;
+  return planes && (pass == CONV_FWD || pass == CONV_DGRAD) && conv_f32x_ok(s) ? CONV_F32_SPLIT : CONV_F32_EXACT;
 }
 
 static ConvRequest with_slab(const float* slab, size_t slab_bytes) {

@@ -65,7 +65,7 @@ namespace dtc {
   X(COMM_TAIL_INLINE, comm_tail_inline, 1) /* the last bucket's all-reduce on the compute stream (no fork / join) */ \
   X(DGRAD_S2H, dgrad_s2h, 1)            /* stride-2 3x3 dgrad (+ shortcut) as a halo sub-pixel conv: 1 K <= 256, 2 all */ \
   X(HALO_SMALL, halo_small, 1)          /* halo FWD/DGRAD: 64x64 double-buffered tiles where they give <= 512 workgroups */ \
-  X(F32_SPLIT, f32_split, 0)            /* (plan time) fp32 executor: 3x3 s1 FWD/DGRAD on the split-bf16 kernel (conv_f32x) */
+  X(F32_SPLIT, f32_split, 0)            /* (plan time) fp32 executor: 3x3 s1 FWD/DGRAD on the split-bf16 kernel (conv_f32x); 2: WGRAD too */
 
 enum {
 #define DTC_OPT_ENUM(id, name, def) OPT_##id,
@@ -232,6 +232,9 @@ int conv_f32(const ConvShape& s, int mode, const float* a, const float* b, float
              int64_t* stats, float* dw, int dw_cols, int dw_ld, float scale, float* slab, size_t slab_bytes,
              hipStream_t st, u64* ts = nullptr);
 size_t f32_conv_workspace(const ConvShape& s, int mode);  // fp32 slab bytes the pass wants
+// dw[k][0:ncols] (row stride ld_out) = scale * sum over the splits of slab[split][k][0:RSC], in split order
+int f32_wgrad_reduce(const float* slab, int splits, int K, int RSC, int ncols, int ld_out, float scale, float* dw,
+                     hipStream_t st, u64* ts = nullptr);
 // Split-bf16 fp32 conv (conv_f32x.hip): 3x3 stride-1 FWD / DGRAD on the bf16 MFMA from three bf16 planes per fp32
 // operand (six plane products, fp32 accumulation): fp32-grade results. src fp32 NHWC (x / dy), wplanes three bf16
 // KRSC planes wstride elements apart (f32_split3 of the fp32 weight), out fp32 (y / dx); FWD: optional BN
@@ -242,9 +245,18 @@ int conv_f32x(const ConvShape& s, int mode, const float* src, const u16* wplanes
               const float* res, int64_t* stats, hipStream_t st, u64* ts = nullptr);
 // planes[p * stride + i] = plane p of src[i], i < n: p0 = bf16(a), p1 = bf16(a - p0), p2 = bf16(a - p0 - p1)
 int f32_split3(const float* src, u16* planes, int64_t n, int64_t stride, hipStream_t st);
-// Which kernel an fp32 FWD / DGRAD runs on (conv_route.cpp): CONV_F32_SPLIT when the split is asked for (the
-// executor: option f32_split; the C ABI: algo), conv_f32x_ok holds and the weight planes exist; else CONV_F32_EXACT
-// (conv_f32). WGRAD is always exact.
+// Split-bf16 fp32 weight gradient (conv_f32x_wgrad.hip): dw[k][r][s][c] = scale * sum dy (x) x of a 3x3 stride-1
+// conv, both fp32 operands split in the kernel. Split-K over pixel steps into fp32 slabs [split][K][9 C] summed by
+// f32_wgrad_reduce; the splits are lowered until `slab` holds them, and one split writes dw itself (no slab needed).
+// conv_f32x_wgrad_ok: rows of 4 / 8 / 16 / 32 pixels whose 64-pixel steps are whole rows or whole images, C and K
+// multiples of 64, tensors below 2 GiB. conv_f32x_wgrad_workspace: the slab bytes it wants (0: one split).
+bool conv_f32x_wgrad_ok(const ConvShape& s);
+size_t conv_f32x_wgrad_workspace(const ConvShape& s);
+int conv_f32x_wgrad(const ConvShape& s, const float* x, const float* dy, float* dw, float scale, float* slab,
+                    size_t slab_bytes, hipStream_t st, u64* ts = nullptr);
+// Which kernel an fp32 pass runs on (conv_route.cpp): CONV_F32_SPLIT when the split is asked for (the executor:
+// option f32_split, 1 for FWD / DGRAD and 2 for WGRAD too; the C ABI: algo) and the pass's predicate holds
+// (conv_f32x_ok and the weight planes exist; WGRAD: conv_f32x_wgrad_ok); else CONV_F32_EXACT (conv_f32).
 enum { CONV_F32_EXACT = 0, CONV_F32_SPLIT = 1 };
 int conv_f32_route(const ConvShape& s, int pass, bool want_split, bool planes);
 int f32_stem_im2col(const float* x, float* cols, int N, int H, int W, hipStream_t st);  // [N*H*W][32]

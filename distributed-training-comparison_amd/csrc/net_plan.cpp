@@ -206,6 +206,8 @@ static void plan_workspace(Net& n, float bucket_cap_mb) {
   auto consider = [&](const ConvShape& s) {
     for (int m = 0; m < 3; ++m)
       slab = std::max(slab, n.f32 ? f32_conv_workspace(s, m) : conv_route(s, m).slab_bytes);
+    // option f32_split = 2: the split-bf16 weight gradient's slabs (the only value that may enlarge the slab)
+    if (n.f32 && option_get(OPT_F32_SPLIT) >= 2 && conv_f32x_wgrad_ok(s)) slab = std::max(slab, conv_f32x_wgrad_workspace(s));
   };
   auto consider_batch = [&](const ConvShape& s) {  // a bucket's 3x3 stride-1 wgrads, 2..DTC_WG_BATCH per launch
     ConvRequest rq;

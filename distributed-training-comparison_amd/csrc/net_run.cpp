@@ -218,9 +218,18 @@ static int64_t* stats_if(Net& n, const BNL& b, bool train) { return train ? n.at
 static int f32_conv(Net& n, int mode, const ConvShape& s, const float* a, const float* b, float* out, const float* res,
                     int64_t* stats, float* dw, int cols, float gs, hipStream_t st, double flops,
                     const u16* wpl = nullptr) {
-  if (conv_f32_route(s, mode, option_get(OPT_F32_SPLIT) != 0, wpl != nullptr) == CONV_F32_SPLIT) {
-    PROF(mode, flops < 0 ? conv_flops(s) : flops, conv_f32x(s, mode, a, wpl, n.plan.wpl_n, out, res, stats, st, ts));
-    return 0;
+  // option f32_split: 1 = FWD / DGRAD, 2 = the weight gradient too (it splits both operands itself: no planes)
+  const bool want = option_get(OPT_F32_SPLIT) >= (mode == CONV_WGRAD ? 2 : 1);
+  if (conv_f32_route(s, mode, want, wpl != nullptr) == CONV_F32_SPLIT) {
+    if (mode == CONV_WGRAD && cols == 0) {
+      PROF(mode, flops < 0 ? conv_flops(s) : flops,
+           conv_f32x_wgrad(s, a, b, dw, gs, n.at<float>(n.plan.SLAB), n.plan.slab_bytes, st, ts));
+      return 0;
+    }
+    if (mode != CONV_WGRAD) {
+      PROF(mode, flops < 0 ? conv_flops(s) : flops, conv_f32x(s, mode, a, wpl, n.plan.wpl_n, out, res, stats, st, ts));
+      return 0;
+    }
   }
   PROF(mode, flops < 0 ? conv_flops(s) : flops,
        conv_f32(s, mode, a, b, out, res, stats, dw, cols, cols, gs, n.at<float>(n.plan.SLAB), n.plan.slab_bytes, st, ts));

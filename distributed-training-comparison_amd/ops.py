@@ -166,6 +166,35 @@ def conv2d_dgrad_f32(dy, w, in_hw, stride, pad, algo=0, res=None, out=None):
     return dx
 
 
+def conv2d_f32_wgrad_route(desc, algo):
+    """dtc_conv2d_f32_wgrad_route_query: which fp32 kernel ("exact" / "split") the weight-gradient entry point runs for
+    `desc` with algo 0 / 1. Host code: nothing is launched."""
+    rc = lib.dtc_conv2d_f32_wgrad_route_query(desc, algo)
+    if rc < 0:
+        call("dtc_conv2d_f32_wgrad_route_query", desc, algo)  # raises with the library's message
+    return CONV_F32_KERNELS[rc]
+
+
+def conv2d_wgrad_f32(x, dy, r, s, stride, pad, algo=0, scale=1.0, out=None, workspace=None):
+    """x [N,H,W,C] fp32, dy [N,P,Q,K] fp32 -> dw [K,R,S,C] fp32 = scale * sum over pixels (the weight gradient of
+    nn.Conv2d without autocast). algo 0: conv_f32; 1: the split-bf16 kernel where it serves the shape. `workspace`
+    (uint8 / float, any size, used as it is: a short one lowers the number of split-K slabs) replaces the tensor of
+    dtc_conv2d_f32_wgrad_workspace_size bytes allocated by default."""
+    require_cuda(x, dy)
+    N, H, W, Cc = x.shape
+    K = dy.shape[3]
+    d = conv_desc(N, H, W, Cc, K, r, s, stride, pad)
+    dw = _out(out, (K, r, s, Cc), torch.float32, x.device, "conv2d_wgrad_f32")
+    if workspace is None:
+        workspace = torch.empty(max(int(lib.dtc_conv2d_f32_wgrad_workspace_size(d, algo)), 16), dtype=torch.uint8,
+                                device=x.device)
+    require_cuda(workspace)
+    nb = workspace.numel() * workspace.element_size()
+    call("dtc_conv2d_f32_wgrad", d, ptr(x), ptr(dy), ptr(dw), scale, algo, ptr(workspace) if nb else None, nb,
+         stream_ptr())
+    return dw
+
+
 def conv2d_dgrad_bn(dy, w, in_hw, stride, pad, ymask, x1, mean1, invstd1, x2=None, mean2=None, invstd2=None,
                     res=None, out=None):
     """conv2d_dgrad fused with bn_bwd_reduce (dtc_conv2d_dgrad_bn): returns (dz, acc1, acc2) where

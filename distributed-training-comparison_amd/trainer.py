@@ -29,6 +29,8 @@ from .nn import CrossEntropyLoss, ResNet18, SyncBatchNorm
 from .optim import LARS, SAM, SGD, Adam, AdamW, clip_grad_norm_
 from .parallel import DDP, DataParallel, PowerSGDState, barrier, bf16_compress_hook, powerSGD_hook
 
+FP32_CONV = ("exact", "split", "split-all")  # --fp32-conv: the value of option f32_split is the index
+
 
 def load_config(argv=None, mode: str = "ddp"):
     p = argparse.ArgumentParser()
@@ -40,9 +42,10 @@ def load_config(argv=None, mode: str = "ddp"):
     p.add_argument("--eval-step", type=int, default=300)
     p.add_argument("--amp", action="store_true", default=False, help="PyTorch(>=1.6.x) AMP")
     # not in the reference: which kernel the fp32 (no --amp) 3x3 stride-1 convs run on
-    p.add_argument("--fp32-conv", choices=("exact", "split"), default="exact",
+    p.add_argument("--fp32-conv", choices=FP32_CONV, default="exact",
                    help="without --amp: exact = the f32-input MFMA convs; split = forward and data-gradient convs on "
-                        "the bf16 MFMA from three bf16 planes per fp32 operand (fp32-grade results, option f32_split)")
+                        "the bf16 MFMA from three bf16 planes per fp32 operand (fp32-grade results, option f32_split); "
+                        "split-all = their weight gradients too (option f32_split = 2)")
     p.add_argument("--contain-test", action="store_true", default=False)
     if mode == "ddp":
         p.add_argument("--world-size", type=int, default=1, help="Total number of processes to run")
@@ -684,7 +687,7 @@ def _run(hparams, rank, ngpus, distributed, data_parallel=False):
     D.fix_seed(hparams.seed)
     scaler = GradScaler() if hparams.amp else None
     # plan-time option: set before the model's executors exist
-    _native.call("dtc_set_option", b"f32_split", 1 if getattr(hparams, "fp32_conv", "exact") == "split" else 0)
+    _native.call("dtc_set_option", b"f32_split", FP32_CONV.index(getattr(hparams, "fp32_conv", "exact")))
     model = ResNet18()
     if getattr(hparams, "sync_bn", False):
         model = SyncBatchNorm.convert_sync_batchnorm(model)

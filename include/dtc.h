@@ -44,7 +44,7 @@ int dtc_install_crash_handler(void);
  * captured graphs), "splitk_ink" (split-K slabs summed in-kernel by the last workgroup of each tile,
  * default 1), "dgrad_s2h" (stride-2 data gradient as a halo sub-pixel conv, default 1), "stem_direct"
  * (plan time: direct 3x3 stem conv, default 1; 0 = im2col + GEMM), "f32_split" (plan time: the fp32 executor's 3x3
- * stride-1 forward and data-gradient convs on the split-bf16 kernel, default 0). */
+ * stride-1 forward and data-gradient convs on the split-bf16 kernel, default 0; 2: their weight gradients too). */
 int dtc_set_option(const char* name, int value);
 int dtc_get_option(const char* name);
 
@@ -171,6 +171,17 @@ int dtc_conv2d_f32_fwd(const dtc_conv_desc* d, const float* x, const void* w, fl
                        void* ws, size_t ws_bytes, void* stream);
 int dtc_conv2d_f32_dgrad(const dtc_conv_desc* d, const float* dy, const void* w, float* dx, const float* res,
                          int algo, void* ws, size_t ws_bytes, void* stream);
+/* The fp32 weight gradient: dw[k][r][s][c] = scale * sum over pixels of dy (x) x, x fp32 NHWC, dy fp32 NPQK, dw fp32.
+ * algo 0: the f32-input MFMA kernel (any descriptor above); it needs a workspace of at least one slab of k*r*s*c*4
+ * bytes (DTC_EINVAL otherwise). algo 1: for the descriptors DTC_CONV_F32_SPLIT serves (here: 64-pixel steps of whole
+ * rows or whole images) the split-bf16 kernel, both operands split in the kernel, element-wise error below 2^-22 of
+ * sum |x||dy|; any other descriptor runs the exact kernel. Both reduce split-K slabs in a fixed order (bit-identical
+ * run to run). A workspace shorter than dtc_conv2d_f32_wgrad_workspace_size lowers the number of splits; the split
+ * kernel runs with none at all (one split). dtc_conv2d_f32_wgrad_route_query (host only): the kernel that runs. */
+int dtc_conv2d_f32_wgrad_route_query(const dtc_conv_desc* d, int algo);
+size_t dtc_conv2d_f32_wgrad_workspace_size(const dtc_conv_desc* d, int algo);
+int dtc_conv2d_f32_wgrad(const dtc_conv_desc* d, const float* x, const float* dy, float* dw, float scale, int algo,
+                         void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------ batch norm (training)
  * Replaces nn.BatchNorm2d train-mode forward/backward (net.py:21,25,37,92) with the F.relu and

@@ -1,5 +1,5 @@
-"""Time the fp32 3x3 stride-1 convs of ResNet-18 (forward and data gradient) on the exact kernel (conv_f32, algo 0)
-and on the split-bf16 kernel (conv_f32x, algo 1), interleaved in one process.
+"""Time the fp32 3x3 stride-1 convs of ResNet-18 (forward, data gradient and weight gradient) on the exact kernel
+(conv_f32, algo 0) and on the split-bf16 kernels (conv_f32x / conv_f32x_wgrad, algo 1), interleaved in one process.
 
 As tools/conv_bench.py: each (layer, pass, algo) is captured ITERS times into a graph on preallocated buffers (raw
 C-ABI calls), so a replay measures device time only; ROUNDS interleaved rounds per case. Prints the median us, the
@@ -40,11 +40,17 @@ def main():
         d = ops.conv_desc(B, H, H, C, C, 3, 3, 1, 1)
         flops = 2.0 * B * H * H * C * 9 * C
         P_ = nat.ptr
-        for pname, mode in (("fwd", 0), ("dgrad", 1)):
-            assert ops.conv2d_f32_route(d, mode, 1) == "split", case
+        dw = torch.empty(C, 3, 3, C, device=dev)
+        wsz = {a: int(nat.lib.dtc_conv2d_f32_wgrad_workspace_size(d, a)) for a in (0, 1)}
+        ws = torch.empty(max(wsz.values()), dtype=torch.uint8, device=dev)
+        for pname, mode in (("fwd", 0), ("dgrad", 1), ("wgrad", 2)):
+            assert (ops.conv2d_f32_wgrad_route(d, 1) if mode == 2 else ops.conv2d_f32_route(d, mode, 1)) == "split", case
             fns = {}
             for algo, wt in ((0, w), (1, wpl)):
-                if mode == 0:
+                if mode == 2:  # x against a dy of the same shape (C = K), each kernel on the slab its size query asks for
+                    fns[algo] = lambda algo=algo: nat.call("dtc_conv2d_f32_wgrad", d, P_(x), P_(out), P_(dw), 1.0, algo,
+                                                           P_(ws), wsz[algo], nat.stream_ptr())
+                elif mode == 0:
                     fns[algo] = lambda algo=algo, wt=wt: nat.call("dtc_conv2d_f32_fwd", d, P_(x), P_(wt), P_(out),
                                                                   P_(stats), algo, None, 0, nat.stream_ptr())
                 else:
