@@ -121,6 +121,9 @@ _SIGS = {
     "dtc_conv2d_f32_route_query": (i32, [PConv, i32, i32]),
     "dtc_conv2d_f32_fwd": (i32, [PConv, vp, vp, vp, vp, i32, vp, sz, vp]),
     "dtc_conv2d_f32_dgrad": (i32, [PConv, vp, vp, vp, vp, i32, vp, sz, vp]),
+    "dtc_conv2d_f32_sc_route_query": (i32, [PConv, i32, i32]),
+    "dtc_conv2d_f32_fwd_sc": (i32, [PConv, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
+    "dtc_conv2d_f32_dgrad_sc": (i32, [PConv, vp, vp, vp, vp, vp, i32, vp]),
     "dtc_conv2d_f32_wgrad_route_query": (i32, [PConv, i32]),
     "dtc_conv2d_f32_wgrad_workspace_size": (sz, [PConv, i32]),
     "dtc_conv2d_f32_wgrad": (i32, [PConv, vp, vp, vp, f32, i32, vp, sz, vp]),

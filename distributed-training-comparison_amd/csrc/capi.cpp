@@ -341,6 +341,51 @@ int dtc_conv2d_f32_dgrad(const dtc_conv_desc* d, const float* dy, const void* w,
   GUARD(return conv2d_f32("dtc_conv2d_f32_dgrad", d, CONV_DGRAD, dy, w, dx, res, nullptr, algo, S(stream));)
 }
 
+// ---- the transition blocks' fused pair on fp32 tensors: conv1 (the descriptor: 3x3 / pad 1, stride 2 in the model)
+// and the block's 1x1 shortcut of the same stride. algo 0 (and any shape the split kernel refuses): the two conv_f32
+// launches
+static bool desc_ok_f32_sc(const dtc_conv_desc* d) { return desc_ok_f32(d) && d->r == 3 && d->s == 3 && d->pad == 1; }
+static ConvShape sc_shape_of(const ConvShape& s) { return ConvShape{s.N, s.H, s.W, s.C, s.K, 1, 1, s.stride, 0}; }
+
+int dtc_conv2d_f32_sc_route_query(const dtc_conv_desc* d, int pass, int algo) {
+  DTC_CHECK_ARG(desc_ok_f32_sc(d), "dtc_conv2d_f32_sc_route_query: not a 3x3 pad-1 convolution conv_f32 takes");
+  DTC_CHECK_ARG((pass == CONV_FWD || pass == CONV_DGRAD) && (algo == 0 || algo == 1),
+                "dtc_conv2d_f32_sc_route_query: pass %d algo %d name no entry point", pass, algo);
+  return conv_f32_sc_route(shape_of(d), pass, algo != 0, true);
+}
+
+int dtc_conv2d_f32_fwd_sc(const dtc_conv_desc* d, const float* x, const void* w, float* y, int64_t* stats,
+                          const void* wsc, float* ysc, int64_t* stats_sc, int algo, void* stream) {
+  DTC_CHECK_ARG(d && x && w && y && wsc && ysc, "dtc_conv2d_f32_fwd_sc: null argument");
+  DTC_CHECK_ARG(desc_ok_f32_sc(d), "dtc_conv2d_f32_fwd_sc: not a 3x3 pad-1 convolution conv_f32 takes");
+  DTC_CHECK_ARG(algo == 0 || algo == 1, "dtc_conv2d_f32_fwd_sc: algo %d (0 exact, 1 split)", algo);
+  const ConvShape s = shape_of(d);
+  GUARD(
+    if (conv_f32_sc_route(s, CONV_FWD, algo != 0, true) == CONV_F32_SPLIT)
+      return conv_f32x_s2_fwd(s, x, (const u16*)w, (int64_t)s.K * 9 * s.C, y, stats, (const u16*)wsc, (int64_t)s.K * s.C,
+                              ysc, stats_sc, S(stream));
+    DTC_TRY(conv_f32(sc_shape_of(s), CONV_FWD, x, (const float*)wsc, ysc, nullptr, stats_sc, nullptr, 0, 0, 0.f, nullptr,
+                     0, S(stream)));
+    return conv_f32(s, CONV_FWD, x, (const float*)w, y, nullptr, stats, nullptr, 0, 0, 0.f, nullptr, 0, S(stream));)
+}
+
+// exact pair: the shortcut's data gradient goes into dx, and conv1's takes dx as its residual in place (conv_f32's
+// epilogue reads and writes each element in one thread): the executor's residual form without a second buffer
+int dtc_conv2d_f32_dgrad_sc(const dtc_conv_desc* d, const float* dy, const void* w, float* dx, const float* dsc,
+                            const void* wsc, int algo, void* stream) {
+  DTC_CHECK_ARG(d && dy && w && dx && dsc && wsc, "dtc_conv2d_f32_dgrad_sc: null argument");
+  DTC_CHECK_ARG(desc_ok_f32_sc(d), "dtc_conv2d_f32_dgrad_sc: not a 3x3 pad-1 convolution conv_f32 takes");
+  DTC_CHECK_ARG(algo == 0 || algo == 1, "dtc_conv2d_f32_dgrad_sc: algo %d (0 exact, 1 split)", algo);
+  const ConvShape s = shape_of(d);
+  GUARD(
+    if (conv_f32_sc_route(s, CONV_DGRAD, algo != 0, true) == CONV_F32_SPLIT)
+      return conv_f32x_s2_dgrad(s, dy, (const u16*)w, (int64_t)s.K * 9 * s.C, dx, dsc, (const u16*)wsc,
+                                (int64_t)s.K * s.C, S(stream));
+    DTC_TRY(conv_f32(sc_shape_of(s), CONV_DGRAD, dsc, (const float*)wsc, dx, nullptr, nullptr, nullptr, 0, 0, 0.f,
+                     nullptr, 0, S(stream)));
+    return conv_f32(s, CONV_DGRAD, dy, (const float*)w, dx, dx, nullptr, nullptr, 0, 0, 0.f, nullptr, 0, S(stream));)
+}
+
 // The fp32 weight gradient: conv_f32's WGRAD (algo 0, or a shape the split kernel refuses) or conv_f32x_wgrad
 int dtc_conv2d_f32_wgrad_route_query(const dtc_conv_desc* d, int algo) {
   DTC_CHECK_ARG(desc_ok_f32(d), "dtc_conv2d_f32_wgrad_route_query: unsupported convolution descriptor");

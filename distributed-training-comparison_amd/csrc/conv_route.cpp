@@ -94,6 +94,14 @@ int conv_f32_route(const ConvShape& s, int pass, bool want_split, bool planes) {
   return planes && (pass == CONV_FWD || pass == CONV_DGRAD) && conv_f32x_ok(s) ? CONV_F32_SPLIT : CONV_F32_EXACT;
 }
 
+// The transition blocks' fused pair (conv1 3x3 stride 2 + the 1x1 stride-2 shortcut, FWD / DGRAD): the split-bf16
+// kernel (conv_f32x_s2) when the caller asks for it, has both weights' planes and its predicate accepts conv1's
+// shape; else the exact pair, two conv_f32 launches
+int conv_f32_sc_route(const ConvShape& s, int pass, bool want_split, bool planes) {
+  return want_split && planes && (pass == CONV_FWD || pass == CONV_DGRAD) && conv_f32x_s2_ok(s, pass) ? CONV_F32_SPLIT
+                                                                                                : CONV_F32_EXACT;
+}
+
 static ConvRequest with_slab(const float* slab, size_t slab_bytes) {
   ConvRequest rq;
   rq.slab_bytes = slab ? slab_bytes : 0;

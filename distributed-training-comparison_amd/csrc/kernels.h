@@ -65,7 +65,8 @@ namespace dtc {
   X(COMM_TAIL_INLINE, comm_tail_inline, 1) /* the last bucket's all-reduce on the compute stream (no fork / join) */ \
   X(DGRAD_S2H, dgrad_s2h, 1)            /* stride-2 3x3 dgrad (+ shortcut) as a halo sub-pixel conv: 1 K <= 256, 2 all */ \
   X(HALO_SMALL, halo_small, 1)          /* halo FWD/DGRAD: 64x64 double-buffered tiles where they give <= 512 workgroups */ \
-  X(F32_SPLIT, f32_split, 0)            /* (plan time) fp32 executor: 3x3 s1 FWD/DGRAD on the split-bf16 kernel (conv_f32x); 2: WGRAD too */
+  X(F32_SPLIT, f32_split, 0)            /* (plan time) fp32 executor: 3x3 s1 FWD/DGRAD on the split-bf16 kernel (conv_f32x); 2: WGRAD too; 3: + the transition blocks' FWD / DGRAD (conv_f32x_s2) */ \
+  X(F32X_S2_FWD, f32x_s2_fwd, 1)        /* conv_f32x_s2 FWD_SC: 1 where it measured faster than the exact pair, 2 every feasible geometry (to measure) */
 
 enum {
 #define DTC_OPT_ENUM(id, name, def) OPT_##id,
@@ -254,6 +255,21 @@ bool conv_f32x_wgrad_ok(const ConvShape& s);
 size_t conv_f32x_wgrad_workspace(const ConvShape& s);
 int conv_f32x_wgrad(const ConvShape& s, const float* x, const float* dy, float* dw, float scale, float* slab,
                     size_t slab_bytes, hipStream_t st, u64* ts = nullptr);
+// Split-bf16 transition-block convs (conv_f32x_s2.hip): conv1 (3x3 / stride 2 / pad 1) of a projection block and its
+// 1x1 stride-2 shortcut in one launch, fp32 in and out. FWD: y = conv(x, W1), ysc = conv1x1(x, Wsc), each with optional
+// BN statistics as conv_f32's; DGRAD: dx = dgrad(dy, W1) + dgrad1x1(dsc, Wsc), every pixel written once. Weights: three
+// bf16 planes each (f32_split3), wstride / wsc_stride elements apart. conv_f32x_s2_ok: even extents, output rows of
+// 4 / 8 / 16 positions whose 32-position tiles are whole rows or whole images, C and K multiples of 64, tensors
+// below 2 GiB; FWD also only where it measured faster than the exact pair (conv_f32x_s2.hip).
+bool conv_f32x_s2_ok(const ConvShape& s, int pass);
+int conv_f32x_s2_fwd(const ConvShape& s, const float* x, const u16* wplanes, int64_t wstride, float* y, int64_t* stats,
+                     const u16* wsc_planes, int64_t wsc_stride, float* ysc, int64_t* stats_sc, hipStream_t st,
+                     u64* ts = nullptr);
+int conv_f32x_s2_dgrad(const ConvShape& s, const float* dy, const u16* wplanes, int64_t wstride, float* dx,
+                       const float* dsc, const u16* wsc_planes, int64_t wsc_stride, hipStream_t st, u64* ts = nullptr);
+// The fused pair's route (conv_route.cpp): CONV_F32_SPLIT when the split is asked for, both weights' planes exist and
+// conv_f32x_s2_ok holds; else CONV_F32_EXACT, the two conv_f32 launches per pass (FWD / DGRAD only)
+int conv_f32_sc_route(const ConvShape& s, int pass, bool want_split, bool planes);
 // Which kernel an fp32 pass runs on (conv_route.cpp): CONV_F32_SPLIT when the split is asked for (the executor:
 // option f32_split, 1 for FWD / DGRAD and 2 for WGRAD too; the C ABI: algo) and the pass's predicate holds
 // (conv_f32x_ok and the weight planes exist; WGRAD: conv_f32x_wgrad_ok); else CONV_F32_EXACT (conv_f32).

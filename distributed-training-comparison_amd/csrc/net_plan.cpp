@@ -235,12 +235,20 @@ static void plan_workspace(Net& n, float bucket_cap_mb) {
   p.wpl_lo = p.wpl_n = 0;
   if (n.f32 && option_get(OPT_F32_SPLIT) != 0) {
     int64_t lo = INT64_MAX, hi = 0;
-    for (auto& b : n.blocks)
+    auto cover = [&](const ConvL& c) {
+      lo = std::min(lo, n.params[c.pidx].offset);
+      hi = std::max(hi, align_up(n.params[c.pidx].offset + n.params[c.pidx].numel, 64));
+    };
+    for (auto& b : n.blocks) {
       for (const ConvL* c : {&b.c1, &b.c2})
-        if (conv_f32x_ok(c->s)) {
-          lo = std::min(lo, n.params[c->pidx].offset);
-          hi = std::max(hi, align_up(n.params[c->pidx].offset + n.params[c->pidx].numel, 64));
-        }
+        if (conv_f32x_ok(c->s)) cover(*c);
+      // 3: the transition blocks' conv1 and shortcut (conv_f32x_s2). In ResNet-18's parameter order they lie between
+      // layer1's and layer4's stride-1 convs, so the range -- and the workspace -- is the one planned at 2
+      if (option_get(OPT_F32_SPLIT) >= 3 && b.proj && conv_f32x_s2_ok(b.c1.s, CONV_DGRAD)) {
+        cover(b.c1);
+        cover(b.sc);
+      }
+    }
     if (hi > lo) {
       p.wpl_lo = lo;
       p.wpl_n = hi - lo;

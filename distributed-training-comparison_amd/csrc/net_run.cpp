@@ -241,6 +241,13 @@ static const u16* f32_planes(const Net& n, const ConvL& c) {
   const int64_t off = n.params[c.pidx].offset;
   return p.wpl_n > 0 && off >= p.wpl_lo && off + n.params[c.pidx].numel <= p.wpl_lo + p.wpl_n ? n.wpl(c.pidx) : nullptr;
 }
+// option f32_split = 3: a projection block's conv1 + shortcut, FWD / DGRAD, in one conv_f32x_s2 launch (both planes
+// planned and the shape accepted)
+static bool f32_sc_split(const Net& n, const BlockL& b, int pass) {
+  return b.proj &&
+         conv_f32_sc_route(b.c1.s, pass, option_get(OPT_F32_SPLIT) >= 3, f32_planes(n, b.c1) && f32_planes(n, b.sc)) ==
+             CONV_F32_SPLIT;
+}
 static int f32_fwd(Net& n, const ConvShape& s, const float* x, const float* w, float* y, int64_t* stats, hipStream_t st,
                    double flops = -1, const u16* wpl = nullptr) {
   return f32_conv(n, CONV_FWD, s, x, w, y, nullptr, stats, nullptr, 0, 0.f, st, flops, wpl);
@@ -272,12 +279,19 @@ static int forward_body_f32(Net& n, float* logits, bool train, hipStream_t st) {
   const float* in = n.at<float>(p.A0);
   for (auto& b : n.blocks) {
     const int64_t M = (int64_t)n.B * b.Hout * b.Wout;
-    DTC_TRY(f32_fwd(n, b.c1.s, in, n.pf(b.c1.pidx), n.at<float>(b.C1), stats_if(n, b.b1, train), st, -1, f32_planes(n, b.c1)));
+    const bool scx = f32_sc_split(n, b, CONV_FWD);
+    if (scx) {
+      PROF(0, conv_flops(b.c1.s) + conv_flops(b.sc.s),
+           conv_f32x_s2_fwd(b.c1.s, in, f32_planes(n, b.c1), p.wpl_n, n.at<float>(b.C1), stats_if(n, b.b1, train),
+                            f32_planes(n, b.sc), p.wpl_n, n.at<float>(b.S), stats_if(n, b.bsc, train), st, ts));
+    } else {
+      DTC_TRY(f32_fwd(n, b.c1.s, in, n.pf(b.c1.pidx), n.at<float>(b.C1), stats_if(n, b.b1, train), st, -1, f32_planes(n, b.c1)));
+    }
     DTC_TRY(bn_act(n, 1, b.b1, n.at<float>(b.C1), nullptr, nullptr, n.at<float>(b.A1), M, train, st));
     DTC_TRY(f32_fwd(n, b.c2.s, n.at<float>(b.A1), n.pf(b.c2.pidx), n.at<float>(b.C2), stats_if(n, b.b2, train), st, -1,
                     f32_planes(n, b.c2)));
     if (b.proj) {
-      DTC_TRY(f32_fwd(n, b.sc.s, in, n.pf(b.sc.pidx), n.at<float>(b.S), stats_if(n, b.bsc, train), st));
+      if (!scx) DTC_TRY(f32_fwd(n, b.sc.s, in, n.pf(b.sc.pidx), n.at<float>(b.S), stats_if(n, b.bsc, train), st));
       DTC_TRY(bn_act(n, 3, b.b2, n.at<float>(b.C2), &b.bsc, n.at<float>(b.S), n.at<float>(b.OUT), M, train, st));
     } else {
       DTC_TRY(bn_act(n, 2, b.b2, n.at<float>(b.C2), nullptr, in, n.at<float>(b.OUT), M, train, st));
@@ -866,9 +880,18 @@ static int backward_body_f32(Net& n, const float* dlogits, float gs, const BwdCt
     DTC_TRY(f32_wgrad(n, b.c1.s, in, dc1, n.gf(b.c1.pidx), gs, st));
     if (b.proj) {
       DTC_TRY(f32_wgrad(n, b.sc.s, in, dsc, n.gf(b.sc.pidx), gs, st));
-      DTC_TRY(f32_dgrad(n, b.sc.s, dsc, n.pf(b.sc.pidx), G[5], nullptr, st));
-      DTC_TRY(cap(n, cp + ".dxs", G[5], st));
-      DTC_TRY(f32_dgrad(n, b.c1.s, dc1, n.pf(b.c1.pidx), G[0], G[5], st, f32_planes(n, b.c1)));
+      if (f32_sc_split(n, b, CONV_DGRAD)) {  // one launch, dx written once: no G[5] round trip
+        if (n.capture) {  // (parity captures store the shortcut's own data gradient: computed for the capture only)
+          DTC_TRY(f32_dgrad(n, b.sc.s, dsc, n.pf(b.sc.pidx), G[5], nullptr, st));
+          DTC_TRY(cap(n, cp + ".dxs", G[5], st));
+        }
+        PROF(1, conv_flops(b.c1.s) + conv_flops(b.sc.s),
+             conv_f32x_s2_dgrad(b.c1.s, dc1, f32_planes(n, b.c1), p.wpl_n, G[0], dsc, f32_planes(n, b.sc), p.wpl_n, st, ts));
+      } else {
+        DTC_TRY(f32_dgrad(n, b.sc.s, dsc, n.pf(b.sc.pidx), G[5], nullptr, st));
+        DTC_TRY(cap(n, cp + ".dxs", G[5], st));
+        DTC_TRY(f32_dgrad(n, b.c1.s, dc1, n.pf(b.c1.pidx), G[0], G[5], st, f32_planes(n, b.c1)));
+      }
     } else {  // dx = dgrad + dz2 (the identity shortcut's gradient)
       DTC_TRY(f32_dgrad(n, b.c1.s, dc1, n.pf(b.c1.pidx), G[0], dz2, st, f32_planes(n, b.c1)));
     }

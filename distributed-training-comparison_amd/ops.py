@@ -166,6 +166,55 @@ def conv2d_dgrad_f32(dy, w, in_hw, stride, pad, algo=0, res=None, out=None):
     return dx
 
 
+def conv2d_f32_sc_route(desc, mode, algo):
+    """dtc_conv2d_f32_sc_route_query: which fp32 kernel ("exact": two conv_f32 launches / "split": one conv_f32x_s2
+    launch) the fused conv1 + shortcut FWD (0) / DGRAD (1) entry point runs for conv1's `desc`. Host code."""
+    rc = lib.dtc_conv2d_f32_sc_route_query(desc, mode, algo)
+    if rc < 0:
+        call("dtc_conv2d_f32_sc_route_query", desc, mode, algo)  # raises with the library's message
+    return CONV_F32_KERNELS[rc]
+
+
+def _f32_sc_weights(d, mode, w, wsc, algo):
+    """(w, wsc) as the fused fp32 entry point takes them: fp32 filters for the exact pair, their planes for the split
+    kernel (split here from fp32 filters; bf16 [3, ...] tensors are taken as the planes), as _f32_weight does."""
+    split = conv2d_f32_sc_route(d, mode, algo) == "split"
+    if w.dtype == torch.bfloat16 or wsc.dtype == torch.bfloat16:
+        if not split or w.dtype != wsc.dtype:
+            raise ValueError("conv2d_f32_sc: weight planes are taken for both filters, where the split kernel runs")
+        return w, wsc
+    return (f32_split3(w), f32_split3(wsc)) if split else (w, wsc)
+
+
+def conv2d_f32_fwd_sc(x, w, wsc, algo=0, stats=None, stats_sc=None, out=None):
+    """conv2d_fwd_sc on fp32 tensors: x [N,H,W,C], w [K,3,3,C], wsc [K,C] fp32 -> (y, ysc) [N,H/2,W/2,K] fp32. algo 0:
+    two conv_f32 launches; 1: one split-bf16 launch where conv2d_f32_sc_route says "split"."""
+    require_cuda(x, w, wsc)
+    N, H, W, Cc = x.shape
+    K = w.shape[-4]
+    d = conv_desc(N, H, W, Cc, K, 3, 3, 2, 1)
+    P, Q = conv_out_hw(H, W, 3, 3, 2, 1)
+    wk, wsck = _f32_sc_weights(d, 0, w, wsc, algo)
+    y, ysc = (_out(o, (N, P, Q, K), torch.float32, x.device, "conv2d_f32_fwd_sc") for o in (out if out is not None else (None, None)))
+    call("dtc_conv2d_f32_fwd_sc", d, ptr(x), ptr(wk), ptr(y), ptr(stats), ptr(wsck), ptr(ysc), ptr(stats_sc), algo,
+         stream_ptr())
+    return y, ysc
+
+
+def conv2d_dgrad_sc_f32(dy, w, dsc, wsc, in_hw, algo=0, out=None):
+    """conv2d_dgrad_sc on fp32 tensors: dx [N,H,W,C] = dgrad(dy, w) + dgrad(dsc, wsc) of a projection block's conv1
+    (3x3 stride 2) and 1x1 stride-2 shortcut. algo as conv2d_f32_fwd_sc's."""
+    require_cuda(dy, w, dsc, wsc)
+    N = dy.shape[0]
+    K, _, _, Cc = w.shape[-4:]
+    H, W = in_hw
+    d = conv_desc(N, H, W, Cc, K, 3, 3, 2, 1)
+    wk, wsck = _f32_sc_weights(d, 1, w, wsc, algo)
+    dx = _out(out, (N, H, W, Cc), torch.float32, dy.device, "conv2d_dgrad_sc_f32")
+    call("dtc_conv2d_f32_dgrad_sc", d, ptr(dy), ptr(wk), ptr(dx), ptr(dsc), ptr(wsck), algo, stream_ptr())
+    return dx
+
+
 def conv2d_f32_wgrad_route(desc, algo):
     """dtc_conv2d_f32_wgrad_route_query: which fp32 kernel ("exact" / "split") the weight-gradient entry point runs for
     `desc` with algo 0 / 1. Host code: nothing is launched."""

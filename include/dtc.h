@@ -44,7 +44,8 @@ int dtc_install_crash_handler(void);
  * captured graphs), "splitk_ink" (split-K slabs summed in-kernel by the last workgroup of each tile,
  * default 1), "dgrad_s2h" (stride-2 data gradient as a halo sub-pixel conv, default 1), "stem_direct"
  * (plan time: direct 3x3 stem conv, default 1; 0 = im2col + GEMM), "f32_split" (plan time: the fp32 executor's 3x3
- * stride-1 forward and data-gradient convs on the split-bf16 kernel, default 0; 2: their weight gradients too). */
+ * stride-1 forward and data-gradient convs on the split-bf16 kernel, default 0; 2: their weight gradients too; 3: also
+ * the transition blocks' conv1 + shortcut forward and data gradient, one split-bf16 launch each). */
 int dtc_set_option(const char* name, int value);
 int dtc_get_option(const char* name);
 
@@ -171,6 +172,31 @@ int dtc_conv2d_f32_fwd(const dtc_conv_desc* d, const float* x, const void* w, fl
                        void* ws, size_t ws_bytes, void* stream);
 int dtc_conv2d_f32_dgrad(const dtc_conv_desc* d, const float* dy, const void* w, float* dx, const float* res,
                          int algo, void* ws, size_t ws_bytes, void* stream);
+/* The transition blocks' fused pair on fp32 tensors: conv1 (the descriptor: 3x3 / stride 2 / pad 1) of a projection
+ * block and the block's 1x1 stride-2 shortcut of the same input, as dtc_conv2d_fwd_sc / dtc_conv2d_dgrad_sc are for
+ * bf16.
+ *   fwd_sc    y = conv(x, w), ysc = conv1x1(x, wsc), both [n][h/2][w/2][k] fp32, each with optional BN statistics
+ *   dgrad_sc  dx = dgrad(dy, w) + dgrad1x1(dsc, wsc), [n][h][w][c] fp32
+ * algo 0: any 3x3 / pad 1 descriptor dtc_conv2d_f32_fwd takes (the shortcut has conv1's stride); the two exact launches
+ * per call (dgrad_sc: the shortcut's data gradient into dx, then conv1's with dx as its residual), bit-identical to
+ * the separate calls; w [k][3][3][c] and wsc [k][c] are fp32.
+ * algo 1: where dtc_conv2d_f32_sc_route_query answers DTC_CONV_F32_SPLIT for (descriptor, pass, 1), ONE launch of the
+ * split-bf16 kernel (element-wise error below 2^-22 of sum |x||w|; bit-identical run to run; x is read once, dx written
+ * once); w and wsc are then the filters' planes [3][k*9*c] and [3][k*c] as dtc_f32_split3 writes them. Where it
+ * answers DTC_CONV_F32_EXACT, algo 1 is algo 0 and takes fp32 filters. The form of w / wsc a call takes is ALWAYS the
+ * query's answer for that pass: ask before every call whose shape or pass is new. Planes passed where the exact pair
+ * runs (or fp32 filters where the split kernel runs) are read as the other form: wrong results, no error.
+ * The query's DTC_CONV_F32_SPLIT needs even h and w, output rows 4 / 8 / 16 wide, c and k multiples of 64 and tensors
+ * below 2 GiB; these are necessary, not sufficient: the forward is further limited to the shapes where it measured
+ * faster than the exact pair, so the two passes can answer differently for one descriptor (the model's layers 2 and
+ * 4 at batch 256: forward exact, data gradient split; option "f32x_s2_fwd" = 2 lifts that limit, for measuring).
+ * dtc_conv2d_f32_sc_route_query (host only): DTC_CONV_F32_EXACT / _SPLIT for (descriptor, DTC_CONV_FWD / _DGRAD, algo),
+ * or a negative value for a descriptor, pass or algo these entry points do not serve. */
+int dtc_conv2d_f32_sc_route_query(const dtc_conv_desc* d, int pass, int algo);
+int dtc_conv2d_f32_fwd_sc(const dtc_conv_desc* d, const float* x, const void* w, float* y, int64_t* stats,
+                          const void* wsc, float* ysc, int64_t* stats_sc, int algo, void* stream);
+int dtc_conv2d_f32_dgrad_sc(const dtc_conv_desc* d, const float* dy, const void* w, float* dx, const float* dsc,
+                            const void* wsc, int algo, void* stream);
 /* The fp32 weight gradient: dw[k][r][s][c] = scale * sum over pixels of dy (x) x, x fp32 NHWC, dy fp32 NPQK, dw fp32.
  * algo 0: the f32-input MFMA kernel (any descriptor above); it needs a workspace of at least one slab of k*r*s*c*4
  * bytes (DTC_EINVAL otherwise). algo 1: for the descriptors DTC_CONV_F32_SPLIT serves (here: 64-pixel steps of whole

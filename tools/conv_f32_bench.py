@@ -1,5 +1,6 @@
 """Time the fp32 3x3 stride-1 convs of ResNet-18 (forward, data gradient and weight gradient) on the exact kernel
-(conv_f32, algo 0) and on the split-bf16 kernels (conv_f32x / conv_f32x_wgrad, algo 1), interleaved in one process.
+(conv_f32, algo 0) and on the split-bf16 kernels (conv_f32x / conv_f32x_wgrad, algo 1), interleaved in one process;
+then the transition blocks' conv1 + shortcut pair (fwd_sc / dgrad_sc: two conv_f32 launches against conv_f32x_s2).
 
 As tools/conv_bench.py: each (layer, pass, algo) is captured ITERS times into a graph on preallocated buffers (raw
 C-ABI calls), so a replay measures device time only; ROUNDS interleaved rounds per case. Prints the median us, the
@@ -15,11 +16,81 @@ import torch  # noqa: E402
 import dtc_import  # noqa: E402
 
 LAYERS = [("l1", 32, 64), ("l2", 16, 128), ("l3", 8, 256), ("l4", 4, 512)]  # (name, H = W, C = K)
+TRANSITIONS = [("t2", 32, 64, 128), ("t3", 16, 128, 256), ("t4", 8, 256, 512)]  # (name, H = W in, C, K): layers 2-4, block 0
+
+
+def time_interleaved(fns, iters, rounds):
+    """us per call of each fn: `iters` calls captured into a graph, `rounds` interleaved rounds of one timed replay."""
+    us = {a: [] for a in fns}
+    for _ in range(rounds):
+        for algo, fn in fns.items():
+            fn()
+            torch.cuda.synchronize()
+            g, s = torch.cuda.CUDAGraph(), torch.cuda.Stream()
+            with torch.cuda.stream(s):
+                with torch.cuda.graph(g, stream=s):
+                    for _ in range(iters):
+                        fn()
+            g.replay()
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            g.replay()
+            e1.record()
+            torch.cuda.synchronize()
+            us[algo].append(e0.elapsed_time(e1) * 1e3 / iters)
+            del g
+    return us
+
+
+def report(label, pname, us, flops, note=""):
+    m = {a: statistics.median(v) for a, v in us.items()}
+    cell = {a: f"{m[a]:8.1f} ({min(us[a]):.1f}..{max(us[a]):.1f})" for a in us}
+    print(f"{label:10s} {pname:8s} {cell[0]:>26s} {flops / m[0] / 1e6:6.1f} {cell[1]:>26s} "
+          f"{flops / m[1] / 1e6:6.1f} {m[0] / m[1]:11.2f}{note}", flush=True)
+
+
+def transition_cases(dtc, cases, iters, rounds):
+    """conv1 (3x3 stride 2) + the 1x1 stride-2 shortcut of a transition block: algo 0 is the exact pair (two conv_f32
+    launches per call, what the executor pays), algo 1 the one conv_f32x_s2 launch."""
+    ops, nat = dtc.ops, dtc._native
+    dev, P_ = torch.device("cuda:0"), nat.ptr
+    geo = {n: (h, c, k) for n, h, c, k in TRANSITIONS}
+    for case in cases.split(","):
+        name, B = case.split(":")[0], int(case.split(":")[1])
+        H, C, K = geo[name]
+        x = torch.randn(B, H, H, C, device=dev)
+        dy, dsc = torch.randn(B, H // 2, H // 2, K, device=dev), torch.randn(B, H // 2, H // 2, K, device=dev)
+        w, wsc = torch.randn(K, 3, 3, C, device=dev) * 0.05, torch.randn(K, C, device=dev) * 0.1
+        wts = {0: (w, wsc), 1: (ops.f32_split3(w), ops.f32_split3(wsc))}
+        y, ysc, dx = torch.empty_like(dy), torch.empty_like(dy), torch.empty_like(x)
+        st, st_sc = ops.new_stats(K, dev), ops.new_stats(K, dev)
+        d = ops.conv_desc(B, H, H, C, K, 3, 3, 2, 1)
+        flops = 2.0 * B * (H // 2) ** 2 * C * 10 * K
+        for pname, mode in (("fwd_sc", 0), ("dgrad_sc", 1)):
+            note = ""
+            if ops.conv2d_f32_sc_route(d, mode, 1) != "split":  # refused by default: timed with the predicate opened
+                nat.call("dtc_set_option", b"f32x_s2_fwd", 2)
+                note = "  (refused by default)"
+            assert ops.conv2d_f32_sc_route(d, mode, 1) == "split", case
+            fns = {}
+            for algo, (wt, wsct) in wts.items():
+                if mode == 0:
+                    fns[algo] = lambda algo=algo, wt=wt, wsct=wsct: nat.call(
+                        "dtc_conv2d_f32_fwd_sc", d, P_(x), P_(wt), P_(y), P_(st), P_(wsct), P_(ysc), P_(st_sc), algo,
+                        nat.stream_ptr())
+                else:
+                    fns[algo] = lambda algo=algo, wt=wt, wsct=wsct: nat.call(
+                        "dtc_conv2d_f32_dgrad_sc", d, P_(dy), P_(wt), P_(dx), P_(dsc), P_(wsct), algo, nat.stream_ptr())
+            report(f"{name} B={B}", pname, time_interleaved(fns, iters, rounds), flops, note)
+            nat.call("dtc_set_option", b"f32x_s2_fwd", 1)
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="l1:256,l2:256,l3:256,l4:256,l3:32,l4:32", help="layer:batch, ...")
+    ap.add_argument("--sc-cases", default="t2:256,t3:256,t4:256,t2:32,t3:32,t4:32",
+                    help="transition blocks (conv1 + shortcut in one call), name:batch, ...; empty: none")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
     args = ap.parse_args()
@@ -27,7 +98,7 @@ def main():
     ops, nat = dtc.ops, dtc._native
     dev = torch.device("cuda:0")
     geo = {n: (h, c) for n, h, c in LAYERS}
-    print(f"{'case':10s} {'pass':6s} {'exact us (min..max)':>26s} {'TF/s':>6s} {'split us (min..max)':>26s} {'TF/s':>6s} "
+    print(f"{'case':10s} {'pass':8s} {'exact us (min..max)':>26s} {'TF/s':>6s} {'split us (min..max)':>26s} {'TF/s':>6s} "
           f"{'exact/split':>11s}")
     for case in args.cases.split(","):
         name, B = case.split(":")[0], int(case.split(":")[1])
@@ -56,29 +127,11 @@ def main():
                 else:
                     fns[algo] = lambda algo=algo, wt=wt: nat.call("dtc_conv2d_f32_dgrad", d, P_(x), P_(wt), P_(out),
                                                                   None, algo, None, 0, nat.stream_ptr())
-            us = {0: [], 1: []}
-            for _ in range(args.rounds):
-                for algo, fn in fns.items():
-                    fn()
-                    torch.cuda.synchronize()
-                    g, s = torch.cuda.CUDAGraph(), torch.cuda.Stream()
-                    with torch.cuda.stream(s):
-                        with torch.cuda.graph(g, stream=s):
-                            for _ in range(args.iters):
-                                fn()
-                    g.replay()
-                    torch.cuda.synchronize()
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    g.replay()
-                    e1.record()
-                    torch.cuda.synchronize()
-                    us[algo].append(e0.elapsed_time(e1) * 1e3 / args.iters)
-                    del g
-            m = {a: statistics.median(v) for a, v in us.items()}
-            cell = {a: f"{m[a]:8.1f} ({min(us[a]):.1f}..{max(us[a]):.1f})" for a in us}
-            print(f"{name + ' B=' + str(B):10s} {pname:6s} {cell[0]:>26s} {flops / m[0] / 1e6:6.1f} {cell[1]:>26s} "
-                  f"{flops / m[1] / 1e6:6.1f} {m[0] / m[1]:11.2f}", flush=True)
+            us = time_interleaved(fns, args.iters, args.rounds)
+            report(f"{name} B={B}", pname, us, flops)
+        del x, w, wpl, out, dw, ws
+    if args.sc_cases:
+        transition_cases(dtc, args.sc_cases, args.iters, args.rounds)
 
 
 if __name__ == "__main__":
