@@ -127,6 +127,9 @@ _SIGS = {
     "dtc_conv2d_f32_wgrad_route_query": (i32, [PConv, i32]),
     "dtc_conv2d_f32_wgrad_workspace_size": (sz, [PConv, i32]),
     "dtc_conv2d_f32_wgrad": (i32, [PConv, vp, vp, vp, f32, i32, vp, sz, vp]),
+    "dtc_conv2d_f32_wgrad_sc_route_query": (i32, [PConv, i32]),
+    "dtc_conv2d_f32_wgrad_sc_workspace_size": (sz, [PConv, i32]),
+    "dtc_conv2d_f32_wgrad_sc": (i32, [PConv, vp, vp, vp, vp, vp, f32, i32, vp, sz, vp]),
     "dtc_conv2d_fwd_sc": (i32, [PConv, vp, vp, vp, vp, vp, vp, vp, vp]),
     "dtc_conv2d_dgrad_sc": (i32, [PConv, vp, vp, vp, vp, vp, vp]),
     "dtc_conv2d_wgrad_sc_workspace_size": (sz, [PConv]),

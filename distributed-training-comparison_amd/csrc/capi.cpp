@@ -417,6 +417,40 @@ int dtc_conv2d_f32_wgrad(const dtc_conv_desc* d, const float* x, const float* dy
                         S(stream));)
 }
 
+// The transition blocks' fused weight-gradient pair: conv_f32x_s2_wgrad (algo 1 where its predicate holds) or the
+// two conv_f32 weight gradients, each on the whole workspace (the splits dtc_conv2d_f32_wgrad(algo 0) runs)
+int dtc_conv2d_f32_wgrad_sc_route_query(const dtc_conv_desc* d, int algo) {
+  DTC_CHECK_ARG(desc_ok_f32_sc(d), "dtc_conv2d_f32_wgrad_sc_route_query: not a 3x3 pad-1 convolution conv_f32 takes");
+  DTC_CHECK_ARG(algo == 0 || algo == 1, "dtc_conv2d_f32_wgrad_sc_route_query: algo %d (0 exact, 1 split)", algo);
+  return conv_f32_wgrad_sc_route(shape_of(d), algo != 0);
+}
+
+size_t dtc_conv2d_f32_wgrad_sc_workspace_size(const dtc_conv_desc* d, int algo) {
+  if (!desc_ok_f32_sc(d) || (algo != 0 && algo != 1)) return 0;
+  const ConvShape s = shape_of(d);
+  if (conv_f32_wgrad_sc_route(s, algo != 0) == CONV_F32_SPLIT) return conv_f32x_s2_wgrad_workspace(s);
+  return std::max(f32_conv_workspace(s, CONV_WGRAD), f32_conv_workspace(sc_shape_of(s), CONV_WGRAD));
+}
+
+int dtc_conv2d_f32_wgrad_sc(const dtc_conv_desc* d, const float* x, const float* dy, const float* dsc, float* dw,
+                            float* dwsc, float scale, int algo, void* ws, size_t ws_bytes, void* stream) {
+  DTC_CHECK_ARG(d && x && dy && dsc && dw && dwsc, "dtc_conv2d_f32_wgrad_sc: null argument");
+  DTC_CHECK_ARG(desc_ok_f32_sc(d), "dtc_conv2d_f32_wgrad_sc: not a 3x3 pad-1 convolution conv_f32 takes");
+  DTC_CHECK_ARG(algo == 0 || algo == 1, "dtc_conv2d_f32_wgrad_sc: algo %d (0 exact, 1 split)", algo);
+  const ConvShape s = shape_of(d);
+  if (!ws) ws_bytes = 0;
+  if (conv_f32_wgrad_sc_route(s, algo != 0) == CONV_F32_SPLIT) {
+    GUARD(return conv_f32x_s2_wgrad(s, x, dy, dsc, dw, dwsc, scale, (float*)ws, ws_bytes, S(stream));)
+  }
+  DTC_CHECK_ARG(ws_bytes >= (size_t)s.K * 9 * s.C * 4,
+                "dtc_conv2d_f32_wgrad_sc: the exact kernels need a workspace of at least one slab, %zu bytes (given %zu)",
+                (size_t)s.K * 9 * s.C * 4, ws_bytes);
+  GUARD(
+    DTC_TRY(conv_f32(s, CONV_WGRAD, x, dy, nullptr, nullptr, nullptr, dw, 0, 0, scale, (float*)ws, ws_bytes, S(stream)));
+    return conv_f32(sc_shape_of(s), CONV_WGRAD, x, dsc, nullptr, nullptr, nullptr, dwsc, 0, 0, scale, (float*)ws,
+                    ws_bytes, S(stream));)
+}
+
 int dtc_conv2d_fwd_sc(const dtc_conv_desc* d, const uint16_t* x, const uint16_t* w, uint16_t* y, int64_t* stats,
                       const uint16_t* wsc, uint16_t* ysc, int64_t* stats_sc, void* stream) {
   DTC_CHECK_ARG(d && x && w && y && wsc && ysc, "dtc_conv2d_fwd_sc: null argument");

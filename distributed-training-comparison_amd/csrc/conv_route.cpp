@@ -102,6 +102,13 @@ int conv_f32_sc_route(const ConvShape& s, int pass, bool want_split, bool planes
                                                                                                 : CONV_F32_EXACT;
 }
 
+// The transition blocks' fused weight-gradient pair (conv1's dw + the shortcut's): the split-bf16 kernel
+// (conv_f32x_s2_wgrad) when the caller asks for it and its predicate accepts conv1's shape; it splits all three
+// operands itself, so no weight planes are involved. Else the exact pair, two conv_f32 weight gradients
+int conv_f32_wgrad_sc_route(const ConvShape& s, bool want_split) {
+  return want_split && conv_f32x_s2_wgrad_ok(s) ? CONV_F32_SPLIT : CONV_F32_EXACT;
+}
+
 static ConvRequest with_slab(const float* slab, size_t slab_bytes) {
   ConvRequest rq;
   rq.slab_bytes = slab ? slab_bytes : 0;

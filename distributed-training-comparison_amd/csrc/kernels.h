@@ -65,8 +65,9 @@ namespace dtc {
   X(COMM_TAIL_INLINE, comm_tail_inline, 1) /* the last bucket's all-reduce on the compute stream (no fork / join) */ \
   X(DGRAD_S2H, dgrad_s2h, 1)            /* stride-2 3x3 dgrad (+ shortcut) as a halo sub-pixel conv: 1 K <= 256, 2 all */ \
   X(HALO_SMALL, halo_small, 1)          /* halo FWD/DGRAD: 64x64 double-buffered tiles where they give <= 512 workgroups */ \
-  X(F32_SPLIT, f32_split, 0)            /* (plan time) fp32 executor: 3x3 s1 FWD/DGRAD on the split-bf16 kernel (conv_f32x); 2: WGRAD too; 3: + the transition blocks' FWD / DGRAD (conv_f32x_s2) */ \
-  X(F32X_S2_FWD, f32x_s2_fwd, 1)        /* conv_f32x_s2 FWD_SC: 1 where it measured faster than the exact pair, 2 every feasible geometry (to measure) */
+  X(F32_SPLIT, f32_split, 0)            /* (plan time) fp32 executor: 3x3 s1 FWD/DGRAD on the split-bf16 kernel (conv_f32x); 2: WGRAD too; 3: + the transition blocks' FWD / DGRAD (conv_f32x_s2); 4: + their WGRAD (conv_f32x_s2_wgrad) */ \
+  X(F32X_S2_FWD, f32x_s2_fwd, 1)        /* conv_f32x_s2 FWD_SC: 1 where it measured faster than the exact pair, 2 every feasible geometry (to measure) */ \
+  X(F32X_S2_WGRAD, f32x_s2_wgrad, 1)    /* conv_f32x_s2_wgrad: 1 where it measured faster than the exact pair, 2 every feasible geometry (to measure) */
 
 enum {
 #define DTC_OPT_ENUM(id, name, def) OPT_##id,
@@ -270,6 +271,19 @@ int conv_f32x_s2_dgrad(const ConvShape& s, const float* dy, const u16* wplanes, 
 // The fused pair's route (conv_route.cpp): CONV_F32_SPLIT when the split is asked for, both weights' planes exist and
 // conv_f32x_s2_ok holds; else CONV_F32_EXACT, the two conv_f32 launches per pass (FWD / DGRAD only)
 int conv_f32_sc_route(const ConvShape& s, int pass, bool want_split, bool planes);
+// Split-bf16 weight gradients of a projection block (conv_f32x_s2_wgrad.hip): conv1's (3x3 / stride 2 / pad 1) dw and
+// the 1x1 stride-2 shortcut's dwsc = scale * sum dsc (x) x in one launch, x, dy and dsc fp32 and split in the kernel.
+// Split-K over 32-position steps into fp32 slabs [split][K][10 C] summed by f32_wgrad_reduce; the splits are lowered
+// until `slab` holds them, and one split writes dw / dwsc itself. conv_f32x_s2_wgrad_ok: conv_f32x_s2_ok's geometry
+// family (even extents, output rows of 4 / 8 / 16 positions whose 32-position steps are whole rows or whole images,
+// C and K multiples of 64, tensors below 2 GiB). conv_f32x_s2_wgrad_workspace: the slab bytes it wants (0: one split).
+bool conv_f32x_s2_wgrad_ok(const ConvShape& s);
+size_t conv_f32x_s2_wgrad_workspace(const ConvShape& s);
+int conv_f32x_s2_wgrad(const ConvShape& s, const float* x, const float* dy, const float* dsc, float* dw, float* dwsc,
+                       float scale, float* slab, size_t slab_bytes, hipStream_t st, u64* ts = nullptr);
+// The fused weight-gradient pair's route (conv_route.cpp): CONV_F32_SPLIT when the split is asked for and
+// conv_f32x_s2_wgrad_ok holds (no weight planes needed); else CONV_F32_EXACT, the two conv_f32 weight gradients
+int conv_f32_wgrad_sc_route(const ConvShape& s, bool want_split);
 // Which kernel an fp32 pass runs on (conv_route.cpp): CONV_F32_SPLIT when the split is asked for (the executor:
 // option f32_split, 1 for FWD / DGRAD and 2 for WGRAD too; the C ABI: algo) and the pass's predicate holds
 // (conv_f32x_ok and the weight planes exist; WGRAD: conv_f32x_wgrad_ok); else CONV_F32_EXACT (conv_f32).

@@ -208,6 +208,8 @@ static void plan_workspace(Net& n, float bucket_cap_mb) {
       slab = std::max(slab, n.f32 ? f32_conv_workspace(s, m) : conv_route(s, m).slab_bytes);
     // option f32_split = 2: the split-bf16 weight gradient's slabs (the only value that may enlarge the slab)
     if (n.f32 && option_get(OPT_F32_SPLIT) >= 2 && conv_f32x_wgrad_ok(s)) slab = std::max(slab, conv_f32x_wgrad_workspace(s));
+    // 4: the transition blocks' fused weight gradient's (0 for any other shape; 3 plans what 2 does)
+    if (n.f32 && option_get(OPT_F32_SPLIT) >= 4 && conv_f32x_s2_wgrad_ok(s)) slab = std::max(slab, conv_f32x_s2_wgrad_workspace(s));
   };
   auto consider_batch = [&](const ConvShape& s) {  // a bucket's 3x3 stride-1 wgrads, 2..DTC_WG_BATCH per launch
     ConvRequest rq;

@@ -877,9 +877,17 @@ static int backward_body_f32(Net& n, const float* dlogits, float gs, const BwdCt
     DTC_TRY(cap(n, cp + ".dz1", G[4], st));
     DTC_TRY(bn_bwd_coef_apply(n, b.b1, G[4], n.at<float>(b.C1), dc1, nullptr, nullptr, nullptr, M, gs, st));
     DTC_TRY(cap(n, cp + ".dc1", dc1, st));
-    DTC_TRY(f32_wgrad(n, b.c1.s, in, dc1, n.gf(b.c1.pidx), gs, st));
+    // option f32_split = 4: a projection block's two weight gradients in one conv_f32x_s2_wgrad launch
+    const bool wgx = b.proj && conv_f32_wgrad_sc_route(b.c1.s, option_get(OPT_F32_SPLIT) >= 4) == CONV_F32_SPLIT;
+    if (wgx) {
+      PROF(2, conv_flops(b.c1.s) + conv_flops(b.sc.s),
+           conv_f32x_s2_wgrad(b.c1.s, in, dc1, dsc, n.gf(b.c1.pidx), n.gf(b.sc.pidx), gs, n.at<float>(p.SLAB),
+                              p.slab_bytes, st, ts));
+    } else {
+      DTC_TRY(f32_wgrad(n, b.c1.s, in, dc1, n.gf(b.c1.pidx), gs, st));
+    }
     if (b.proj) {
-      DTC_TRY(f32_wgrad(n, b.sc.s, in, dsc, n.gf(b.sc.pidx), gs, st));
+      if (!wgx) DTC_TRY(f32_wgrad(n, b.sc.s, in, dsc, n.gf(b.sc.pidx), gs, st));
       if (f32_sc_split(n, b, CONV_DGRAD)) {  // one launch, dx written once: no G[5] round trip
         if (n.capture) {  // (parity captures store the shortcut's own data gradient: computed for the capture only)
           DTC_TRY(f32_dgrad(n, b.sc.s, dsc, n.pf(b.sc.pidx), G[5], nullptr, st));

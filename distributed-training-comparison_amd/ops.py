@@ -244,6 +244,37 @@ def conv2d_wgrad_f32(x, dy, r, s, stride, pad, algo=0, scale=1.0, out=None, work
     return dw
 
 
+def conv2d_f32_wgrad_sc_route(desc, algo):
+    """dtc_conv2d_f32_wgrad_sc_route_query: which fp32 kernel ("exact": two conv_f32 weight gradients / "split": one
+    conv_f32x_s2_wgrad launch) the fused conv1 + shortcut weight-gradient entry point runs for conv1's `desc`. Host code."""
+    rc = lib.dtc_conv2d_f32_wgrad_sc_route_query(desc, algo)
+    if rc < 0:
+        call("dtc_conv2d_f32_wgrad_sc_route_query", desc, algo)  # raises with the library's message
+    return CONV_F32_KERNELS[rc]
+
+
+def conv2d_wgrad_sc_f32(x, dy, dsc, algo=0, scale=1.0, workspace=None):
+    """x [N,H,W,C], dy and dsc [N,H/2,W/2,K] fp32 -> (dw [K,3,3,C], dwsc [K,C]) fp32: the weight gradients of a
+    projection block's conv1 (3x3 stride 2 pad 1) and 1x1 stride-2 shortcut. algo 0: two conv_f32 launches; 1: one
+    split-bf16 launch where conv2d_f32_wgrad_sc_route says "split". `workspace` as conv2d_wgrad_f32's."""
+    require_cuda(x, dy, dsc)
+    N, H, W, Cc = x.shape
+    K = dy.shape[3]
+    if dsc.shape != dy.shape:
+        raise ValueError("conv2d_wgrad_sc_f32: dy and dsc must have one shape")
+    d = conv_desc(N, H, W, Cc, K, 3, 3, 2, 1)
+    dw = _out(None, (K, 3, 3, Cc), torch.float32, x.device, "conv2d_wgrad_sc_f32")
+    dwsc = _out(None, (K, Cc), torch.float32, x.device, "conv2d_wgrad_sc_f32")
+    if workspace is None:
+        workspace = torch.empty(max(int(lib.dtc_conv2d_f32_wgrad_sc_workspace_size(d, algo)), 16), dtype=torch.uint8,
+                                device=x.device)
+    require_cuda(workspace)
+    nb = workspace.numel() * workspace.element_size()
+    call("dtc_conv2d_f32_wgrad_sc", d, ptr(x), ptr(dy), ptr(dsc), ptr(dw), ptr(dwsc), scale, algo,
+         ptr(workspace) if nb else None, nb, stream_ptr())
+    return dw, dwsc
+
+
 def conv2d_dgrad_bn(dy, w, in_hw, stride, pad, ymask, x1, mean1, invstd1, x2=None, mean2=None, invstd2=None,
                     res=None, out=None):
     """conv2d_dgrad fused with bn_bwd_reduce (dtc_conv2d_dgrad_bn): returns (dz, acc1, acc2) where

@@ -29,7 +29,7 @@ from .nn import CrossEntropyLoss, ResNet18, SyncBatchNorm
 from .optim import LARS, SAM, SGD, Adam, AdamW, clip_grad_norm_
 from .parallel import DDP, DataParallel, PowerSGDState, barrier, bf16_compress_hook, powerSGD_hook
 
-FP32_CONV = ("exact", "split", "split-all", "split-s2")  # --fp32-conv: the value of option f32_split is the index
+FP32_CONV = ("exact", "split", "split-all", "split-s2", "split-full")  # --fp32-conv: the value of option f32_split is the index
 
 
 def load_config(argv=None, mode: str = "ddp"):
@@ -46,7 +46,8 @@ def load_config(argv=None, mode: str = "ddp"):
                    help="without --amp: exact = the f32-input MFMA convs; split = forward and data-gradient convs on "
                         "the bf16 MFMA from three bf16 planes per fp32 operand (fp32-grade results, option f32_split); "
                         "split-all = their weight gradients too (option f32_split = 2); split-s2 = also the transition "
-                        "blocks' conv1 + shortcut forward and data gradient (3)")
+                        "blocks' conv1 + shortcut forward and data gradient (3); split-full = also their two weight "
+                        "gradients, one launch (4): every conv of layers 1-4 on the bf16 MFMA")
     p.add_argument("--contain-test", action="store_true", default=False)
     if mode == "ddp":
         p.add_argument("--world-size", type=int, default=1, help="Total number of processes to run")

@@ -45,7 +45,8 @@ int dtc_install_crash_handler(void);
  * default 1), "dgrad_s2h" (stride-2 data gradient as a halo sub-pixel conv, default 1), "stem_direct"
  * (plan time: direct 3x3 stem conv, default 1; 0 = im2col + GEMM), "f32_split" (plan time: the fp32 executor's 3x3
  * stride-1 forward and data-gradient convs on the split-bf16 kernel, default 0; 2: their weight gradients too; 3: also
- * the transition blocks' conv1 + shortcut forward and data gradient, one split-bf16 launch each). */
+ * the transition blocks' conv1 + shortcut forward and data gradient, one split-bf16 launch each; 4: also their two
+ * weight gradients, one split-bf16 launch). */
 int dtc_set_option(const char* name, int value);
 int dtc_get_option(const char* name);
 
@@ -208,6 +209,23 @@ int dtc_conv2d_f32_wgrad_route_query(const dtc_conv_desc* d, int algo);
 size_t dtc_conv2d_f32_wgrad_workspace_size(const dtc_conv_desc* d, int algo);
 int dtc_conv2d_f32_wgrad(const dtc_conv_desc* d, const float* x, const float* dy, float* dw, float scale, int algo,
                          void* ws, size_t ws_bytes, void* stream);
+/* The transition blocks' weight-gradient pair on fp32 tensors: conv1's (the descriptor: 3x3 / stride 2 / pad 1, as for
+ * dtc_conv2d_f32_fwd_sc) dw[k][3][3][c] = scale * sum dy (x) x and the 1x1 shortcut's dwsc[k][c] = scale * sum dsc (x) x
+ * of the same input x; dy and dsc are [n][h/2][w/2][k] fp32.
+ * algo 0, or algo 1 where dtc_conv2d_f32_wgrad_sc_route_query answers DTC_CONV_F32_EXACT: the two exact weight
+ * gradients, bit-identical to two dtc_conv2d_f32_wgrad(algo 0) calls on their default workspaces; needs a workspace of
+ * at least k*9*c*4 bytes (DTC_EINVAL otherwise).
+ * algo 1 where it answers DTC_CONV_F32_SPLIT (even h and w, output rows 4 / 8 / 16 wide whose 32-position steps are
+ * whole rows or whole images, c and k multiples of 64, tensors below 2 GiB): ONE launch of the split-bf16 kernel, all
+ * three operands split in the kernel, x read once, element-wise error below 2^-22 of sum |x||dy|; split-K slabs
+ * [split][k][10 c] reduced in a fixed order (bit-identical run to run). A workspace shorter than
+ * dtc_conv2d_f32_wgrad_sc_workspace_size lowers the number of splits; the kernel runs with none at all (one split).
+ * The conditions are necessary, not sufficient: small problems with 16-wide output rows answer DTC_CONV_F32_EXACT,
+ * because the fused launch measured no faster there (option "f32x_s2_wgrad" = 2 lifts that limit, for measuring). */
+int dtc_conv2d_f32_wgrad_sc_route_query(const dtc_conv_desc* d, int algo);
+size_t dtc_conv2d_f32_wgrad_sc_workspace_size(const dtc_conv_desc* d, int algo);
+int dtc_conv2d_f32_wgrad_sc(const dtc_conv_desc* d, const float* x, const float* dy, const float* dsc, float* dw,
+                            float* dwsc, float scale, int algo, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------ batch norm (training)
  * Replaces nn.BatchNorm2d train-mode forward/backward (net.py:21,25,37,92) with the F.relu and

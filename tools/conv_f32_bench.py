@@ -1,6 +1,7 @@
 """Time the fp32 3x3 stride-1 convs of ResNet-18 (forward, data gradient and weight gradient) on the exact kernel
 (conv_f32, algo 0) and on the split-bf16 kernels (conv_f32x / conv_f32x_wgrad, algo 1), interleaved in one process;
-then the transition blocks' conv1 + shortcut pair (fwd_sc / dgrad_sc: two conv_f32 launches against conv_f32x_s2).
+then the transition blocks' conv1 + shortcut pair (fwd_sc / dgrad_sc: two conv_f32 launches against conv_f32x_s2;
+wgrad_sc: the two conv_f32 weight gradients against the one conv_f32x_s2_wgrad launch, its reduces included).
 
 As tools/conv_bench.py: each (layer, pass, algo) is captured ITERS times into a graph on preallocated buffers (raw
 C-ABI calls), so a replay measures device time only; ROUNDS interleaved rounds per case. Prints the median us, the
@@ -50,9 +51,10 @@ def report(label, pname, us, flops, note=""):
           f"{flops / m[1] / 1e6:6.1f} {m[0] / m[1]:11.2f}{note}", flush=True)
 
 
-def transition_cases(dtc, cases, iters, rounds):
+def transition_cases(dtc, cases, iters, rounds, passes=(("fwd_sc", 0), ("dgrad_sc", 1))):
     """conv1 (3x3 stride 2) + the 1x1 stride-2 shortcut of a transition block: algo 0 is the exact pair (two conv_f32
-    launches per call, what the executor pays), algo 1 the one conv_f32x_s2 launch."""
+    launches per call, what the executor pays), algo 1 the one conv_f32x_s2 / conv_f32x_s2_wgrad launch (wgrad_sc: each
+    side on the workspace its size query asks for)."""
     ops, nat = dtc.ops, dtc._native
     dev, P_ = torch.device("cuda:0"), nat.ptr
     geo = {n: (h, c, k) for n, h, c, k in TRANSITIONS}
@@ -67,8 +69,26 @@ def transition_cases(dtc, cases, iters, rounds):
         st, st_sc = ops.new_stats(K, dev), ops.new_stats(K, dev)
         d = ops.conv_desc(B, H, H, C, K, 3, 3, 2, 1)
         flops = 2.0 * B * (H // 2) ** 2 * C * 10 * K
-        for pname, mode in (("fwd_sc", 0), ("dgrad_sc", 1)):
+        dw, dwsc = torch.empty(K, 3, 3, C, device=dev), torch.empty(K, C, device=dev)
+        wsz = {a: int(nat.lib.dtc_conv2d_f32_wgrad_sc_workspace_size(d, a)) for a in (0, 1)}
+        nat.call("dtc_set_option", b"f32x_s2_wgrad", 2)  # (the buffer holds the fused kernel's slab where it is refused too)
+        ws = torch.empty(max(wsz[0], int(nat.lib.dtc_conv2d_f32_wgrad_sc_workspace_size(d, 1)), 16), dtype=torch.uint8,
+                         device=dev)
+        nat.call("dtc_set_option", b"f32x_s2_wgrad", 1)
+        for pname, mode in passes:
             note = ""
+            if mode == 2:
+                if ops.conv2d_f32_wgrad_sc_route(d, 1) != "split":  # refused by default: timed with the predicate opened
+                    nat.call("dtc_set_option", b"f32x_s2_wgrad", 2)
+                    note = "  (refused by default)"
+                assert ops.conv2d_f32_wgrad_sc_route(d, 1) == "split", case
+                wsz[1] = int(nat.lib.dtc_conv2d_f32_wgrad_sc_workspace_size(d, 1))
+                fns = {algo: lambda algo=algo: nat.call(
+                    "dtc_conv2d_f32_wgrad_sc", d, P_(x), P_(dy), P_(dsc), P_(dw), P_(dwsc), 1.0, algo,
+                    P_(ws) if wsz[algo] else None, wsz[algo], nat.stream_ptr()) for algo in (0, 1)}
+                report(f"{name} B={B}", pname, time_interleaved(fns, iters, rounds), flops, note)
+                nat.call("dtc_set_option", b"f32x_s2_wgrad", 1)
+                continue
             if ops.conv2d_f32_sc_route(d, mode, 1) != "split":  # refused by default: timed with the predicate opened
                 nat.call("dtc_set_option", b"f32x_s2_fwd", 2)
                 note = "  (refused by default)"
@@ -88,9 +108,11 @@ def transition_cases(dtc, cases, iters, rounds):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--cases", default="l1:256,l2:256,l3:256,l4:256,l3:32,l4:32", help="layer:batch, ...")
+    ap.add_argument("--cases", default="l1:256,l2:256,l3:256,l4:256,l3:32,l4:32", help="layer:batch, ...; empty: none")
     ap.add_argument("--sc-cases", default="t2:256,t3:256,t4:256,t2:32,t3:32,t4:32",
                     help="transition blocks (conv1 + shortcut in one call), name:batch, ...; empty: none")
+    ap.add_argument("--wgrad-sc-cases", default=",".join(f"t{l}:{b}" for b in (256, 128, 64, 32) for l in (2, 3, 4)),
+                    help="transition blocks' fused weight gradients (wgrad_sc rows), name:batch, ...; empty: none")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
     args = ap.parse_args()
@@ -100,7 +122,7 @@ def main():
     geo = {n: (h, c) for n, h, c in LAYERS}
     print(f"{'case':10s} {'pass':8s} {'exact us (min..max)':>26s} {'TF/s':>6s} {'split us (min..max)':>26s} {'TF/s':>6s} "
           f"{'exact/split':>11s}")
-    for case in args.cases.split(","):
+    for case in filter(None, args.cases.split(",")):
         name, B = case.split(":")[0], int(case.split(":")[1])
         H, C = geo[name]
         x = torch.randn(B, H, H, C, device=dev)
@@ -132,6 +154,8 @@ def main():
         del x, w, wpl, out, dw, ws
     if args.sc_cases:
         transition_cases(dtc, args.sc_cases, args.iters, args.rounds)
+    if args.wgrad_sc_cases:
+        transition_cases(dtc, args.wgrad_sc_cases, args.iters, args.rounds, (("wgrad_sc", 2),))
 
 
 if __name__ == "__main__":
