@@ -32,7 +32,8 @@
 //   [0, 110592)        three halo images (plane 0, 1, 2) of 288 rows x 128 B
 //   [110592, 159744)   two weight buffers of three planes x 64 rows x 128 B
 //   (epilogue: [0, 2048) the BN statistics staging [4 waves][64 channels][2])
-// Registers: 357 (FWD) / 360 (DGRAD) of 512 (256 VGPR + 101 / 104 AGPR); no scratch.
+// Registers: 357 (FWD) / 360 (DGRAD) of 512 (256 VGPR + 101 / 104 AGPR); no scratch. The general-geometry instances
+// (GEN = 1, at the kernel): the same LDS map, 361 / 364 registers, no scratch.
 #include "common.h"
 #include "f32_split.h"
 #include "flat.h"
@@ -61,6 +62,9 @@ struct FxParams {
   uint32_t src_bytes;
   int rows, imgs, hb, nh, tiles_y, tiles_a, nchunk, xcd_remap;
   u64* ts;
+  // general geometry (GEN): a tile is rs rows x one seg-column segment of one image, each tile row padded to segp slots
+  int seg, segp, rs, spr, tpi;
+  FastDiv fd_tpi, fd_spr, fd_segp, fd_w2;
 };
 
 // ---------------------------------------------------------------- the split
@@ -103,7 +107,18 @@ __device__ __forceinline__ int fx_frag_pixel(int j, int W) {
   return j;
 }
 
-template <int PASS>
+// GEN = 1, the general (row segment) geometry of tile_common.h, for rows the classic tile does not cover (224 / 112 /
+// 56 / 28 / 14 / 7 wide): a tile is rs rows x one seg-column segment (seg = row_segment(W)) of ONE image, its halo the
+// (rs + 2) x (seg + 2) box around it, whose border is padding only where it leaves the image (beside another segment
+// or tile it holds that neighbour's pixels). Slots: every tile row is padded to segp = seg rounded up to 16 slots, slot
+// l = row l / segp, column l % segp, valid iff the column is below seg and the row below rs. A 16-pixel B fragment is
+// then 16 consecutive pixels of one tile row = 16 consecutive halo rows, the conflict-free case of the classic 16- /
+// 32-wide rows (a dense l / seg mapping would let a fragment straddle two rows of a 56- or 28-wide segment, whose halo
+// rows collide mod 8). A padded slot reads halo rows of its own (in capacity; every row of the images is written each
+// chunk), and an MFMA column only feeds its own output column: its result is never stored nor counted.
+// Addressing: the buffer descriptor covers the tile's image only (base src + n0 H W Cin), so the 32-bit offsets hold
+// for tensors past 2 GiB; output, residual and statistics offsets are 64-bit.
+template <int PASS, int GEN>
 __global__ void __launch_bounds__(256) conv_f32x_kernel(const FxParams p) {
   constexpr int FM = FX_BM / 16;        // 4 channel fragments per wave
   constexpr int FN = FX_BN / (4 * 16);  // 2 pixel fragments per wave
@@ -117,15 +132,18 @@ __global__ void __launch_bounds__(256) conv_f32x_kernel(const FxParams p) {
   if (p.xcd_remap && gridDim.x >= 16) bid = (int)xcd_grouped_id(blockIdx.x, gridDim.x);
   const int ta = bid % p.tiles_a, tb = bid / p.tiles_a;
   const int a0 = ta * FX_BM;
-  int n0, y0;
-  if (p.imgs == 1) {
+  int n0, y0, q0 = 0;
+  if constexpr (GEN) {
+    seg_tile_origin(tb, p.tpi, p.fd_tpi, p.spr, p.fd_spr, p.rs, p.seg, n0, y0, q0);
+    n0 = __builtin_amdgcn_readfirstlane(n0);  // (the descriptor below is per tile: keep its base in SGPRs)
+  } else if (p.imgs == 1) {
     n0 = tb / p.tiles_y;
     y0 = (tb - n0 * p.tiles_y) * p.rows;
   } else {
     n0 = tb * p.imgs;
     y0 = 0;
   }
-  const int W2 = p.W + 2;
+  const int W2 = (GEN ? p.seg : p.W) + 2;
   const int px0 = (n0 * p.H + y0) * p.W;
   const int M = p.N * p.H * p.W;
   const int lrow = lane >> 3, pc = lane & 7;
@@ -155,13 +173,19 @@ __global__ void __launch_bounds__(256) conv_f32x_kernel(const FxParams p) {
   };
 
   // ---- halo units: unit u of this thread is halo row (u 256 + t) / 8, channels 8 ((u 256 + t) % 8) .. + 7
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)p.src, 0, p.src_bytes, 0x00020000);
+  const float* const sbase = GEN ? p.src + (size_t)n0 * p.H * p.W * p.Cin : p.src;  // GEN: src_bytes is one image
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)sbase, 0, p.src_bytes, 0x00020000);
   uint32_t hoff[FX_UNITS];  // byte offset of the unit in chunk 0 (DMA_OOB: a padded pixel, loads zeros)
 #pragma unroll
   for (int u = 0; u < FX_UNITS; ++u) {
     const int hr = (u * 256 + t) >> 3;
     uint32_t off = DMA_OOB;
-    if (hr < p.nh) {
+    if (GEN && hr < p.nh) {  // halo pixel (hy, hx) of the box around rows y0.., columns q0.. of image n0
+      const int hy = (int)fdiv((uint32_t)hr, p.fd_w2), hx = hr - hy * W2;
+      const int y = y0 + hy - 1, x = q0 + hx - 1;
+      if ((unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W)
+        off = (uint32_t)(((y * p.W + x) * p.Cin + pc * 8) * 4);
+    } else if (hr < p.nh) {
       const int i = hr / p.hb, rem = hr - i * p.hb;
       const int hy = rem / W2, hx = rem - hy * W2;
       const int n = n0 + i, y = y0 + hy - 1, x = hx - 1;
@@ -194,14 +218,20 @@ __global__ void __launch_bounds__(256) conv_f32x_kernel(const FxParams p) {
   // ---- B fragments: halo row of each of this lane's pixels at tap (0, 0), then every tap's LDS offset
   const int bcol0 = wave * (FX_BN / 4);
   const int spx = p.rows * p.W;  // pixels per image slice
-  const int fpx = fx_frag_pixel(lane & 15, p.W);
+  const int fpx = GEN ? lane & 15 : fx_frag_pixel(lane & 15, p.W);
   uint32_t boff[9][FN];
 #pragma unroll
   for (int j = 0; j < FN; ++j) {
     const int l = bcol0 + j * 16 + fpx;
-    const int i = l / spx, rem = l - i * spx;
-    const int y = rem / p.W, x = rem - y * p.W;
-    const int hbr = i * p.hb + y * W2 + x;
+    int hbr;
+    if constexpr (GEN) {  // (a padded slot's rows run past the box: held within the images' capacity for every tap)
+      const int y = (int)fdiv((uint32_t)l, p.fd_segp), x = l - y * p.segp;
+      hbr = min(y * W2 + x, FX_HCAP - 1 - 2 * W2 - 2);
+    } else {
+      const int i = l / spx, rem = l - i * spx;
+      const int y = rem / p.W, x = rem - y * p.W;
+      hbr = i * p.hb + y * W2 + x;
+    }
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap) boff[tap][j] = halo_frag_off(hbr + halo_tap_shift<1>(tap, W2, 0), lane);
   }
@@ -296,11 +326,20 @@ __global__ void __launch_bounds__(256) conv_f32x_kernel(const FxParams p) {
     for (int v = 0; v < 4; ++v) s4[i][v] = q4[i][v] = 0.f;
 #pragma unroll
   for (int j = 0; j < FN; ++j) {
-    const int pix = px0 + bcol0 + j * 16 + fpx;
-    if (pix >= M) continue;  // a padded image slot of the last tile
+    size_t pix;
+    if constexpr (GEN) {
+      const int l = bcol0 + j * 16 + fpx;
+      const int y = (int)fdiv((uint32_t)l, p.fd_segp), x = l - y * p.segp;
+      if (x >= p.seg || y >= p.rs) continue;  // a padded slot
+      pix = ((size_t)n0 * p.H + y0 + y) * p.W + q0 + x;
+    } else {
+      const int pi = px0 + bcol0 + j * 16 + fpx;
+      if (pi >= M) continue;  // a padded image slot of the last tile
+      pix = (size_t)pi;
+    }
 #pragma unroll
     for (int i = 0; i < FM; ++i) {
-      const size_t o = (size_t)pix * p.Cout + a0 + i * 16 + rq;
+      const size_t o = pix * p.Cout + a0 + i * 16 + rq;
       f32x4 d = tot[i][j] + lo[i][j];
       if constexpr (PASS == FX_DGRAD) {
         if (p.res) d += *(const f32x4*)(p.res + o);
@@ -349,18 +388,52 @@ static bool fx_geometry(const ConvShape& s, TileSplit& t, int& hb, int& nh) {
   return nh <= FX_HCAP && (uint64_t)s.N * s.H * s.W * std::max(s.C, s.K) * 4 < (1ull << 31);
 }
 
+// General geometry of a feasible shape: rs rows x one seg-column segment of one image per tile, every tile row
+// padded to segp slots (the kernel's comment); nh halo rows
+struct FxGen {
+  SegTile g;
+  int segp = 0, nh = 0;
+};
+static bool fx_geometry_gen(const ConvShape& s, FxGen& f) {
+  if (!conv3x3_ok(s, 1)) return false;
+  const int seg = row_segment(s.W);
+  if (seg == 0) return false;
+  f.segp = (seg + 15) / 16 * 16;
+  f.g = seg_tile(s.H, s.W, seg, rows_dividing(s.H, FX_BN / f.segp));
+  f.nh = halo_box_s1(f.g.rs, seg);
+  // one image within the per-tile buffer descriptor (32-bit byte offsets; DMA_OOB must lie outside it), and the
+  // tile index within FastDiv's 31 bits
+  const int64_t cmax = std::max(s.C, s.K);
+  return f.nh <= FX_HCAP && (int64_t)s.H * s.W * cmax * 4 < (1ll << 31) &&
+         (int64_t)s.N * f.g.tpi * (cmax / FX_BM) < (1ll << 31);
+}
+// Option f32x_gen: 0 classic geometry only; 1 the general tiles that measured faster than conv_f32;
+// 2 every feasible one (for measuring, and the small test shapes)
+static bool fx_gen_admitted(const ConvShape& s, const FxGen& f) {
+  const int lvl = option_get(OPT_F32X_GEN);
+  if (lvl >= 2) return true;
+  // measured: tiles of 112 (56- / 28-wide segments) and 98 (14-wide rows) pixels in the 128 slots are
+  // 1.5-2.5x faster than conv_f32 at every batch; the 49-pixel tile of 7-wide rows is slower from batch 256 on.
+  // Fills between the two were not measured: refused
+  return lvl == 1 && f.g.rs * f.g.seg >= 98;
+}
+
 bool conv_f32x_ok(const ConvShape& s) {
   TileSplit t;
   int hb, nh;
-  return fx_geometry(s, t, hb, nh);
+  if (fx_geometry(s, t, hb, nh)) return true;
+  FxGen f;
+  return option_get(OPT_F32X_GEN) != 0 && fx_geometry_gen(s, f) && fx_gen_admitted(s, f);
 }
 
 int conv_f32x(const ConvShape& s, int mode, const float* src, const u16* wplanes, int64_t wstride, float* out,
               const float* res, int64_t* stats, hipStream_t st, u64* ts) {
   TileSplit t;
+  FxGen f;
   int hb = 0, nh = 0;
   DTC_CHECK_ARG(mode == CONV_FWD || mode == CONV_DGRAD, "conv_f32x: forward and data gradient only");
-  DTC_CHECK_ARG(fx_geometry(s, t, hb, nh), "conv_f32x: unsupported shape");
+  const bool gen = !fx_geometry(s, t, hb, nh);  // the instance follows the geometry: classic where it holds
+  DTC_CHECK_ARG(!gen || fx_geometry_gen(s, f), "conv_f32x: unsupported shape");
   DTC_CHECK_ARG(src && wplanes && out && wstride >= (int64_t)s.K * 9 * s.C && wstride % 8 == 0 &&
                     aligned(wplanes, 16) && aligned(src, 16) && aligned(out, 16) && (!res || aligned(res, 16)),
                 "conv_f32x: null / misaligned argument or weight planes closer than one filter bank");
@@ -371,17 +444,34 @@ int conv_f32x(const ConvShape& s, int mode, const float* src, const u16* wplanes
   p.N = s.N; p.H = s.H; p.W = s.W; p.C = s.C;
   p.Cin = mode == CONV_FWD ? s.C : s.K;
   p.Cout = mode == CONV_FWD ? s.K : s.C;
-  p.src_bytes = (uint32_t)((uint64_t)s.N * s.H * s.W * p.Cin * 4);
-  p.rows = t.rows; p.imgs = t.imgs; p.hb = hb; p.nh = nh;
-  p.tiles_y = s.H / t.rows;
   p.tiles_a = p.Cout / FX_BM;
   p.nchunk = p.Cin / 64;
   p.xcd_remap = option_get(OPT_XCD_REMAP);
   p.ts = ts;
-  const int tiles_b = t.imgs == 1 ? s.N * p.tiles_y : (s.N + t.imgs - 1) / t.imgs;
+  int64_t tiles_b;
+  if (gen) {
+    p.src_bytes = (uint32_t)((uint64_t)s.H * s.W * p.Cin * 4);  // one image: the descriptor is made per tile
+    p.nh = f.nh;
+    p.seg = f.g.seg; p.segp = f.segp; p.rs = f.g.rs; p.spr = f.g.spr; p.tpi = f.g.tpi;
+    p.fd_tpi = make_fastdiv(f.g.tpi);
+    p.fd_spr = make_fastdiv(f.g.spr);
+    p.fd_segp = make_fastdiv(f.segp);
+    p.fd_w2 = make_fastdiv(f.g.seg + 2);
+    tiles_b = (int64_t)s.N * f.g.tpi;
+  } else {
+    p.src_bytes = (uint32_t)((uint64_t)s.N * s.H * s.W * p.Cin * 4);
+    p.rows = t.rows; p.imgs = t.imgs; p.hb = hb; p.nh = nh;
+    p.tiles_y = s.H / t.rows;
+    tiles_b = t.imgs == 1 ? s.N * p.tiles_y : (s.N + t.imgs - 1) / t.imgs;
+  }
   const dim3 grid((unsigned)(tiles_b * p.tiles_a), 1);
-  if (mode == CONV_FWD) DTC_KLAUNCH(conv_f32x_kernel<FX_FWD>, grid, dim3(256), 0, st, p);
-  else DTC_KLAUNCH(conv_f32x_kernel<FX_DGRAD>, grid, dim3(256), 0, st, p);
+  if (mode == CONV_FWD) {
+    if (gen) DTC_KLAUNCH((conv_f32x_kernel<FX_FWD, 1>), grid, dim3(256), 0, st, p);
+    else DTC_KLAUNCH((conv_f32x_kernel<FX_FWD, 0>), grid, dim3(256), 0, st, p);
+  } else {
+    if (gen) DTC_KLAUNCH((conv_f32x_kernel<FX_DGRAD, 1>), grid, dim3(256), 0, st, p);
+    else DTC_KLAUNCH((conv_f32x_kernel<FX_DGRAD, 0>), grid, dim3(256), 0, st, p);
+  }
   DTC_LAUNCH_CHECK();
   return 0;
 }

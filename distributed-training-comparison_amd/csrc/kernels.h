@@ -67,7 +67,8 @@ namespace dtc {
   X(HALO_SMALL, halo_small, 1)          /* halo FWD/DGRAD: 64x64 double-buffered tiles where they give <= 512 workgroups */ \
   X(F32_SPLIT, f32_split, 0)            /* (plan time) fp32 executor: 3x3 s1 FWD/DGRAD on the split-bf16 kernel (conv_f32x); 2: WGRAD too; 3: + the transition blocks' FWD / DGRAD (conv_f32x_s2); 4: + their WGRAD (conv_f32x_s2_wgrad) */ \
   X(F32X_S2_FWD, f32x_s2_fwd, 1)        /* conv_f32x_s2 FWD_SC: 1 where it measured faster than the exact pair, 2 every feasible geometry (to measure) */ \
-  X(F32X_S2_WGRAD, f32x_s2_wgrad, 1)    /* conv_f32x_s2_wgrad: 1 where it measured faster than the exact pair, 2 every feasible geometry (to measure) */
+  X(F32X_S2_WGRAD, f32x_s2_wgrad, 1)    /* conv_f32x_s2_wgrad: 1 where it measured faster than the exact pair, 2 every feasible geometry (to measure) */ \
+  X(F32X_GEN, f32x_gen, 0)              /* conv_f32x general (row-segment) tiles, the 224x224 geometry: 0 classic rows only, 1 where it measured faster than conv_f32, 2 every feasible geometry (to measure) */
 
 enum {
 #define DTC_OPT_ENUM(id, name, def) OPT_##id,
@@ -241,7 +242,9 @@ int f32_wgrad_reduce(const float* slab, int splits, int K, int RSC, int ncols, i
 // operand (six plane products, fp32 accumulation): fp32-grade results. src fp32 NHWC (x / dy), wplanes three bf16
 // KRSC planes wstride elements apart (f32_split3 of the fp32 weight), out fp32 (y / dx); FWD: optional BN
 // statistics as conv_f32's; DGRAD: optional fp32 residual. conv_f32x_ok: rows of 4 / 8 / 16 / 32 pixels whose 128-
-// pixel tiles are whole rows or whole images, C and K multiples of 64, tensors below 2 GiB.
+// pixel tiles are whole rows or whole images, C and K multiples of 64, tensors below 2 GiB. With option f32x_gen also
+// the general geometry (a tile is rows of one row_segment(W)-column segment of one image: 224 / 112 / 56 / 28 / 14 / 7
+// wide rows): one image below 2 GiB, tensors of any size; 1: the tiles that measured faster than conv_f32, 2: all.
 bool conv_f32x_ok(const ConvShape& s);
 int conv_f32x(const ConvShape& s, int mode, const float* src, const u16* wplanes, int64_t wstride, float* out,
               const float* res, int64_t* stats, hipStream_t st, u64* ts = nullptr);

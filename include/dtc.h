@@ -46,7 +46,8 @@ int dtc_install_crash_handler(void);
  * (plan time: direct 3x3 stem conv, default 1; 0 = im2col + GEMM), "f32_split" (plan time: the fp32 executor's 3x3
  * stride-1 forward and data-gradient convs on the split-bf16 kernel, default 0; 2: their weight gradients too; 3: also
  * the transition blocks' conv1 + shortcut forward and data gradient, one split-bf16 launch each; 4: also their two
- * weight gradients, one split-bf16 launch). */
+ * weight gradients, one split-bf16 launch), "f32x_gen" (the split-bf16 forward / data gradient on row-segment tiles,
+ * the 224x224 model's rows: default 0 off, 1 where measured faster, 2 wherever feasible; see the fp32 convolution). */
 int dtc_set_option(const char* name, int value);
 int dtc_get_option(const char* name);
 
@@ -159,7 +160,10 @@ int dtc_conv2d_wgrad_batch(const dtc_conv_desc* d, int n, const uint16_t* const*
  *   DTC_CONV_F32_SPLIT (1)  3x3 / stride 1 / pad 1 with rows of 4 / 8 / 16 / 32 pixels and c, k multiples of 64: the
  *     bf16 MFMA on three bf16 planes per fp32 operand, six plane products, fp32 accumulation (element-wise error
  *     below 2^-22 of sum |x||w|); w is the filter's three planes [3][k*r*s*c] as dtc_f32_split3 writes them. For any
- *     other descriptor algo 1 runs the exact kernel, and w is the fp32 filter.
+ *     other descriptor algo 1 runs the exact kernel, and w is the fp32 filter. Option "f32x_gen" (default 0) widens
+ *     what algo 1 serves to the general geometry -- rows of any width up to 64 or a multiple of 64 / 56 / 32 pixels
+ *     (224 / 112 / 56 / 28 / 14 / 7), one image below 2 GiB, tensors of any size: 1 where the split kernel measured
+ *     faster than the exact one, 2 wherever it is feasible (for measuring). The route query follows the option.
  * dtc_conv2d_f32_route_query (host only) returns which of the two a descriptor, pass (DTC_CONV_FWD / DTC_CONV_DGRAD)
  * and algo run -- and so which form of w the call takes -- or a negative value for a descriptor or pass neither
  * serves. stats (FWD, optional): the BN statistics of the fp32 output, as dtc_conv2d_fwd's. res (DGRAD, optional):

@@ -2,6 +2,8 @@
 (conv_f32, algo 0) and on the split-bf16 kernels (conv_f32x / conv_f32x_wgrad, algo 1), interleaved in one process;
 then the transition blocks' conv1 + shortcut pair (fwd_sc / dgrad_sc: two conv_f32 launches against conv_f32x_s2;
 wgrad_sc: the two conv_f32 weight gradients against the one conv_f32x_s2_wgrad launch, its reduces included).
+--gen-cases: the same forward / data gradient at the 224x224 model's rows (g1 .. g4: 224 / 112 / 56 / 28 wide), which
+the split kernel serves on its general (row-segment) tiles under option f32x_gen; their weight gradient stays exact.
 
 As tools/conv_bench.py: each (layer, pass, algo) is captured ITERS times into a graph on preallocated buffers (raw
 C-ABI calls), so a replay measures device time only; ROUNDS interleaved rounds per case. Prints the median us, the
@@ -17,6 +19,8 @@ import torch  # noqa: E402
 import dtc_import  # noqa: E402
 
 LAYERS = [("l1", 32, 64), ("l2", 16, 128), ("l3", 8, 256), ("l4", 4, 512)]  # (name, H = W, C = K)
+GEN_LAYERS = [("g1", 224, 64), ("g2", 112, 128), ("g3", 56, 256), ("g4", 28, 512),  # the 224x224 model's layers 1-4
+              ("g5", 14, 512), ("g6", 7, 512)]  # (not in the default cases) narrower rows: 98 and 49 of a tile's 128 slots
 TRANSITIONS = [("t2", 32, 64, 128), ("t3", 16, 128, 256), ("t4", 8, 256, 512)]  # (name, H = W in, C, K): layers 2-4, block 0
 
 
@@ -113,18 +117,26 @@ def main():
                     help="transition blocks (conv1 + shortcut in one call), name:batch, ...; empty: none")
     ap.add_argument("--wgrad-sc-cases", default=",".join(f"t{l}:{b}" for b in (256, 128, 64, 32) for l in (2, 3, 4)),
                     help="transition blocks' fused weight gradients (wgrad_sc rows), name:batch, ...; empty: none")
+    ap.add_argument("--gen-cases", default=",".join(f"g{l}:{b}" for b in (32, 128) for l in (1, 2, 3, 4)),
+                    help="general-geometry rows (fwd / dgrad under option f32x_gen), name:batch, ...; empty: none")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
     args = ap.parse_args()
     dtc = dtc_import.load()
     ops, nat = dtc.ops, dtc._native
     dev = torch.device("cuda:0")
-    geo = {n: (h, c) for n, h, c in LAYERS}
+    geo = {n: (h, c) for n, h, c in LAYERS + GEN_LAYERS}
     print(f"{'case':10s} {'pass':8s} {'exact us (min..max)':>26s} {'TF/s':>6s} {'split us (min..max)':>26s} {'TF/s':>6s} "
           f"{'exact/split':>11s}")
-    for case in filter(None, args.cases.split(",")):
+    for case in filter(None, (args.cases + "," + args.gen_cases).split(",")):
         name, B = case.split(":")[0], int(case.split(":")[1])
         H, C = geo[name]
+        gen, note = name.startswith("g"), ""
+        if gen:  # timed with every feasible general tile admitted; the note says what the default rule (1) does
+            nat.call("dtc_set_option", b"f32x_gen", 1)
+            if ops.conv2d_f32_route(ops.conv_desc(B, H, H, C, C, 3, 3, 1, 1), 0, 1) != "split":
+                note = "  (refused at f32x_gen = 1)"
+            nat.call("dtc_set_option", b"f32x_gen", 2)
         x = torch.randn(B, H, H, C, device=dev)
         w = torch.randn(C, 3, 3, C, device=dev) * 0.05
         wpl = ops.f32_split3(w)
@@ -136,7 +148,7 @@ def main():
         dw = torch.empty(C, 3, 3, C, device=dev)
         wsz = {a: int(nat.lib.dtc_conv2d_f32_wgrad_workspace_size(d, a)) for a in (0, 1)}
         ws = torch.empty(max(wsz.values()), dtype=torch.uint8, device=dev)
-        for pname, mode in (("fwd", 0), ("dgrad", 1), ("wgrad", 2)):
+        for pname, mode in (("fwd", 0), ("dgrad", 1), ("wgrad", 2))[:2 if gen else 3]:
             assert (ops.conv2d_f32_wgrad_route(d, 1) if mode == 2 else ops.conv2d_f32_route(d, mode, 1)) == "split", case
             fns = {}
             for algo, wt in ((0, w), (1, wpl)):
@@ -150,7 +162,8 @@ def main():
                     fns[algo] = lambda algo=algo, wt=wt: nat.call("dtc_conv2d_f32_dgrad", d, P_(x), P_(wt), P_(out),
                                                                   None, algo, None, 0, nat.stream_ptr())
             us = time_interleaved(fns, args.iters, args.rounds)
-            report(f"{name} B={B}", pname, us, flops)
+            report(f"{name} B={B}", pname, us, flops, note)
+        nat.call("dtc_set_option", b"f32x_gen", 0)
         del x, w, wpl, out, dw, ws
     if args.sc_cases:
         transition_cases(dtc, args.sc_cases, args.iters, args.rounds)
