@@ -36,6 +36,9 @@
 // Registers: 254 of the 256 a wave has at 512 threads per workgroup (254 VGPR + 0 AGPR: 144 accumulators, 32 held
 // operands, 36 plane fragments), 92 SGPR; no scratch. Two LDS stages because the registers hold one step of operands.
 // Measured: 1.8-2.9x conv_f32's weight gradient at batch 256, 1.1-1.2x at batch 32.
+// Two instances (-Rpass-analysis=kernel-resource-usage): the classic one above (GEN = 0: 254 VGPR + 0 AGPR, 92 SGPR, no
+// scratch) and the general geometry's (GEN = 1, at the kernel: 252 VGPR + 0 AGPR, 106 SGPR, no scratch; the same LDS
+// map), measured 2.0-3.3x conv_f32's weight gradient at rows of 224 / 112 / 56 / 28 / 14 / 7.
 #include "common.h"
 #include "f32_split.h"
 #include "flat.h"
@@ -63,6 +66,10 @@ struct XwParams {
   int spimg;               // steps per image (imgs == 1)
   int nsteps, steps_per_split;
   u64* ts;
+  // general geometry (GEN): a step is `rows` rows x one seg-column segment of one image, spr segments per row, tpi
+  // steps per image; x_bytes / dy_bytes are ONE image (the descriptors are made per step)
+  int seg, spr, tpi;
+  FastDiv fd_tpi, fd_spr;
 };
 
 // pixel (within the 64-pixel step) of k-step ks, lane block b = lane >> 4, tr read h, lane quad q
@@ -70,6 +77,18 @@ __device__ __forceinline__ int xw_pixel(int ks, int b, int h, int q) { return ks
 // the trswz swizzle of LDS row r as an 8-B unit XOR
 __device__ __forceinline__ int xw_uswz(int r) { return (((r >> 1) & 1) << 2) | (((r >> 3) & 1) << 3); }
 
+// GEN = 1, the general (row segment) geometry of tile_common.h, for rows the classic step does not cover (224 / 112 /
+// 56 / 28 / 14 / 7 wide) and tensors past 2 GiB: a step is rs rows x one seg-column segment of ONE image (the pair is
+// xw_geometry_gen's choice), origin (n0, y0, q0) from seg_tile_origin, wave-uniform. Halo: the (rs + 2) x (seg + 2) box
+// around it at pitch seg + 2; halo column hx is image column q0 + hx - 1, row hy image row y0 + hy - 1, real data wherever
+// that lies inside the image (a neighbouring segment's or step's pixels) and an offset outside the descriptor only
+// where it leaves the image. Slots: l of 64 is row l / seg, column l % seg of the step, dense; a slot at or past
+// rs seg loads zeros of dy, so whatever halo rows its tr reads address (inside the 144 rows for every tap:
+// xw_geometry_gen checks it; all 144 are written every step) it adds exactly nothing. Addressing: both buffer
+// descriptors are made per step over the step's image (base x + n0 H W C, dy + n0 H W K in 64-bit arithmetic, range
+// one image) and live in SGPRs for the loads of that step only; every in-kernel offset stays 32-bit, so the tensors
+// may pass 2 GiB. imgs == 1, so hyi packs (halo column << 16) | halo row. Everything else is the classic kernel.
+template <int GEN>
 __global__ void __launch_bounds__(512) conv_f32x_wgrad_kernel(const XwParams p) {
   __shared__ __attribute__((aligned(1024))) char smem[2 * XW_STAGE];
   stamp_start(p.ts);
@@ -79,20 +98,25 @@ __global__ void __launch_bounds__(512) conv_f32x_wgrad_kernel(const XwParams p) 
   const int c0 = (tile / ktiles) * 64, k0 = (tile % ktiles) * 64;
   const int st_begin = split * p.steps_per_split;
   const int st_end = min(p.nsteps, st_begin + p.steps_per_split);
-  const int W2 = p.W + 2, pc = t & 7;
+  const int W2 = (GEN ? p.seg : p.W) + 2, pc = t & 7;
   const int M = p.N * p.H * p.W;
 
   // ---- loads: unit u of this thread is halo row (u 512 + t) / 8, channels c0 + 8 pc .. + 7, relative to the step's
   // first pixel; the dy unit is pixel t / 8 of the step, channels k0 + 8 pc .. + 7
   const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc((void*)p.dy, 0, p.dy_bytes, 0x00020000);
-  int hrel[XW_UNITS], hyi[XW_UNITS];  // byte offset from the step's first pixel; (image << 16) | (row + 1), -1: never
+  // byte offset from the step's first pixel; (image << 16) | (row + 1) [GEN: (column + 1) << 16 | (row + 1)], -1: never
+  int hrel[XW_UNITS], hyi[XW_UNITS];
 #pragma unroll
   for (int u = 0; u < XW_UNITS; ++u) {
     const int hr = (u * 512 + t) >> 3;
     hrel[u] = 0;
     hyi[u] = -1;
-    if (hr < p.nh) {
+    if (GEN && hr < p.nh) {
+      const int hy = hr / W2, hx = hr - hy * W2;
+      hrel[u] = (((hy - 1) * p.W + hx - 1) * p.C + c0 + pc * 8) * 4;
+      hyi[u] = (hx << 16) | hy;
+    } else if (hr < p.nh) {
       const int i = hr / p.hb, rem = hr - i * p.hb;
       const int hy = rem / W2, hx = rem - hy * W2;
       if ((unsigned)(hx - 1) < (unsigned)p.W) {
@@ -102,13 +126,37 @@ __global__ void __launch_bounds__(512) conv_f32x_wgrad_kernel(const XwParams p) 
     }
   }
   const int drow = t >> 3;
-  const uint32_t drel = (uint32_t)((drow * p.K + k0 + pc * 8) * 4);
+  uint32_t drel = (uint32_t)((drow * p.K + k0 + pc * 8) * 4);
+  if constexpr (GEN) {  // slot drow is pixel (drow / seg, drow % seg) of the step; a padded slot loads zeros
+    const int dr = drow / p.seg;
+    drel = dr < p.rows ? (uint32_t)(((dr * p.W + drow - dr * p.seg) * p.K + k0 + pc * 8) * 4) : DMA_OOB;
+  }
   f32x4 pf[XW_UNITS + 1][2];  // the next step's operands, fp32, in flight / held until the step boundary
   auto load16 = [](const __amdgpu_buffer_rsrc_t& r, uint32_t o, f32x4 (&d)[2]) {
     d[0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, o, 0, 0));
     d[1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, o + 16u, 0, 0));
   };
   auto load_step = [&](int step) {
+    if constexpr (GEN) {
+      int n0, y0, q0;
+      seg_tile_origin(step, p.tpi, p.fd_tpi, p.spr, p.fd_spr, p.rows, p.seg, n0, y0, q0);
+      n0 = __builtin_amdgcn_readfirstlane(n0);  // (the descriptors are per step: keep them in SGPRs)
+      y0 = __builtin_amdgcn_readfirstlane(y0);
+      q0 = __builtin_amdgcn_readfirstlane(q0);
+      const size_t img = (size_t)n0 * p.H * p.W;
+      const auto gx = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x + img * p.C), 0, p.x_bytes, 0x00020000);
+      const auto gd = __builtin_amdgcn_make_buffer_rsrc((void*)(p.dy + img * p.K), 0, p.dy_bytes, 0x00020000);
+      const uint32_t pix0 = (uint32_t)(y0 * p.W + q0);
+#pragma unroll
+      for (int u = 0; u < XW_UNITS; ++u) {
+        if (u == XW_UNITS - 1 && wave >= 2) break;  // rows 128 .. 143: waves 0 and 1
+        const int y = y0 + (hyi[u] & 0xffff) - 1, xc = q0 + (hyi[u] >> 16) - 1;
+        const bool ok = hyi[u] >= 0 && (unsigned)y < (unsigned)p.H && (unsigned)xc < (unsigned)p.W;
+        load16(gx, ok ? pix0 * (uint32_t)(p.C * 4) + (uint32_t)hrel[u] : DMA_OOB, pf[u]);
+      }
+      load16(gd, drel != DMA_OOB ? pix0 * (uint32_t)(p.K * 4) + drel : DMA_OOB, pf[XW_UNITS]);
+      return;
+    }
     int n0, y0;
     if (p.imgs == 1) {
       n0 = step / p.spimg;
@@ -155,6 +203,11 @@ __global__ void __launch_bounds__(512) conv_f32x_wgrad_kernel(const XwParams p) 
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int tp = xw_pixel(ks, lg, h, lq);
+      if constexpr (GEN) {
+        const int pr = tp / p.seg;
+        hm[ks][h] = pr * W2 + tp - pr * p.seg;
+        continue;
+      }
       const int ii = tp / spi, rem = tp - ii * spi;
       const int pr = rem / p.W, q = rem - pr * p.W;
       hm[ks][h] = ii * p.hb + pr * W2 + q;
@@ -266,6 +319,8 @@ __global__ void __launch_bounds__(512) conv_f32x_wgrad_kernel(const XwParams p) 
 // ---------------------------------------------------------------- host side
 struct XwGeom {
   int rows = 0, imgs = 0, hb = 0, nh = 0, nsteps = 0;
+  bool gen = false;  // the general instance: `rows` rows x one g.seg-column segment of one image per step
+  SegTile g;
 };
 // Step geometry of a feasible shape: 64 pixels are whole rows of one image or whole images (a last step of fewer
 // images than `imgs` is padded with zeros by the loads)
@@ -284,9 +339,58 @@ static bool xw_geometry(const ConvShape& s, XwGeom& g) {
   return true;
 }
 
+// General geometry of a feasible shape. The step rule: over the divisors seg <= 64 of W, with rs = the largest row
+// count <= 64 / seg that divides H, the pair with the most pixels rs seg, ties to the larger seg (fewer side halo
+// columns), among those whose halo (rs + 2) x (seg + 2) fits the 144 rows and whose padded slots' tr reads stay inside
+// them at the largest tap shift. (224: 32 x 2, 112: 16 x 4, 56: 8 x 8 -- in LDS the classic 32- / 16- / 8-wide steps --
+// 28: 28 x 2 = 56 pixels, 14 and 7: 7 x 7 = 49, 64: 32 x 2.)
+static bool xw_geometry_gen(const ConvShape& s, XwGeom& g) {
+  if (!conv3x3_ok(s, 1)) return false;
+  int best = 0;
+  for (int seg = 1; seg <= std::min(s.W, 64); ++seg) {
+    if (s.W % seg) continue;
+    const int rs = rows_dividing(s.H, 64 / seg), w2 = seg + 2;
+    // slot 63, the last a tr read addresses, at tap (2, 2): its halo row must exist (a padded slot's too)
+    if (halo_box_s1(rs, seg) > XW_HROWS || (63 / seg + 2) * w2 + 63 % seg + 2 >= XW_HROWS) continue;
+    if (rs * seg >= best) {
+      best = rs * seg;
+      g.g = seg_tile(s.H, s.W, seg, rs);
+    }
+  }
+  if (best == 0) return false;
+  g.gen = true;
+  g.rows = g.g.rs;
+  g.imgs = 1;
+  g.hb = g.nh = halo_box_s1(g.g.rs, g.g.seg);
+  // one image of either operand within the per-step buffer descriptors (32-bit byte offsets; DMA_OOB must lie outside
+  // them), and the step index within FastDiv's 31 bits. The tensors themselves may pass 2 GiB
+  const int64_t nsteps = (int64_t)s.N * g.g.tpi;
+  if ((int64_t)s.H * s.W * std::max(s.C, s.K) * 4 >= (1ll << 31) || nsteps >= (1ll << 31)) return false;
+  g.nsteps = (int)nsteps;
+  return true;
+}
+// Option f32x_gen for the weight gradient: 0 classic geometry only; 1 the general step classes (seg, rs) that measured
+// faster than conv_f32's weight gradient; 2 every feasible one (for measuring, and the small test shapes)
+static bool xw_gen_admitted(const XwGeom& g) {
+  const int lvl = option_get(OPT_F32X_GEN);
+  if (lvl >= 2) return true;
+  // measured (profiles/f32_split_gen_wgrad_bench.txt): the five step classes of the 224 / 112 / 56 / 28 and
+  // 14 / 7 wide rows -- 32 x 2, 16 x 4, 8 x 8 (64 pixels), 28 x 2 (56), 7 x 7 (49) -- ran 2.0-3.3x faster than
+  // conv_f32's weight gradient at every batch measured (32 and 128 or 256), the split's whole min..max range below the
+  // exact kernel's. Every other class (odd row counts that leave rs short, other widths) was not measured: refused
+  const int seg = g.g.seg, rs = g.g.rs;
+  return lvl == 1 && ((seg == 32 && rs == 2) || (seg == 16 && rs == 4) || (seg == 8 && rs == 8) ||
+                      (seg == 28 && rs == 2) || (seg == 7 && rs == 7));
+}
+// the classic geometry first, unchanged; otherwise, under option f32x_gen, the general one
+static bool xw_geometry_any(const ConvShape& s, XwGeom& g) {
+  if (xw_geometry(s, g)) return true;
+  return option_get(OPT_F32X_GEN) != 0 && xw_geometry_gen(s, g) && xw_gen_admitted(g);
+}
+
 bool conv_f32x_wgrad_ok(const ConvShape& s) {
   XwGeom g;
-  return xw_geometry(s, g);
+  return xw_geometry_any(s, g);
 }
 
 // Splits that fill the chip's 256 CUs with (tiles x splits) workgroups, at least four steps each: a split's
@@ -303,7 +407,7 @@ static int xw_splits_run(int nsteps, int splits) {
 
 size_t conv_f32x_wgrad_workspace(const ConvShape& s) {
   XwGeom g;
-  if (!xw_geometry(s, g)) return 0;
+  if (!xw_geometry_any(s, g)) return 0;
   const int splits = xw_splits_run(g.nsteps, xw_splits(s, g));
   return splits == 1 ? 0 : (size_t)splits * s.K * 9 * s.C * 4;
 }
@@ -311,7 +415,7 @@ size_t conv_f32x_wgrad_workspace(const ConvShape& s) {
 int conv_f32x_wgrad(const ConvShape& s, const float* x, const float* dy, float* dw, float scale, float* slab,
                     size_t slab_bytes, hipStream_t st, u64* ts) {
   XwGeom g;
-  DTC_CHECK_ARG(xw_geometry(s, g), "conv_f32x_wgrad: unsupported shape");
+  DTC_CHECK_ARG(xw_geometry_any(s, g), "conv_f32x_wgrad: unsupported shape");
   DTC_CHECK_ARG(x && dy && dw && aligned(x, 16) && aligned(dy, 16) && aligned(dw, 16) && (!slab || aligned(slab, 16)),
                 "conv_f32x_wgrad: null / misaligned argument");
   const size_t one = (size_t)s.K * 9 * s.C * 4;
@@ -331,8 +435,16 @@ int conv_f32x_wgrad(const ConvShape& s, const float* x, const float* dy, float* 
   p.nsteps = g.nsteps;
   p.steps_per_split = (g.nsteps + splits - 1) / splits;
   p.ts = ts;
+  if (g.gen) {  // one image: the descriptors are made per step
+    p.x_bytes = (uint32_t)((uint64_t)s.H * s.W * s.C * 4);
+    p.dy_bytes = (uint32_t)((uint64_t)s.H * s.W * s.K * 4);
+    p.seg = g.g.seg; p.spr = g.g.spr; p.tpi = g.g.tpi;
+    p.fd_tpi = make_fastdiv(g.g.tpi);
+    p.fd_spr = make_fastdiv(g.g.spr);
+  }
   const dim3 grid((unsigned)((s.C / 64) * (s.K / 64)), (unsigned)splits);
-  DTC_KLAUNCH(conv_f32x_wgrad_kernel, grid, dim3(512), 0, st, p);
+  if (g.gen) DTC_KLAUNCH(conv_f32x_wgrad_kernel<1>, grid, dim3(512), 0, st, p);
+  else DTC_KLAUNCH(conv_f32x_wgrad_kernel<0>, grid, dim3(512), 0, st, p);
   DTC_LAUNCH_CHECK();
   if (splits == 1) return 0;
   return f32_wgrad_reduce(slab, splits, s.K, 9 * s.C, 9 * s.C, 9 * s.C, scale, dw, st, ts);

@@ -68,7 +68,7 @@ namespace dtc {
   X(F32_SPLIT, f32_split, 0)            /* (plan time) fp32 executor: 3x3 s1 FWD/DGRAD on the split-bf16 kernel (conv_f32x); 2: WGRAD too; 3: + the transition blocks' FWD / DGRAD (conv_f32x_s2); 4: + their WGRAD (conv_f32x_s2_wgrad) */ \
   X(F32X_S2_FWD, f32x_s2_fwd, 1)        /* conv_f32x_s2 FWD_SC: 1 where it measured faster than the exact pair, 2 every feasible geometry (to measure) */ \
   X(F32X_S2_WGRAD, f32x_s2_wgrad, 1)    /* conv_f32x_s2_wgrad: 1 where it measured faster than the exact pair, 2 every feasible geometry (to measure) */ \
-  X(F32X_GEN, f32x_gen, 0)              /* conv_f32x general (row-segment) tiles, the 224x224 geometry: 0 classic rows only, 1 where it measured faster than conv_f32, 2 every feasible geometry (to measure) */
+  X(F32X_GEN, f32x_gen, 0)              /* conv_f32x / conv_f32x_wgrad general (row-segment) tiles, the 224x224 geometry: 0 classic rows only, 1 where it measured faster than conv_f32, 2 every feasible geometry (to measure) */
 
 enum {
 #define DTC_OPT_ENUM(id, name, def) OPT_##id,
@@ -254,7 +254,10 @@ int f32_split3(const float* src, u16* planes, int64_t n, int64_t stride, hipStre
 // conv, both fp32 operands split in the kernel. Split-K over pixel steps into fp32 slabs [split][K][9 C] summed by
 // f32_wgrad_reduce; the splits are lowered until `slab` holds them, and one split writes dw itself (no slab needed).
 // conv_f32x_wgrad_ok: rows of 4 / 8 / 16 / 32 pixels whose 64-pixel steps are whole rows or whole images, C and K
-// multiples of 64, tensors below 2 GiB. conv_f32x_wgrad_workspace: the slab bytes it wants (0: one split).
+// multiples of 64, tensors below 2 GiB. With option f32x_gen also the general geometry (a step is rows of one segment
+// of one image, at most 64 pixels and 144 halo rows: 224 / 112 / 56 / 28 / 14 / 7 wide rows): one image below 2 GiB,
+// tensors of any size; 1: the step classes that measured faster than conv_f32's weight gradient, 2: all.
+// conv_f32x_wgrad_workspace: the slab bytes it wants (0: one split).
 bool conv_f32x_wgrad_ok(const ConvShape& s);
 size_t conv_f32x_wgrad_workspace(const ConvShape& s);
 int conv_f32x_wgrad(const ConvShape& s, const float* x, const float* dy, float* dw, float scale, float* slab,

@@ -46,8 +46,9 @@ int dtc_install_crash_handler(void);
  * (plan time: direct 3x3 stem conv, default 1; 0 = im2col + GEMM), "f32_split" (plan time: the fp32 executor's 3x3
  * stride-1 forward and data-gradient convs on the split-bf16 kernel, default 0; 2: their weight gradients too; 3: also
  * the transition blocks' conv1 + shortcut forward and data gradient, one split-bf16 launch each; 4: also their two
- * weight gradients, one split-bf16 launch), "f32x_gen" (the split-bf16 forward / data gradient on row-segment tiles,
- * the 224x224 model's rows: default 0 off, 1 where measured faster, 2 wherever feasible; see the fp32 convolution). */
+ * weight gradients, one split-bf16 launch), "f32x_gen" (the split-bf16 forward / data gradient / weight gradient on
+ * row-segment tiles, the 224x224 model's rows: default 0 off, 1 where measured faster, 2 wherever feasible; see the fp32
+ * convolution). */
 int dtc_set_option(const char* name, int value);
 int dtc_get_option(const char* name);
 
@@ -206,7 +207,9 @@ int dtc_conv2d_f32_dgrad_sc(const dtc_conv_desc* d, const float* dy, const void*
  * algo 0: the f32-input MFMA kernel (any descriptor above); it needs a workspace of at least one slab of k*r*s*c*4
  * bytes (DTC_EINVAL otherwise). algo 1: for the descriptors DTC_CONV_F32_SPLIT serves (here: 64-pixel steps of whole
  * rows or whole images) the split-bf16 kernel, both operands split in the kernel, element-wise error below 2^-22 of
- * sum |x||dy|; any other descriptor runs the exact kernel. Both reduce split-K slabs in a fixed order (bit-identical
+ * sum |x||dy|; any other descriptor runs the exact kernel. Option "f32x_gen" widens what algo 1 serves here too: steps
+ * of rows of one row segment of one image (224 / 112 / 56 / 28 / 14 / 7 wide rows, one image below 2 GiB, tensors of any
+ * size; 1: the step classes that measured faster than the exact kernel, 2: every feasible one). Both reduce split-K slabs in a fixed order (bit-identical
  * run to run). A workspace shorter than dtc_conv2d_f32_wgrad_workspace_size lowers the number of splits; the split
  * kernel runs with none at all (one split). dtc_conv2d_f32_wgrad_route_query (host only): the kernel that runs. */
 int dtc_conv2d_f32_wgrad_route_query(const dtc_conv_desc* d, int algo);

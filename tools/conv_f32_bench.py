@@ -2,8 +2,8 @@
 (conv_f32, algo 0) and on the split-bf16 kernels (conv_f32x / conv_f32x_wgrad, algo 1), interleaved in one process;
 then the transition blocks' conv1 + shortcut pair (fwd_sc / dgrad_sc: two conv_f32 launches against conv_f32x_s2;
 wgrad_sc: the two conv_f32 weight gradients against the one conv_f32x_s2_wgrad launch, its reduces included).
---gen-cases: the same forward / data gradient at the 224x224 model's rows (g1 .. g4: 224 / 112 / 56 / 28 wide), which
-the split kernel serves on its general (row-segment) tiles under option f32x_gen; their weight gradient stays exact.
+--gen-cases: the same three passes at the 224x224 model's rows (g1 .. g4: 224 / 112 / 56 / 28 wide), which the split
+kernels serve on their general (row-segment) tiles and steps under option f32x_gen.
 
 As tools/conv_bench.py: each (layer, pass, algo) is captured ITERS times into a graph on preallocated buffers (raw
 C-ABI calls), so a replay measures device time only; ROUNDS interleaved rounds per case. Prints the median us, the
@@ -118,7 +118,8 @@ def main():
     ap.add_argument("--wgrad-sc-cases", default=",".join(f"t{l}:{b}" for b in (256, 128, 64, 32) for l in (2, 3, 4)),
                     help="transition blocks' fused weight gradients (wgrad_sc rows), name:batch, ...; empty: none")
     ap.add_argument("--gen-cases", default=",".join(f"g{l}:{b}" for b in (32, 128) for l in (1, 2, 3, 4)),
-                    help="general-geometry rows (fwd / dgrad under option f32x_gen), name:batch, ...; empty: none")
+                    help="general-geometry rows (all three passes under option f32x_gen), name:batch, ...; empty: none")
+    ap.add_argument("--passes", default="", help="of fwd,dgrad,wgrad for --cases / --gen-cases; empty: all")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
     args = ap.parse_args()
@@ -131,11 +132,12 @@ def main():
     for case in filter(None, (args.cases + "," + args.gen_cases).split(",")):
         name, B = case.split(":")[0], int(case.split(":")[1])
         H, C = geo[name]
-        gen, note = name.startswith("g"), ""
+        gen, refused = name.startswith("g"), set()
         if gen:  # timed with every feasible general tile admitted; the note says what the default rule (1) does
             nat.call("dtc_set_option", b"f32x_gen", 1)
-            if ops.conv2d_f32_route(ops.conv_desc(B, H, H, C, C, 3, 3, 1, 1), 0, 1) != "split":
-                note = "  (refused at f32x_gen = 1)"
+            d1 = ops.conv_desc(B, H, H, C, C, 3, 3, 1, 1)
+            refused = {m for m in (0, 1, 2)
+                       if (ops.conv2d_f32_wgrad_route(d1, 1) if m == 2 else ops.conv2d_f32_route(d1, m, 1)) != "split"}
             nat.call("dtc_set_option", b"f32x_gen", 2)
         x = torch.randn(B, H, H, C, device=dev)
         w = torch.randn(C, 3, 3, C, device=dev) * 0.05
@@ -148,7 +150,10 @@ def main():
         dw = torch.empty(C, 3, 3, C, device=dev)
         wsz = {a: int(nat.lib.dtc_conv2d_f32_wgrad_workspace_size(d, a)) for a in (0, 1)}
         ws = torch.empty(max(wsz.values()), dtype=torch.uint8, device=dev)
-        for pname, mode in (("fwd", 0), ("dgrad", 1), ("wgrad", 2))[:2 if gen else 3]:
+        for pname, mode in (("fwd", 0), ("dgrad", 1), ("wgrad", 2)):
+            if args.passes and pname not in args.passes.split(","):
+                continue
+            note = "  (refused at f32x_gen = 1)" if mode in refused else ""
             assert (ops.conv2d_f32_wgrad_route(d, 1) if mode == 2 else ops.conv2d_f32_route(d, mode, 1)) == "split", case
             fns = {}
             for algo, wt in ((0, w), (1, wpl)):
