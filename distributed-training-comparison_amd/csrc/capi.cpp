@@ -294,14 +294,30 @@ int dtc_conv2d_fwd(const dtc_conv_desc* d, const uint16_t* x, const uint16_t* w,
   GUARD(return conv_fwd(shape_of(d), x, w, y, stats, (float*)ws, c.slab_bytes, S(stream), nullptr, c.tick);)
 }
 
-// ---- fp32 convolutions: conv_f32 (exact) or the split-bf16 kernel (conv_f32x), chosen by conv_f32_route
+// ---- fp32 convolutions: conv_f32 (exact) or the split-bf16 kernels, as conv_f32_plan (conv_f32_route.cpp) answers
+// with algo != 0 for "the split is wanted". Two families: one conv, and (sc) a transition block's conv1 (the
+// descriptor: 3x3 / pad 1, stride 2 in the model) together with the block's 1x1 shortcut of the same stride.
 // what conv_f32 takes: C and K multiples of 16, stride 1 / 2, tensors whose pixel index fits 31 bits
-static bool desc_ok_f32(const dtc_conv_desc* d) {
+static bool desc_ok_f32(const dtc_conv_desc* d, bool sc = false) {
   if (!d || d->n <= 0 || d->h <= 0 || d->w <= 0 || d->c <= 0 || d->k <= 0 || d->r <= 0 || d->s <= 0) return false;
   if (d->c % 16 != 0 || d->k % 16 != 0 || (d->stride != 1 && d->stride != 2) || d->pad < 0) return false;
+  if (sc && !(d->r == 3 && d->s == 3 && d->pad == 1)) return false;
   const int64_t p = (d->h + 2 * d->pad - d->r) / d->stride + 1, q = (d->w + 2 * d->pad - d->s) / d->stride + 1;
   return d->h + 2 * d->pad >= d->r && d->w + 2 * d->pad >= d->s && p > 0 && q > 0 &&
          (int64_t)d->n * d->h * d->w < (1ll << 31);
+}
+static int f32_bad_desc(const char* fn, bool sc) {
+  return set_error(DTC_EINVAL, sc ? "%s: not a 3x3 pad-1 convolution conv_f32 takes" : "%s: unsupported convolution descriptor", fn);
+}
+// what every fp32 entry point refuses before it plans: null arguments, the family's descriptors, algo
+static int f32_refuse(const char* fn, bool sc, const dtc_conv_desc* d, bool args, int algo) {
+  if (!args) return set_error(DTC_EINVAL, "%s: null argument", fn);
+  if (!desc_ok_f32(d, sc)) return f32_bad_desc(fn, sc);
+  if (algo != 0 && algo != 1) return set_error(DTC_EINVAL, "%s: algo %d (0 exact, 1 split)", fn, algo);
+  return 0;
+}
+static ConvF32Plan f32_plan(const ConvShape& s, int pass, bool sc, int algo) {
+  return conv_f32_plan(s, pass, sc, algo != 0, true);
 }
 
 static_assert(DTC_CONV_F32_EXACT == CONV_F32_EXACT && DTC_CONV_F32_SPLIT == CONV_F32_SPLIT, "DTC_CONV_F32_* mirror");
@@ -311,20 +327,41 @@ int dtc_f32_split3(const float* src, uint16_t* planes, int64_t n, void* stream) 
   GUARD(return f32_split3(src, planes, n, n, S(stream));)
 }
 
-int dtc_conv2d_f32_route_query(const dtc_conv_desc* d, int pass, int algo) {
-  DTC_CHECK_ARG(desc_ok_f32(d), "dtc_conv2d_f32_route_query: unsupported convolution descriptor");
+// the FWD / DGRAD route queries of both families (the weight gradients have their own: no pass argument)
+static int f32_route_query(const char* fn, const dtc_conv_desc* d, int pass, bool sc, int algo) {
+  if (!desc_ok_f32(d, sc)) return f32_bad_desc(fn, sc);
   DTC_CHECK_ARG((pass == CONV_FWD || pass == CONV_DGRAD) && (algo == 0 || algo == 1),
-                "dtc_conv2d_f32_route_query: pass %d algo %d name no entry point", pass, algo);
-  return conv_f32_route(shape_of(d), pass, algo != 0, true);
+                "%s: pass %d algo %d name no entry point", fn, pass, algo);
+  return f32_plan(shape_of(d), pass, sc, algo).kernel;
 }
+int dtc_conv2d_f32_route_query(const dtc_conv_desc* d, int pass, int algo) {
+  return f32_route_query("dtc_conv2d_f32_route_query", d, pass, false, algo);
+}
+int dtc_conv2d_f32_sc_route_query(const dtc_conv_desc* d, int pass, int algo) {
+  return f32_route_query("dtc_conv2d_f32_sc_route_query", d, pass, true, algo);
+}
+int dtc_conv2d_f32_wgrad_route_query(const dtc_conv_desc* d, int algo) {
+  DTC_TRY(f32_refuse("dtc_conv2d_f32_wgrad_route_query", false, d, true, algo));
+  return f32_plan(shape_of(d), CONV_WGRAD, false, algo).kernel;
+}
+int dtc_conv2d_f32_wgrad_sc_route_query(const dtc_conv_desc* d, int algo) {
+  DTC_TRY(f32_refuse("dtc_conv2d_f32_wgrad_sc_route_query", true, d, true, algo));
+  return f32_plan(shape_of(d), CONV_WGRAD, true, algo).kernel;
+}
+
+// the slab the weight gradient's route wants (the exact pair: the larger of its two, each launch takes the whole)
+static size_t f32_wgrad_ws(const dtc_conv_desc* d, bool sc, int algo) {
+  if (!desc_ok_f32(d, sc) || (algo != 0 && algo != 1)) return 0;
+  return f32_plan(shape_of(d), CONV_WGRAD, sc, algo).slab_bytes;
+}
+size_t dtc_conv2d_f32_wgrad_workspace_size(const dtc_conv_desc* d, int algo) { return f32_wgrad_ws(d, false, algo); }
+size_t dtc_conv2d_f32_wgrad_sc_workspace_size(const dtc_conv_desc* d, int algo) { return f32_wgrad_ws(d, true, algo); }
 
 static int conv2d_f32(const char* fn, const dtc_conv_desc* d, int pass, const float* a, const void* w, float* out,
                       const float* res, int64_t* stats, int algo, hipStream_t st) {
-  if (!(d && a && w && out)) return set_error(DTC_EINVAL, "%s: null argument", fn);
-  if (!desc_ok_f32(d)) return set_error(DTC_EINVAL, "%s: unsupported convolution descriptor", fn);
-  if (algo != 0 && algo != 1) return set_error(DTC_EINVAL, "%s: algo %d (0 exact, 1 split)", fn, algo);
+  DTC_TRY(f32_refuse(fn, false, d, d && a && w && out, algo));
   const ConvShape s = shape_of(d);
-  if (conv_f32_route(s, pass, algo != 0, true) == CONV_F32_SPLIT)
+  if (f32_plan(s, pass, false, algo).kernel == CONV_F32_SPLIT)
     return conv_f32x(s, pass, a, (const u16*)w, (int64_t)s.K * s.R * s.S * s.C, out, res, stats, st);
   return conv_f32(s, pass, a, (const float*)w, out, res, stats, nullptr, 0, 0, 0.f, nullptr, 0, st);
 }
@@ -341,31 +378,17 @@ int dtc_conv2d_f32_dgrad(const dtc_conv_desc* d, const float* dy, const void* w,
   GUARD(return conv2d_f32("dtc_conv2d_f32_dgrad", d, CONV_DGRAD, dy, w, dx, res, nullptr, algo, S(stream));)
 }
 
-// ---- the transition blocks' fused pair on fp32 tensors: conv1 (the descriptor: 3x3 / pad 1, stride 2 in the model)
-// and the block's 1x1 shortcut of the same stride. algo 0 (and any shape the split kernel refuses): the two conv_f32
-// launches
-static bool desc_ok_f32_sc(const dtc_conv_desc* d) { return desc_ok_f32(d) && d->r == 3 && d->s == 3 && d->pad == 1; }
-static ConvShape sc_shape_of(const ConvShape& s) { return ConvShape{s.N, s.H, s.W, s.C, s.K, 1, 1, s.stride, 0}; }
-
-int dtc_conv2d_f32_sc_route_query(const dtc_conv_desc* d, int pass, int algo) {
-  DTC_CHECK_ARG(desc_ok_f32_sc(d), "dtc_conv2d_f32_sc_route_query: not a 3x3 pad-1 convolution conv_f32 takes");
-  DTC_CHECK_ARG((pass == CONV_FWD || pass == CONV_DGRAD) && (algo == 0 || algo == 1),
-                "dtc_conv2d_f32_sc_route_query: pass %d algo %d name no entry point", pass, algo);
-  return conv_f32_sc_route(shape_of(d), pass, algo != 0, true);
-}
-
+// algo 0 (and any shape the split kernel refuses): the two conv_f32 launches
 int dtc_conv2d_f32_fwd_sc(const dtc_conv_desc* d, const float* x, const void* w, float* y, int64_t* stats,
                           const void* wsc, float* ysc, int64_t* stats_sc, int algo, void* stream) {
-  DTC_CHECK_ARG(d && x && w && y && wsc && ysc, "dtc_conv2d_f32_fwd_sc: null argument");
-  DTC_CHECK_ARG(desc_ok_f32_sc(d), "dtc_conv2d_f32_fwd_sc: not a 3x3 pad-1 convolution conv_f32 takes");
-  DTC_CHECK_ARG(algo == 0 || algo == 1, "dtc_conv2d_f32_fwd_sc: algo %d (0 exact, 1 split)", algo);
+  DTC_TRY(f32_refuse("dtc_conv2d_f32_fwd_sc", true, d, d && x && w && y && wsc && ysc, algo));
   const ConvShape s = shape_of(d);
   GUARD(
-    if (conv_f32_sc_route(s, CONV_FWD, algo != 0, true) == CONV_F32_SPLIT)
+    if (f32_plan(s, CONV_FWD, true, algo).kernel == CONV_F32_SPLIT)
       return conv_f32x_s2_fwd(s, x, (const u16*)w, (int64_t)s.K * 9 * s.C, y, stats, (const u16*)wsc, (int64_t)s.K * s.C,
                               ysc, stats_sc, S(stream));
-    DTC_TRY(conv_f32(sc_shape_of(s), CONV_FWD, x, (const float*)wsc, ysc, nullptr, stats_sc, nullptr, 0, 0, 0.f, nullptr,
-                     0, S(stream)));
+    DTC_TRY(conv_f32(conv_f32_sc_shape(s), CONV_FWD, x, (const float*)wsc, ysc, nullptr, stats_sc, nullptr, 0, 0, 0.f,
+                     nullptr, 0, S(stream)));
     return conv_f32(s, CONV_FWD, x, (const float*)w, y, nullptr, stats, nullptr, 0, 0, 0.f, nullptr, 0, S(stream));)
 }
 
@@ -373,41 +396,24 @@ int dtc_conv2d_f32_fwd_sc(const dtc_conv_desc* d, const float* x, const void* w,
 // epilogue reads and writes each element in one thread): the executor's residual form without a second buffer
 int dtc_conv2d_f32_dgrad_sc(const dtc_conv_desc* d, const float* dy, const void* w, float* dx, const float* dsc,
                             const void* wsc, int algo, void* stream) {
-  DTC_CHECK_ARG(d && dy && w && dx && dsc && wsc, "dtc_conv2d_f32_dgrad_sc: null argument");
-  DTC_CHECK_ARG(desc_ok_f32_sc(d), "dtc_conv2d_f32_dgrad_sc: not a 3x3 pad-1 convolution conv_f32 takes");
-  DTC_CHECK_ARG(algo == 0 || algo == 1, "dtc_conv2d_f32_dgrad_sc: algo %d (0 exact, 1 split)", algo);
+  DTC_TRY(f32_refuse("dtc_conv2d_f32_dgrad_sc", true, d, d && dy && w && dx && dsc && wsc, algo));
   const ConvShape s = shape_of(d);
   GUARD(
-    if (conv_f32_sc_route(s, CONV_DGRAD, algo != 0, true) == CONV_F32_SPLIT)
+    if (f32_plan(s, CONV_DGRAD, true, algo).kernel == CONV_F32_SPLIT)
       return conv_f32x_s2_dgrad(s, dy, (const u16*)w, (int64_t)s.K * 9 * s.C, dx, dsc, (const u16*)wsc,
                                 (int64_t)s.K * s.C, S(stream));
-    DTC_TRY(conv_f32(sc_shape_of(s), CONV_DGRAD, dsc, (const float*)wsc, dx, nullptr, nullptr, nullptr, 0, 0, 0.f,
+    DTC_TRY(conv_f32(conv_f32_sc_shape(s), CONV_DGRAD, dsc, (const float*)wsc, dx, nullptr, nullptr, nullptr, 0, 0, 0.f,
                      nullptr, 0, S(stream)));
     return conv_f32(s, CONV_DGRAD, dy, (const float*)w, dx, dx, nullptr, nullptr, 0, 0, 0.f, nullptr, 0, S(stream));)
 }
 
 // The fp32 weight gradient: conv_f32's WGRAD (algo 0, or a shape the split kernel refuses) or conv_f32x_wgrad
-int dtc_conv2d_f32_wgrad_route_query(const dtc_conv_desc* d, int algo) {
-  DTC_CHECK_ARG(desc_ok_f32(d), "dtc_conv2d_f32_wgrad_route_query: unsupported convolution descriptor");
-  DTC_CHECK_ARG(algo == 0 || algo == 1, "dtc_conv2d_f32_wgrad_route_query: algo %d (0 exact, 1 split)", algo);
-  return conv_f32_route(shape_of(d), CONV_WGRAD, algo != 0, false);
-}
-
-size_t dtc_conv2d_f32_wgrad_workspace_size(const dtc_conv_desc* d, int algo) {
-  if (!desc_ok_f32(d) || (algo != 0 && algo != 1)) return 0;
-  const ConvShape s = shape_of(d);
-  return conv_f32_route(s, CONV_WGRAD, algo != 0, false) == CONV_F32_SPLIT ? conv_f32x_wgrad_workspace(s)
-                                                                          : f32_conv_workspace(s, CONV_WGRAD);
-}
-
 int dtc_conv2d_f32_wgrad(const dtc_conv_desc* d, const float* x, const float* dy, float* dw, float scale, int algo,
                          void* ws, size_t ws_bytes, void* stream) {
-  DTC_CHECK_ARG(d && x && dy && dw, "dtc_conv2d_f32_wgrad: null argument");
-  DTC_CHECK_ARG(desc_ok_f32(d), "dtc_conv2d_f32_wgrad: unsupported convolution descriptor");
-  DTC_CHECK_ARG(algo == 0 || algo == 1, "dtc_conv2d_f32_wgrad: algo %d (0 exact, 1 split)", algo);
+  DTC_TRY(f32_refuse("dtc_conv2d_f32_wgrad", false, d, d && x && dy && dw, algo));
   const ConvShape s = shape_of(d);
   if (!ws) ws_bytes = 0;
-  if (conv_f32_route(s, CONV_WGRAD, algo != 0, false) == CONV_F32_SPLIT) {
+  if (f32_plan(s, CONV_WGRAD, false, algo).kernel == CONV_F32_SPLIT) {
     GUARD(return conv_f32x_wgrad(s, x, dy, dw, scale, (float*)ws, ws_bytes, S(stream));)
   }
   DTC_CHECK_ARG(ws_bytes >= (size_t)s.K * s.R * s.S * s.C * 4,
@@ -419,27 +425,12 @@ int dtc_conv2d_f32_wgrad(const dtc_conv_desc* d, const float* x, const float* dy
 
 // The transition blocks' fused weight-gradient pair: conv_f32x_s2_wgrad (algo 1 where its predicate holds) or the
 // two conv_f32 weight gradients, each on the whole workspace (the splits dtc_conv2d_f32_wgrad(algo 0) runs)
-int dtc_conv2d_f32_wgrad_sc_route_query(const dtc_conv_desc* d, int algo) {
-  DTC_CHECK_ARG(desc_ok_f32_sc(d), "dtc_conv2d_f32_wgrad_sc_route_query: not a 3x3 pad-1 convolution conv_f32 takes");
-  DTC_CHECK_ARG(algo == 0 || algo == 1, "dtc_conv2d_f32_wgrad_sc_route_query: algo %d (0 exact, 1 split)", algo);
-  return conv_f32_wgrad_sc_route(shape_of(d), algo != 0);
-}
-
-size_t dtc_conv2d_f32_wgrad_sc_workspace_size(const dtc_conv_desc* d, int algo) {
-  if (!desc_ok_f32_sc(d) || (algo != 0 && algo != 1)) return 0;
-  const ConvShape s = shape_of(d);
-  if (conv_f32_wgrad_sc_route(s, algo != 0) == CONV_F32_SPLIT) return conv_f32x_s2_wgrad_workspace(s);
-  return std::max(f32_conv_workspace(s, CONV_WGRAD), f32_conv_workspace(sc_shape_of(s), CONV_WGRAD));
-}
-
 int dtc_conv2d_f32_wgrad_sc(const dtc_conv_desc* d, const float* x, const float* dy, const float* dsc, float* dw,
                             float* dwsc, float scale, int algo, void* ws, size_t ws_bytes, void* stream) {
-  DTC_CHECK_ARG(d && x && dy && dsc && dw && dwsc, "dtc_conv2d_f32_wgrad_sc: null argument");
-  DTC_CHECK_ARG(desc_ok_f32_sc(d), "dtc_conv2d_f32_wgrad_sc: not a 3x3 pad-1 convolution conv_f32 takes");
-  DTC_CHECK_ARG(algo == 0 || algo == 1, "dtc_conv2d_f32_wgrad_sc: algo %d (0 exact, 1 split)", algo);
+  DTC_TRY(f32_refuse("dtc_conv2d_f32_wgrad_sc", true, d, d && x && dy && dsc && dw && dwsc, algo));
   const ConvShape s = shape_of(d);
   if (!ws) ws_bytes = 0;
-  if (conv_f32_wgrad_sc_route(s, algo != 0) == CONV_F32_SPLIT) {
+  if (f32_plan(s, CONV_WGRAD, true, algo).kernel == CONV_F32_SPLIT) {
     GUARD(return conv_f32x_s2_wgrad(s, x, dy, dsc, dw, dwsc, scale, (float*)ws, ws_bytes, S(stream));)
   }
   DTC_CHECK_ARG(ws_bytes >= (size_t)s.K * 9 * s.C * 4,
@@ -447,7 +438,7 @@ int dtc_conv2d_f32_wgrad_sc(const dtc_conv_desc* d, const float* x, const float*
                 (size_t)s.K * 9 * s.C * 4, ws_bytes);
   GUARD(
     DTC_TRY(conv_f32(s, CONV_WGRAD, x, dy, nullptr, nullptr, nullptr, dw, 0, 0, scale, (float*)ws, ws_bytes, S(stream)));
-    return conv_f32(sc_shape_of(s), CONV_WGRAD, x, dsc, nullptr, nullptr, nullptr, dwsc, 0, 0, scale, (float*)ws,
+    return conv_f32(conv_f32_sc_shape(s), CONV_WGRAD, x, dsc, nullptr, nullptr, nullptr, dwsc, 0, 0, scale, (float*)ws,
                     ws_bytes, S(stream));)
 }
 

@@ -197,8 +197,7 @@ __global__ void __launch_bounds__(256) conv_f32x_kernel(const FxParams p) {
   f32x4 pf[FX_UNITS][2];  // the next chunk's halo, fp32, in flight / held until the chunk boundary
   auto load_unit = [&](int u, int cc) {
     const uint32_t o = hoff[u] == DMA_OOB ? DMA_OOB : hoff[u] + (uint32_t)(cc * 256);
-    pf[u][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, o, 0, 0));
-    pf[u][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, o + 16u, 0, 0));
+    f32x_load16(rs, o, pf[u]);
   };
   auto write_halo = [&]() {  // split the held chunk and write its three images
 #pragma unroll

@@ -184,8 +184,7 @@ __global__ void __launch_bounds__(256) conv_f32x_s2_kernel(const S2xParams p) {
   auto load_unit = [&](int u, int cc) {
     const uint32_t o = hoff[u] == DMA_OOB ? DMA_OOB : hoff[u] + (uint32_t)(cc * 256);
     const __amdgpu_buffer_rsrc_t r = (!FWD && u == UNITS - 1) ? rs2 : rs;
-    pf[u][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, o, 0, 0));
-    pf[u][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, o + 16u, 0, 0));
+    f32x_load16(r, o, pf[u]);
   };
   auto write_halo = [&]() {  // split the held chunk and write its three images
 #pragma unroll

@@ -84,8 +84,6 @@ struct XsParams {
   u64* ts;
 };
 
-// the trswz swizzle of LDS row r as an 8-B unit XOR
-__device__ __forceinline__ int xs_uswz(int r) { return (((r >> 1) & 1) << 2) | (((r >> 3) & 1) << 3); }
 
 __global__ void __launch_bounds__(512) conv_f32x_s2_wgrad_kernel(const XsParams p) {
   __shared__ __attribute__((aligned(1024))) char smem[2 * XS_STAGE];
@@ -124,10 +122,6 @@ __global__ void __launch_bounds__(512) conv_f32x_s2_wgrad_kernel(const XsParams 
   const int dchunk = (wave >= 6 ? 4 : 0) + dch;           // its chunk of the shared dy | dsc row
   const uint32_t drel = (uint32_t)((drow * p.K + k0 + dch * 8) * 4);
   f32x4 pf[XS_UNITS + 1][2];  // the next step's operands, fp32, in flight / held until the step boundary
-  auto load16 = [](const __amdgpu_buffer_rsrc_t& r, uint32_t o, f32x4 (&d)[2]) {
-    d[0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, o, 0, 0));
-    d[1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, o + 16u, 0, 0));
-  };
   auto load_step = [&](int step) {
     int n0, y0;  // first image and first output row of the step
     if (p.imgs == 1) {
@@ -143,29 +137,21 @@ __global__ void __launch_bounds__(512) conv_f32x_s2_wgrad_kernel(const XsParams 
       if (u == XS_UNITS - 1 && wave >= 7) break;  // rows 128 .. 179: waves 0 .. 6
       const int i = hyi[u] >> 16, y = 2 * y0 + (hyi[u] & 0xffff) - 1;  // y <= H - 1; -1: the top padding
       const bool ok = hyi[u] >= 0 && n0 + i < p.N && y >= 0;
-      load16(rx, ok ? (uint32_t)(base + hrel[u]) : DMA_OOB, pf[u]);
+      f32x_load16(rx, ok ? (uint32_t)(base + hrel[u]) : DMA_OOB, pf[u]);
     }
     if (wave >= 4) {
       const int m = step * 32 + drow;
-      load16(rd, m < M ? (uint32_t)(step * 32 * p.K * 4) + drel : DMA_OOB, pf[XS_UNITS]);
+      f32x_load16(rd, m < M ? (uint32_t)(step * 32 * p.K * 4) + drel : DMA_OOB, pf[XS_UNITS]);
     }
-  };
-  auto split_write = [&](const f32x4 (&v2)[2], char* dst, int plane_bytes) {
-    const float v[8] = {v2[0][0], v2[0][1], v2[0][2], v2[0][3], v2[1][0], v2[1][1], v2[1][2], v2[1][3]};
-    uint4 q0, q1, q2;
-    split8(v, q0, q1, q2);
-    *(uint4*)dst = q0;
-    *(uint4*)(dst + plane_bytes) = q1;
-    *(uint4*)(dst + 2 * plane_bytes) = q2;
   };
   auto write_step = [&](char* sb) {  // split the held step and write its six images
 #pragma unroll
     for (int u = 0; u < XS_UNITS; ++u) {
       if (u == XS_UNITS - 1 && wave >= 7) break;
       const int hr = (u * 512 + t) >> 3;
-      if (u < XS_UNITS - 1 || hr < XS_HROWS) split_write(pf[u], sb + hr * 128 + ((pc ^ trswz(hr)) << 4), XS_HPL);
+      if (u < XS_UNITS - 1 || hr < XS_HROWS) f32x_split_write(pf[u], sb + hr * 128 + ((pc ^ trswz(hr)) << 4), XS_HPL);
     }
-    if (wave >= 4) split_write(pf[XS_UNITS], sb + XS_DY + drow * 128 + ((dchunk ^ trswz(drow)) << 4), XS_DPL);
+    if (wave >= 4) f32x_split_write(pf[XS_UNITS], sb + XS_DY + drow * 128 + ((dchunk ^ trswz(drow)) << 4), XS_DPL);
   };
 
   // ---- fragments. Lane (lg, lq, lp) of a tr read h addresses position 8 lg + lq + 4 h of the step, 8-B unit
@@ -181,8 +167,8 @@ __global__ void __launch_bounds__(512) conv_f32x_s2_wgrad_kernel(const XsParams 
     const int ii = tp / spi, rem = tp - ii * spi;
     const int pr = rem / p.Wo, q = rem - pr * p.Wo;
     hm[h] = ii * p.hb + 2 * pr * pitch + q;
-    b0[h] = (uint32_t)(XS_DY + tp * 128 + (((wn * 4 + lp) ^ xs_uswz(tp)) << 3));
-    b1[h] = (uint32_t)(XS_DY + tp * 128 + ((((wm == 3 ? 8 : 0) + wn * 4 + lp) ^ xs_uswz(tp)) << 3));
+    b0[h] = (uint32_t)(XS_DY + tp * 128 + (((wn * 4 + lp) ^ f32x_uswz(tp)) << 3));
+    b1[h] = (uint32_t)(XS_DY + tp * 128 + ((((wm == 3 ? 8 : 0) + wn * 4 + lp) ^ f32x_uswz(tp)) << 3));
   }
   uint32_t ao[10][2];  // x fragment i: GEMM row = tap 64 + channel; tap 9 (the shortcut) reads the centre tap
 #pragma unroll
@@ -193,7 +179,7 @@ __global__ void __launch_bounds__(512) conv_f32x_s2_wgrad_kernel(const XsParams 
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int ra = hm[h] + toff;
-      ao[i][h] = (uint32_t)(ra * 128 + ((unit ^ xs_uswz(ra)) << 3));
+      ao[i][h] = (uint32_t)(ra * 128 + ((unit ^ f32x_uswz(ra)) << 3));
     }
   }
 
@@ -201,18 +187,12 @@ __global__ void __launch_bounds__(512) conv_f32x_s2_wgrad_kernel(const XsParams 
 #pragma unroll
   for (int i = 0; i < 10; ++i) acc[i] = lo[i] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  typedef __attribute__((address_space(3))) bf16x4_t lds_v4;
-  auto tr8 = [&](const char* sb, uint32_t o0, uint32_t o1) {
-    const bf16x4_t t0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_v4*)(sb + o0));
-    const bf16x4_t t1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_v4*)(sb + o1));
-    return __builtin_shufflevector(t0, t1, 0, 1, 2, 3, 4, 5, 6, 7);
-  };
   auto compute = [&](const char* sb) {
     bf16x8 bd[2][3];  // [0]: fragments 0 .. 5, [1]: fragments 6 .. 9
 #pragma unroll
     for (int pl = 0; pl < 3; ++pl) {
-      bd[0][pl] = tr8(sb + pl * XS_DPL, b0[0], b0[1]);
-      bd[1][pl] = tr8(sb + pl * XS_DPL, b1[0], b1[1]);
+      bd[0][pl] = f32x_tr8(sb + pl * XS_DPL, b0[0], b0[1]);
+      bd[1][pl] = f32x_tr8(sb + pl * XS_DPL, b1[0], b1[1]);
     }
 #pragma unroll
     for (int i = 0; i < 10; i += 2) {
@@ -220,7 +200,7 @@ __global__ void __launch_bounds__(512) conv_f32x_s2_wgrad_kernel(const XsParams 
 #pragma unroll
       for (int e = 0; e < 2; ++e)
 #pragma unroll
-        for (int pl = 0; pl < 3; ++pl) ax[e][pl] = tr8(sb + pl * XS_HPL, ao[i + e][0], ao[i + e][1]);
+        for (int pl = 0; pl < 3; ++pl) ax[e][pl] = f32x_tr8(sb + pl * XS_HPL, ao[i + e][0], ao[i + e][1]);
       const bf16x8(&b)[3] = bd[i >= 6];
       constexpr int PX[6] = {2, 1, 0, 1, 0, 0}, PD[6] = {0, 1, 2, 0, 1, 0};  // (x plane, dy plane)
 #pragma unroll
@@ -307,22 +287,12 @@ bool conv_f32x_s2_wgrad_ok(const ConvShape& s) {
   return s.W / 2 != 16 || (int64_t)g.nsteps * (s.C / 64) * (s.K / XS_BK) >= 2048;
 }
 
-// Splits that fill the chip's 256 CUs with (tiles x splits) workgroups, at least four steps each (xw_splits' rule)
-static int xs_splits(const ConvShape& s, const XsGeom& g) {
-  const int tiles = (s.C / 64) * (s.K / XS_BK);
-  return std::min(std::max(1, 256 / tiles), std::max(1, g.nsteps / 4));
-}
-// `splits` equal shares of nsteps, none empty: the splits that run
-static int xs_splits_run(int nsteps, int splits) {
-  const int per = (nsteps + splits - 1) / splits;
-  return (nsteps + per - 1) / per;
-}
-
 size_t conv_f32x_s2_wgrad_workspace(const ConvShape& s) {
   XsGeom g;
   if (!xs_geometry(s, g)) return 0;
-  const int splits = xs_splits_run(g.nsteps, xs_splits(s, g));
-  return splits == 1 ? 0 : (size_t)splits * s.K * 10 * s.C * 4;
+  const size_t one = (size_t)s.K * 10 * s.C * 4;
+  const int splits = f32x_wgrad_splits_on_hand((s.C / 64) * (s.K / XS_BK), g.nsteps, one, SIZE_MAX);
+  return splits == 1 ? 0 : splits * one;
 }
 
 int conv_f32x_s2_wgrad(const ConvShape& s, const float* x, const float* dy, const float* dsc, float* dw, float* dwsc,
@@ -332,12 +302,8 @@ int conv_f32x_s2_wgrad(const ConvShape& s, const float* x, const float* dy, cons
   DTC_CHECK_ARG(x && dy && dsc && dw && dwsc && aligned(x, 16) && aligned(dy, 16) && aligned(dsc, 16) &&
                     aligned(dw, 16) && aligned(dwsc, 16) && (!slab || aligned(slab, 16)),
                 "conv_f32x_s2_wgrad: null / misaligned argument");
-  const int C10 = 10 * s.C;
-  const size_t one = (size_t)s.K * C10 * 4;
-  int splits = xs_splits(s, g);
-  if (!slab) slab_bytes = 0;
-  splits = (int)std::min<size_t>(splits, slab_bytes / one);  // the slab on hand bounds the splits ...
-  splits = xs_splits_run(g.nsteps, std::max(1, splits));     // ... and one split needs none
+  const int C10 = 10 * s.C, tiles = (s.C / 64) * (s.K / XS_BK);
+  const int splits = f32x_wgrad_splits_on_hand(tiles, g.nsteps, (size_t)s.K * C10 * 4, slab ? slab_bytes : 0);
   XsParams p{};
   p.x = x; p.dy = dy; p.dsc = dsc;
   if (splits == 1) {
@@ -359,7 +325,7 @@ int conv_f32x_s2_wgrad(const ConvShape& s, const float* x, const float* dy, cons
   p.nsteps = g.nsteps;
   p.steps_per_split = (g.nsteps + splits - 1) / splits;
   p.ts = ts;
-  const dim3 grid((unsigned)((s.C / 64) * (s.K / XS_BK)), (unsigned)splits);
+  const dim3 grid((unsigned)tiles, (unsigned)splits);
   DTC_KLAUNCH(conv_f32x_s2_wgrad_kernel, grid, dim3(512), 0, st, p);
   DTC_LAUNCH_CHECK();
   if (splits == 1) return 0;

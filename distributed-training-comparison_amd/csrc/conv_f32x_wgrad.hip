@@ -74,8 +74,6 @@ struct XwParams {
 
 // pixel (within the 64-pixel step) of k-step ks, lane block b = lane >> 4, tr read h, lane quad q
 __device__ __forceinline__ int xw_pixel(int ks, int b, int h, int q) { return ks * 32 + 8 * b + q + 4 * h; }
-// the trswz swizzle of LDS row r as an 8-B unit XOR
-__device__ __forceinline__ int xw_uswz(int r) { return (((r >> 1) & 1) << 2) | (((r >> 3) & 1) << 3); }
 
 // GEN = 1, the general (row segment) geometry of tile_common.h, for rows the classic step does not cover (224 / 112 /
 // 56 / 28 / 14 / 7 wide) and tensors past 2 GiB: a step is rs rows x one seg-column segment of ONE image (the pair is
@@ -132,10 +130,6 @@ __global__ void __launch_bounds__(512) conv_f32x_wgrad_kernel(const XwParams p) 
     drel = dr < p.rows ? (uint32_t)(((dr * p.W + drow - dr * p.seg) * p.K + k0 + pc * 8) * 4) : DMA_OOB;
   }
   f32x4 pf[XW_UNITS + 1][2];  // the next step's operands, fp32, in flight / held until the step boundary
-  auto load16 = [](const __amdgpu_buffer_rsrc_t& r, uint32_t o, f32x4 (&d)[2]) {
-    d[0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, o, 0, 0));
-    d[1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, o + 16u, 0, 0));
-  };
   auto load_step = [&](int step) {
     if constexpr (GEN) {
       int n0, y0, q0;
@@ -152,9 +146,9 @@ __global__ void __launch_bounds__(512) conv_f32x_wgrad_kernel(const XwParams p) 
         if (u == XW_UNITS - 1 && wave >= 2) break;  // rows 128 .. 143: waves 0 and 1
         const int y = y0 + (hyi[u] & 0xffff) - 1, xc = q0 + (hyi[u] >> 16) - 1;
         const bool ok = hyi[u] >= 0 && (unsigned)y < (unsigned)p.H && (unsigned)xc < (unsigned)p.W;
-        load16(gx, ok ? pix0 * (uint32_t)(p.C * 4) + (uint32_t)hrel[u] : DMA_OOB, pf[u]);
+        f32x_load16(gx, ok ? pix0 * (uint32_t)(p.C * 4) + (uint32_t)hrel[u] : DMA_OOB, pf[u]);
       }
-      load16(gd, drel != DMA_OOB ? pix0 * (uint32_t)(p.K * 4) + drel : DMA_OOB, pf[XW_UNITS]);
+      f32x_load16(gd, drel != DMA_OOB ? pix0 * (uint32_t)(p.K * 4) + drel : DMA_OOB, pf[XW_UNITS]);
       return;
     }
     int n0, y0;
@@ -171,27 +165,19 @@ __global__ void __launch_bounds__(512) conv_f32x_wgrad_kernel(const XwParams p) 
       if (u == XW_UNITS - 1 && wave >= 2) break;  // rows 128 .. 143: waves 0 and 1
       const int i = hyi[u] >> 16, y = y0 + (hyi[u] & 0xffff) - 1;
       const bool ok = hyi[u] >= 0 && n0 + i < p.N && (unsigned)y < (unsigned)p.H;
-      load16(rx, ok ? (uint32_t)(base + hrel[u]) : DMA_OOB, pf[u]);
+      f32x_load16(rx, ok ? (uint32_t)(base + hrel[u]) : DMA_OOB, pf[u]);
     }
     const int m = step * 64 + drow;
-    load16(rd, m < M ? (uint32_t)(step * 64 * p.K * 4) + drel : DMA_OOB, pf[XW_UNITS]);
-  };
-  auto split_write = [&](const f32x4 (&v2)[2], char* dst, int plane_bytes) {
-    const float v[8] = {v2[0][0], v2[0][1], v2[0][2], v2[0][3], v2[1][0], v2[1][1], v2[1][2], v2[1][3]};
-    uint4 q0, q1, q2;
-    split8(v, q0, q1, q2);
-    *(uint4*)dst = q0;
-    *(uint4*)(dst + plane_bytes) = q1;
-    *(uint4*)(dst + 2 * plane_bytes) = q2;
+    f32x_load16(rd, m < M ? (uint32_t)(step * 64 * p.K * 4) + drel : DMA_OOB, pf[XW_UNITS]);
   };
   auto write_step = [&](char* sb) {  // split the held step and write its six images
 #pragma unroll
     for (int u = 0; u < XW_UNITS; ++u) {
       if (u == XW_UNITS - 1 && wave >= 2) break;
       const int hr = (u * 512 + t) >> 3;
-      split_write(pf[u], sb + hr * 128 + ((pc ^ trswz(hr)) << 4), XW_HPL);
+      f32x_split_write(pf[u], sb + hr * 128 + ((pc ^ trswz(hr)) << 4), XW_HPL);
     }
-    split_write(pf[XW_UNITS], sb + XW_DY + drow * 128 + ((pc ^ trswz(drow)) << 4), XW_DPL);
+    f32x_split_write(pf[XW_UNITS], sb + XW_DY + drow * 128 + ((pc ^ trswz(drow)) << 4), XW_DPL);
   };
 
   // ---- per-lane halo row, at tap (0, 0), of the pixels this lane's tr reads address
@@ -219,7 +205,7 @@ __global__ void __launch_bounds__(512) conv_f32x_wgrad_kernel(const XwParams p) 
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
     const int kr = xw_pixel(0, lg, h, lq);
-    b0[h] = (uint32_t)(XW_DY + kr * 128 + (((wn * 8 + lp) ^ xw_uswz(kr)) << 3));
+    b0[h] = (uint32_t)(XW_DY + kr * 128 + (((wn * 8 + lp) ^ f32x_uswz(kr)) << 3));
   }
 
   f32x4 acc[9][2], lo[9][2];
@@ -228,12 +214,6 @@ __global__ void __launch_bounds__(512) conv_f32x_wgrad_kernel(const XwParams p) 
 #pragma unroll
     for (int j = 0; j < 2; ++j) acc[i][j] = lo[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  typedef __attribute__((address_space(3))) bf16x4_t lds_v4;
-  auto tr8 = [&](const char* sb, uint32_t o0, uint32_t o1) {
-    const bf16x4_t t0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_v4*)(sb + o0));
-    const bf16x4_t t1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_v4*)(sb + o1));
-    return __builtin_shufflevector(t0, t1, 0, 1, 2, 3, 4, 5, 6, 7);
-  };
   auto compute = [&](const char* sb, const int (&hr)[2][2]) {
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
@@ -242,7 +222,7 @@ __global__ void __launch_bounds__(512) conv_f32x_wgrad_kernel(const XwParams p) 
       for (int pl = 0; pl < 3; ++pl)
 #pragma unroll
         for (int j = 0; j < 2; ++j)
-          bd[pl][j] = tr8(sb + pl * XW_DPL + ks * 4096, b0[0] ^ (uint32_t)(j * 32), b0[1] ^ (uint32_t)(j * 32));
+          bd[pl][j] = f32x_tr8(sb + pl * XW_DPL + ks * 4096, b0[0] ^ (uint32_t)(j * 32), b0[1] ^ (uint32_t)(j * 32));
 #pragma unroll
       for (int i = 0; i < 9; ++i) {
         const int row = wm * 144 + i * 16;  // GEMM row = tap 64 + channel
@@ -252,11 +232,11 @@ __global__ void __launch_bounds__(512) conv_f32x_wgrad_kernel(const XwParams p) 
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           const int ra = hr[ks][h] + toff;
-          ao[h] = (uint32_t)(ra * 128 + ((unit ^ xw_uswz(ra)) << 3));
+          ao[h] = (uint32_t)(ra * 128 + ((unit ^ f32x_uswz(ra)) << 3));
         }
         bf16x8 ax[3];
 #pragma unroll
-        for (int pl = 0; pl < 3; ++pl) ax[pl] = tr8(sb + pl * XW_HPL, ao[0], ao[1]);
+        for (int pl = 0; pl < 3; ++pl) ax[pl] = f32x_tr8(sb + pl * XW_HPL, ao[0], ao[1]);
         constexpr int PX[6] = {2, 1, 0, 1, 0, 0}, PD[6] = {0, 1, 2, 0, 1, 0};  // (x plane, dy plane)
 #pragma unroll
         for (int q = 0; q < 6; ++q)
@@ -393,23 +373,12 @@ bool conv_f32x_wgrad_ok(const ConvShape& s) {
   return xw_geometry_any(s, g);
 }
 
-// Splits that fill the chip's 256 CUs with (tiles x splits) workgroups, at least four steps each: a split's
-// prologue (its first loads and split, not overlapped) and its slab are paid once per workgroup
-static int xw_splits(const ConvShape& s, const XwGeom& g) {
-  const int tiles = (s.C / 64) * (s.K / 64);
-  return std::min(std::max(1, 256 / tiles), std::max(1, g.nsteps / 4));
-}
-// `splits` equal shares of nsteps, none empty: the splits that run
-static int xw_splits_run(int nsteps, int splits) {
-  const int per = (nsteps + splits - 1) / splits;
-  return (nsteps + per - 1) / per;
-}
-
 size_t conv_f32x_wgrad_workspace(const ConvShape& s) {
   XwGeom g;
   if (!xw_geometry_any(s, g)) return 0;
-  const int splits = xw_splits_run(g.nsteps, xw_splits(s, g));
-  return splits == 1 ? 0 : (size_t)splits * s.K * 9 * s.C * 4;
+  const size_t one = (size_t)s.K * 9 * s.C * 4;
+  const int splits = f32x_wgrad_splits_on_hand((s.C / 64) * (s.K / 64), g.nsteps, one, SIZE_MAX);
+  return splits == 1 ? 0 : splits * one;
 }
 
 int conv_f32x_wgrad(const ConvShape& s, const float* x, const float* dy, float* dw, float scale, float* slab,
@@ -418,11 +387,8 @@ int conv_f32x_wgrad(const ConvShape& s, const float* x, const float* dy, float* 
   DTC_CHECK_ARG(xw_geometry_any(s, g), "conv_f32x_wgrad: unsupported shape");
   DTC_CHECK_ARG(x && dy && dw && aligned(x, 16) && aligned(dy, 16) && aligned(dw, 16) && (!slab || aligned(slab, 16)),
                 "conv_f32x_wgrad: null / misaligned argument");
-  const size_t one = (size_t)s.K * 9 * s.C * 4;
-  int splits = xw_splits(s, g);
-  if (!slab) slab_bytes = 0;
-  splits = (int)std::min<size_t>(splits, slab_bytes / one);  // the slab on hand bounds the splits ...
-  splits = xw_splits_run(g.nsteps, std::max(1, splits));     // ... and one split needs none
+  const int tiles = (s.C / 64) * (s.K / 64);
+  const int splits = f32x_wgrad_splits_on_hand(tiles, g.nsteps, (size_t)s.K * 9 * s.C * 4, slab ? slab_bytes : 0);
   XwParams p{};
   p.x = x; p.dy = dy;
   p.out = splits == 1 ? dw : slab;
@@ -442,7 +408,7 @@ int conv_f32x_wgrad(const ConvShape& s, const float* x, const float* dy, float* 
     p.fd_tpi = make_fastdiv(g.g.tpi);
     p.fd_spr = make_fastdiv(g.g.spr);
   }
-  const dim3 grid((unsigned)((s.C / 64) * (s.K / 64)), (unsigned)splits);
+  const dim3 grid((unsigned)tiles, (unsigned)splits);
   if (g.gen) DTC_KLAUNCH(conv_f32x_wgrad_kernel<1>, grid, dim3(512), 0, st, p);
   else DTC_KLAUNCH(conv_f32x_wgrad_kernel<0>, grid, dim3(512), 0, st, p);
   DTC_LAUNCH_CHECK();

@@ -86,29 +86,6 @@ ConvRoute conv_route(const ConvShape& s, int pass, const ConvRequest& rq) {
   return r;
 }
 
-// The fp32 convs' router: the split-bf16 kernels serve the shapes their predicates accept when the caller asks for
-// them (FWD / DGRAD: and has the weight planes; WGRAD splits both operands itself); everything else is conv_f32
-int conv_f32_route(const ConvShape& s, int pass, bool want_split, bool planes) {
-  if (!want_split) return CONV_F32_EXACT;
-  if (pass == CONV_WGRAD) return conv_f32x_wgrad_ok(s) ? CONV_F32_SPLIT : CONV_F32_EXACT;
-  return planes && (pass == CONV_FWD || pass == CONV_DGRAD) && conv_f32x_ok(s) ? CONV_F32_SPLIT : CONV_F32_EXACT;
-}
-
-// The transition blocks' fused pair (conv1 3x3 stride 2 + the 1x1 stride-2 shortcut, FWD / DGRAD): the split-bf16
-// kernel (conv_f32x_s2) when the caller asks for it, has both weights' planes and its predicate accepts conv1's
-// shape; else the exact pair, two conv_f32 launches
-int conv_f32_sc_route(const ConvShape& s, int pass, bool want_split, bool planes) {
-  return want_split && planes && (pass == CONV_FWD || pass == CONV_DGRAD) && conv_f32x_s2_ok(s, pass) ? CONV_F32_SPLIT
-                                                                                                : CONV_F32_EXACT;
-}
-
-// The transition blocks' fused weight-gradient pair (conv1's dw + the shortcut's): the split-bf16 kernel
-// (conv_f32x_s2_wgrad) when the caller asks for it and its predicate accepts conv1's shape; it splits all three
-// operands itself, so no weight planes are involved. Else the exact pair, two conv_f32 weight gradients
-int conv_f32_wgrad_sc_route(const ConvShape& s, bool want_split) {
-  return want_split && conv_f32x_s2_wgrad_ok(s) ? CONV_F32_SPLIT : CONV_F32_EXACT;
-}
-
 static ConvRequest with_slab(const float* slab, size_t slab_bytes) {
   ConvRequest rq;
   rq.slab_bytes = slab ? slab_bytes : 0;

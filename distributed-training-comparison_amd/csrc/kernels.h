@@ -65,7 +65,7 @@ namespace dtc {
   X(COMM_TAIL_INLINE, comm_tail_inline, 1) /* the last bucket's all-reduce on the compute stream (no fork / join) */ \
   X(DGRAD_S2H, dgrad_s2h, 1)            /* stride-2 3x3 dgrad (+ shortcut) as a halo sub-pixel conv: 1 K <= 256, 2 all */ \
   X(HALO_SMALL, halo_small, 1)          /* halo FWD/DGRAD: 64x64 double-buffered tiles where they give <= 512 workgroups */ \
-  X(F32_SPLIT, f32_split, 0)            /* (plan time) fp32 executor: 3x3 s1 FWD/DGRAD on the split-bf16 kernel (conv_f32x); 2: WGRAD too; 3: + the transition blocks' FWD / DGRAD (conv_f32x_s2); 4: + their WGRAD (conv_f32x_s2_wgrad) */ \
+  X(F32_SPLIT, f32_split, 0)            /* (plan time) fp32 executor: the passes that ask for the split-bf16 kernels, by conv_f32_route.cpp's level table: 1 3x3 s1 FWD/DGRAD (conv_f32x); 2: WGRAD too; 3: + the transition blocks' FWD / DGRAD (conv_f32x_s2); 4: + their WGRAD (conv_f32x_s2_wgrad) */ \
   X(F32X_S2_FWD, f32x_s2_fwd, 1)        /* conv_f32x_s2 FWD_SC: 1 where it measured faster than the exact pair, 2 every feasible geometry (to measure) */ \
   X(F32X_S2_WGRAD, f32x_s2_wgrad, 1)    /* conv_f32x_s2_wgrad: 1 where it measured faster than the exact pair, 2 every feasible geometry (to measure) */ \
   X(F32X_GEN, f32x_gen, 0)              /* conv_f32x / conv_f32x_wgrad general (row-segment) tiles, the 224x224 geometry: 0 classic rows only, 1 where it measured faster than conv_f32, 2 every feasible geometry (to measure) */
@@ -274,9 +274,6 @@ int conv_f32x_s2_fwd(const ConvShape& s, const float* x, const u16* wplanes, int
                      u64* ts = nullptr);
 int conv_f32x_s2_dgrad(const ConvShape& s, const float* dy, const u16* wplanes, int64_t wstride, float* dx,
                        const float* dsc, const u16* wsc_planes, int64_t wsc_stride, hipStream_t st, u64* ts = nullptr);
-// The fused pair's route (conv_route.cpp): CONV_F32_SPLIT when the split is asked for, both weights' planes exist and
-// conv_f32x_s2_ok holds; else CONV_F32_EXACT, the two conv_f32 launches per pass (FWD / DGRAD only)
-int conv_f32_sc_route(const ConvShape& s, int pass, bool want_split, bool planes);
 // Split-bf16 weight gradients of a projection block (conv_f32x_s2_wgrad.hip): conv1's (3x3 / stride 2 / pad 1) dw and
 // the 1x1 stride-2 shortcut's dwsc = scale * sum dsc (x) x in one launch, x, dy and dsc fp32 and split in the kernel.
 // Split-K over 32-position steps into fp32 slabs [split][K][10 C] summed by f32_wgrad_reduce; the splits are lowered
@@ -287,14 +284,19 @@ bool conv_f32x_s2_wgrad_ok(const ConvShape& s);
 size_t conv_f32x_s2_wgrad_workspace(const ConvShape& s);
 int conv_f32x_s2_wgrad(const ConvShape& s, const float* x, const float* dy, const float* dsc, float* dw, float* dwsc,
                        float scale, float* slab, size_t slab_bytes, hipStream_t st, u64* ts = nullptr);
-// The fused weight-gradient pair's route (conv_route.cpp): CONV_F32_SPLIT when the split is asked for and
-// conv_f32x_s2_wgrad_ok holds (no weight planes needed); else CONV_F32_EXACT, the two conv_f32 weight gradients
-int conv_f32_wgrad_sc_route(const ConvShape& s, bool want_split);
-// Which kernel an fp32 pass runs on (conv_route.cpp): CONV_F32_SPLIT when the split is asked for (the executor:
-// option f32_split, 1 for FWD / DGRAD and 2 for WGRAD too; the C ABI: algo) and the pass's predicate holds
-// (conv_f32x_ok and the weight planes exist; WGRAD: conv_f32x_wgrad_ok); else CONV_F32_EXACT (conv_f32).
+// The fp32 convs' planner (conv_f32_route.cpp, which has the table): the kernel an fp32 pass runs on and the slab that
+// route wants. sc: the launch is a projection block's conv1 (the shape) together with its 1x1 shortcut
+// (conv_f32_sc_shape). CONV_F32_SPLIT when the split is wanted (the executor: conv_f32_split_on, the level table of
+// option f32_split; the C ABI: algo != 0), the pass's predicate holds and, for FWD / DGRAD, the weight planes exist;
+// else CONV_F32_EXACT: conv_f32, for the pair two launches.
 enum { CONV_F32_EXACT = 0, CONV_F32_SPLIT = 1 };
-int conv_f32_route(const ConvShape& s, int pass, bool want_split, bool planes);
+struct ConvF32Plan {
+  int kernel = CONV_F32_EXACT;
+  size_t slab_bytes = 0;
+};
+bool conv_f32_split_on(int pass, bool sc);
+ConvShape conv_f32_sc_shape(const ConvShape& s);
+ConvF32Plan conv_f32_plan(const ConvShape& s, int pass, bool sc, bool want_split, bool planes);
 int f32_stem_im2col(const float* x, float* cols, int N, int H, int W, hipStream_t st);  // [N*H*W][32]
 int f32_stem_pack_weight(const float* w27, float* w32, int K, hipStream_t st);          // [K][27] -> [K][32]
 

@@ -206,10 +206,12 @@ static void plan_workspace(Net& n, float bucket_cap_mb) {
   auto consider = [&](const ConvShape& s) {
     for (int m = 0; m < 3; ++m)
       slab = std::max(slab, n.f32 ? f32_conv_workspace(s, m) : conv_route(s, m).slab_bytes);
-    // option f32_split = 2: the split-bf16 weight gradient's slabs (the only value that may enlarge the slab)
-    if (n.f32 && option_get(OPT_F32_SPLIT) >= 2 && conv_f32x_wgrad_ok(s)) slab = std::max(slab, conv_f32x_wgrad_workspace(s));
-    // 4: the transition blocks' fused weight gradient's (0 for any other shape; 3 plans what 2 does)
-    if (n.f32 && option_get(OPT_F32_SPLIT) >= 4 && conv_f32x_s2_wgrad_ok(s)) slab = std::max(slab, conv_f32x_s2_wgrad_workspace(s));
+  };
+  // fp32: beside conv_f32's slab (above: a partial dw always runs on it) the slab of the route conv_f32_plan picks; sc:
+  // conv1 + shortcut launched as a pair. Only the split weight gradients' slabs can enlarge it (f32_split 2 and 4)
+  auto consider_f32 = [&](const ConvShape& s, bool sc) {
+    for (int m = 0; m < 3; ++m)
+      slab = std::max(slab, conv_f32_plan(s, m, sc, conv_f32_split_on(m, sc), true).slab_bytes);
   };
   auto consider_batch = [&](const ConvShape& s) {  // a bucket's 3x3 stride-1 wgrads, 2..DTC_WG_BATCH per launch
     ConvRequest rq;
@@ -222,6 +224,11 @@ static void plan_workspace(Net& n, float bucket_cap_mb) {
     consider(b.c1.s);
     consider(b.c2.s);
     if (b.proj) consider(b.sc.s);
+    if (n.f32) {
+      consider_f32(b.c1.s, false);
+      consider_f32(b.c2.s, false);
+      if (b.proj) consider_f32(b.c1.s, true);
+    }
     if (!n.f32) {  // (conv1 + shortcut in one wgrad_s2 launch: its slab is conv1's own WGRAD route's)
       consider_batch(b.c1.s);
       consider_batch(b.c2.s);
@@ -235,18 +242,23 @@ static void plan_workspace(Net& n, float bucket_cap_mb) {
   // option f32_split (fp32): the bf16 weight planes of the convs the split kernel serves, rewritten by every forward
   p.WPL = 0;
   p.wpl_lo = p.wpl_n = 0;
-  if (n.f32 && option_get(OPT_F32_SPLIT) != 0) {
+  if (n.f32) {
     int64_t lo = INT64_MAX, hi = 0;
     auto cover = [&](const ConvL& c) {
       lo = std::min(lo, n.params[c.pidx].offset);
       hi = std::max(hi, align_up(n.params[c.pidx].offset + n.params[c.pidx].numel, 64));
     };
+    // the routes that read planes: FWD / DGRAD of a conv, or of a transition block's pair, that go to a split kernel
+    // (DGRAD decides for both passes: conv_f32x_s2's forward is refused at sizes where its data gradient is not)
+    auto split = [&](const ConvShape& s, bool sc) {
+      return conv_f32_plan(s, CONV_DGRAD, sc, conv_f32_split_on(CONV_DGRAD, sc), true).kernel == CONV_F32_SPLIT;
+    };
     for (auto& b : n.blocks) {
       for (const ConvL* c : {&b.c1, &b.c2})
-        if (conv_f32x_ok(c->s)) cover(*c);
-      // 3: the transition blocks' conv1 and shortcut (conv_f32x_s2). In ResNet-18's parameter order they lie between
-      // layer1's and layer4's stride-1 convs, so the range -- and the workspace -- is the one planned at 2
-      if (option_get(OPT_F32_SPLIT) >= 3 && b.proj && conv_f32x_s2_ok(b.c1.s, CONV_DGRAD)) {
+        if (split(c->s, false)) cover(*c);
+      // In ResNet-18's parameter order the pairs lie between layer1's and layer4's stride-1 convs, so the range -- and
+      // the workspace -- is the one planned without them
+      if (b.proj && split(b.c1.s, true)) {
         cover(b.c1);
         cover(b.sc);
       }

@@ -213,23 +213,20 @@ static int64_t* stats_if(Net& n, const BNL& b, bool train) { return train ? n.at
 // flops < 0: the conv's own): y = conv(x, w) (+ BN statistics), dx = conv_transpose(dy, w) (+ res),
 // dw[k][0:cols] = gs * sum dy (x) im2col(x)
 // wpl (FWD / DGRAD of a block's conv): plane 0 of the weight's bf16 planes where they are planned (option f32_split);
-// conv_f32_route then sends the shapes conv_f32x serves to it (the same algorithmic FLOPs: the six plane products
-// are the kernel's business)
+// conv_f32_plan then sends the shapes conv_f32x serves to it (the same algorithmic FLOPs: the six plane products
+// are the kernel's business). A partial dw (cols: the stem) is conv_f32's alone
 static int f32_conv(Net& n, int mode, const ConvShape& s, const float* a, const float* b, float* out, const float* res,
                     int64_t* stats, float* dw, int cols, float gs, hipStream_t st, double flops,
                     const u16* wpl = nullptr) {
-  // option f32_split: 1 = FWD / DGRAD, 2 = the weight gradient too (it splits both operands itself: no planes)
-  const bool want = option_get(OPT_F32_SPLIT) >= (mode == CONV_WGRAD ? 2 : 1);
-  if (conv_f32_route(s, mode, want, wpl != nullptr) == CONV_F32_SPLIT) {
-    if (mode == CONV_WGRAD && cols == 0) {
+  const bool want = cols == 0 && conv_f32_split_on(mode, false);
+  if (conv_f32_plan(s, mode, false, want, wpl != nullptr).kernel == CONV_F32_SPLIT) {
+    if (mode == CONV_WGRAD) {
       PROF(mode, flops < 0 ? conv_flops(s) : flops,
            conv_f32x_wgrad(s, a, b, dw, gs, n.at<float>(n.plan.SLAB), n.plan.slab_bytes, st, ts));
-      return 0;
-    }
-    if (mode != CONV_WGRAD) {
+    } else {
       PROF(mode, flops < 0 ? conv_flops(s) : flops, conv_f32x(s, mode, a, wpl, n.plan.wpl_n, out, res, stats, st, ts));
-      return 0;
     }
+    return 0;
   }
   PROF(mode, flops < 0 ? conv_flops(s) : flops,
        conv_f32(s, mode, a, b, out, res, stats, dw, cols, cols, gs, n.at<float>(n.plan.SLAB), n.plan.slab_bytes, st, ts));
@@ -241,12 +238,11 @@ static const u16* f32_planes(const Net& n, const ConvL& c) {
   const int64_t off = n.params[c.pidx].offset;
   return p.wpl_n > 0 && off >= p.wpl_lo && off + n.params[c.pidx].numel <= p.wpl_lo + p.wpl_n ? n.wpl(c.pidx) : nullptr;
 }
-// option f32_split = 3: a projection block's conv1 + shortcut, FWD / DGRAD, in one conv_f32x_s2 launch (both planes
-// planned and the shape accepted)
+// a projection block's conv1 + shortcut in one split-bf16 launch: FWD / DGRAD (conv_f32x_s2: both weights' planes
+// planned) or WGRAD (conv_f32x_s2_wgrad), where conv_f32_plan says so
 static bool f32_sc_split(const Net& n, const BlockL& b, int pass) {
-  return b.proj &&
-         conv_f32_sc_route(b.c1.s, pass, option_get(OPT_F32_SPLIT) >= 3, f32_planes(n, b.c1) && f32_planes(n, b.sc)) ==
-             CONV_F32_SPLIT;
+  return b.proj && conv_f32_plan(b.c1.s, pass, true, conv_f32_split_on(pass, true),
+                                 f32_planes(n, b.c1) && f32_planes(n, b.sc)).kernel == CONV_F32_SPLIT;
 }
 static int f32_fwd(Net& n, const ConvShape& s, const float* x, const float* w, float* y, int64_t* stats, hipStream_t st,
                    double flops = -1, const u16* wpl = nullptr) {
@@ -877,8 +873,7 @@ static int backward_body_f32(Net& n, const float* dlogits, float gs, const BwdCt
     DTC_TRY(cap(n, cp + ".dz1", G[4], st));
     DTC_TRY(bn_bwd_coef_apply(n, b.b1, G[4], n.at<float>(b.C1), dc1, nullptr, nullptr, nullptr, M, gs, st));
     DTC_TRY(cap(n, cp + ".dc1", dc1, st));
-    // option f32_split = 4: a projection block's two weight gradients in one conv_f32x_s2_wgrad launch
-    const bool wgx = b.proj && conv_f32_wgrad_sc_route(b.c1.s, option_get(OPT_F32_SPLIT) >= 4) == CONV_F32_SPLIT;
+    const bool wgx = f32_sc_split(n, b, CONV_WGRAD);  // both weight gradients in one conv_f32x_s2_wgrad launch
     if (wgx) {
       PROF(2, conv_flops(b.c1.s) + conv_flops(b.sc.s),
            conv_f32x_s2_wgrad(b.c1.s, in, dc1, dsc, n.gf(b.c1.pidx), n.gf(b.sc.pidx), gs, n.at<float>(p.SLAB),

@@ -87,6 +87,18 @@ def test_workspace_tiers_and_determinism(dtc, cuda):
         _check(what, runs[0].cpu().numpy(), x, dy)
 
 
+def test_slab_on_hand_bounds_the_splits(dtc, cuda):
+    """(8, 16, 16, 64, 64): 32 steps of four rows, one tile, so the kernel wants 8 splits. A workspace of three slabs
+    runs three (11 + 11 + 10 steps) and the reduce, none runs one split that writes dw itself: both within the bound."""
+    shape = (8, 16, 16, 64, 64)
+    x, dy = _inputs(shape, "randn")
+    one = 64 * 9 * 64 * 4
+    assert dtc._native.lib.dtc_conv2d_f32_wgrad_workspace_size(dtc.ops.conv_desc(*shape, 3, 3, 1, 1), 1) == 8 * one
+    for what, nbytes in (("three slabs", 3 * one), ("no workspace", 0)):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=cuda)
+        _check(f"wgrad {shape} {what}", _wgrad(dtc, cuda, x, dy, algo=1, workspace=ws).cpu().numpy(), x, dy)
+
+
 def test_refused_shape_runs_the_exact_kernel(dtc, cuda):
     """algo=1 at a shape the split kernel refuses (7-wide rows) is conv_f32's weight gradient, bit for bit."""
     shape = (1, 5, 7, 64, 64)

@@ -88,6 +88,18 @@ def test_workspace_tiers_and_determinism(dtc, cuda, every_geometry):
         assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]), what
 
 
+def test_slab_on_hand_bounds_the_splits(dtc, cuda, every_geometry):
+    """(8, 16, 16, 64 -> 128): 16 steps of four output rows, four tiles, so the kernel wants 4 splits. A workspace of two
+    slabs runs two and the reduces, none runs one split that writes dw and dwsc itself: both within the bound."""
+    shape = (8, 16, 16, 64, 128)
+    ins = _inputs(shape, "randn")
+    one = 128 * 10 * 64 * 4
+    assert dtc._native.lib.dtc_conv2d_f32_wgrad_sc_workspace_size(dtc.ops.conv_desc(*shape, 3, 3, 2, 1), 1) == 4 * one
+    for what, nbytes in (("two slabs", 2 * one), ("no workspace", 0)):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=cuda)
+        _run_and_check(dtc, cuda, f"wgrad_sc {shape} {what}", *ins, algo=1, workspace=ws)
+
+
 def test_exact_pair_is_the_separate_calls_and_serves_refused_shapes(dtc, cuda):
     """algo=0 equals the two conv2d_wgrad_f32(algo=0) calls bit for bit; algo=1 at a refused shape (6-wide output rows)
     equals algo=0."""

@@ -4,6 +4,7 @@
     python tools/conv_digest.py [--out FILE]           on the GPU: one line per (entry point, shape, option set)
     python tools/conv_digest.py --sizes [--out FILE]   no GPU needed: the workspace-size queries over the same grid
     python tools/conv_digest.py --routes [--out FILE]  no GPU needed: the router's answers (below)
+    python tools/conv_digest.py --f32-routes [--out FILE]  no GPU needed: the fp32 convs' planner (below)
     DTC_LIB=/path/to/other/libdtc_amd.so python tools/conv_digest.py ...    the other build; then cmp the files
 
 A GPU line holds the dtc:: kernel names in launch order (tools/step_digest.py's kernels_of; one profiler session per
@@ -20,7 +21,13 @@ dtc_conv2d_wgrad_batch_workspace_size (1..4) for every shape (also at batch 32 /
 and the descriptors the ABI rejects) under EVERY option set, and dtc_rn18_workspace_bytes of four networks.
 --routes prints one line per dtc_conv2d_route_query answer (workspace unlimited) over the whole GRID of
 tests/test_conv_route.py, under every option set of that test, for every (pass, flags, nprob) of its _requests:
-kernel, tile, splits, halo_cfg, halo_gen, sc_ok, refused, slab_wanted and slab_used."""
+kernel, tile, splits, halo_cfg, halo_gen, sc_ok, refused, slab_wanted and slab_used.
+--f32-routes prints, per (option set, shape) of F32_OPTION_SETS x f32_shapes(), what the fp32 planner answers through
+the C ABI at algo 0 and 1: dtc_conv2d_f32_route_query and dtc_conv2d_f32_sc_route_query (FWD, DGRAD),
+dtc_conv2d_f32_wgrad_route_query, dtc_conv2d_f32_wgrad_sc_route_query and the two weight-gradient workspace sizes, one
+letter per answer (e exact, s split, x error: the query rejects the descriptor; the first line names the columns); then
+dtc_rn18_workspace_bytes of fp32 executors for every (f32_split, f32x_gen). tests/golden/f32_routes.txt is this output
+of the commit before the planner; tests/test_conv_f32_plan.py compares."""
 import argparse
 import ctypes as C
 import hashlib
@@ -128,6 +135,67 @@ def routes(emit):
                     emit(f"{oid(o)} | {shape} | {mode} {flags} {nprob} | {N.CONV_KERNELS[r.kernel]} {r.gemm_bm}x{r.gemm_bn} "
                          f"splits={r.splits} halo_cfg={r.halo_cfg} halo_gen={r.halo_gen} sc_ok={r.sc_ok} "
                          f"refused={r.refused} slab_wanted={r.slab_wanted} slab_used={r.slab_used}")
+
+
+# ---------------------------------------------------------------------------------------------- fp32 planner (CPU)
+F32_OPTION_SETS = [{"f32x_gen": g, "f32x_s2_fwd": f, "f32x_s2_wgrad": w} for g in (0, 1, 2) for f in (1, 2) for w in (1, 2)]
+F32_NETS = [(8, 32, 32), (256, 32, 32), (2, 224, 224)]
+
+
+def f32_threshold_shapes():
+    """Both sides of every measured threshold in the split kernels' predicates, from their arithmetic.
+    conv_f32x_s2_ok (FWD) counts (tile, 64-channel K tile, 64-channel C chunk) units, a tile being 32 positions of the
+    [H/2][W/2] grid, and accepts at most 1024 / 4096 / 2048 of them at 16- / 8- / 4-wide output rows: the model's
+    transition shapes have 8 N x 2, 2 N x 4 x 2 and ceil(N / 2) x 8 x 4 units, so batches 64 | 65, 256 | 257, 128 | 129.
+    conv_f32x_s2_wgrad_ok refuses 16-wide rows below 2048 (32-position step, 64 C x 32 K tile) units: 8 N x 4, so
+    batches 63 | 64. fx_gen_admitted (f32x_gen = 1) wants tiles of at least 98 pixels: 14 x 14 maps fill 7 x 14 = 98,
+    10 x 14 maps 5 x 14 = 70, 7 x 7 maps 49. xw_gen_admitted (f32x_gen = 1) takes the step classes 32 x 2, 16 x 4, 8 x 8,
+    28 x 2 (the 224 / 112 / 56 / 28 wide layer shapes) and 7 x 7 (14 x 14 and 7 x 7 maps); 24 x 24 maps step 8 x 8, a
+    measured class at an unmeasured width, and 10 x 14 maps 7 x 5, no measured class."""
+    s2 = [(n, 32, 32, 64, 128) for n in (63, 64, 65)] + [(n, 16, 16, 128, 256) for n in (256, 257)] + \
+         [(n, 8, 8, 256, 512) for n in (128, 129)]
+    s1 = [(2, 14, 14, 512, 512), (2, 10, 14, 512, 512), (2, 7, 7, 512, 512), (2, 24, 24, 128, 128)]
+    return [(n, h, w, c, k, 3, 3, 2, 1) for (n, h, w, c, k) in s2] + [(n, h, w, c, k, 3, 3, 1, 1) for (n, h, w, c, k) in s1]
+
+
+def f32_shapes():
+    refused = []
+    for mod in ("test_conv_f32_split_route", "test_conv_f32_split_sc_route", "test_conv_f32_split_wgrad_route",
+                "test_conv_f32_split_wgrad_sc_route", "test_conv_f32_split_wgrad_gen_route"):
+        refused += getattr(__import__(f"tests.{mod}", fromlist=[mod]), "REFUSED", [])
+    shapes = [s for b in (2, 32, 64, 128, 256) for s in layer_shapes(b, 32)] + \
+        [s for b in (1, 2, 128) for s in layer_shapes(b, 224)] + refused + odd_shapes() + f32_threshold_shapes()
+    return list(dict.fromkeys(tuple(s) for s in shapes))
+
+
+def f32_routes(emit):
+    """Compact on purpose (the recording is a committed file): e exact, s split, x error (the descriptor rejected)."""
+    def ans(*rcs):
+        return "".join({0: "e", 1: "s"}.get(rc, "x") for rc in rcs)
+
+    emit("# options (f32x_gen, f32x_s2_fwd, f32x_s2_wgrad) | n,h,w,c,k,r,s,stride,pad | routes at algo 0 then 1: fwd dgrad "
+         "fwd_sc dgrad_sc wgrad wgrad_sc | workspace bytes at algo 0,1: wgrad wgrad_sc")
+    for o in F32_OPTION_SETS:
+        with Options(o):
+            for s in f32_shapes():
+                d = dtc._native.ConvDesc(*s)
+                one = [ans(*(lib.dtc_conv2d_f32_route_query(d, p, a) for a in (0, 1))) for p in (0, 1)]
+                sc = [ans(*(lib.dtc_conv2d_f32_sc_route_query(d, p, a) for a in (0, 1))) for p in (0, 1)]
+                wg = ans(*(lib.dtc_conv2d_f32_wgrad_route_query(d, a) for a in (0, 1)))
+                wgsc = ans(*(lib.dtc_conv2d_f32_wgrad_sc_route_query(d, a) for a in (0, 1)))
+                ws = [lib.dtc_conv2d_f32_wgrad_workspace_size(d, a) for a in (0, 1)]
+                wssc = [lib.dtc_conv2d_f32_wgrad_sc_workspace_size(d, a) for a in (0, 1)]
+                emit(f"{''.join(str(v) for v in o.values())} | {','.join(map(str, s))} | {one[0]} {one[1]} {sc[0]} {sc[1]} "
+                     f"{wg} {wgsc} | {ws[0]},{ws[1]} {wssc[0]},{wssc[1]}")
+    for split in range(5):
+        for gen in range(3):
+            with Options({"f32_split": split, "f32x_gen": gen}):
+                for (b, h, w) in F32_NETS:
+                    net = C.c_void_p()
+                    dtc._native.call("dtc_rn18_create", C.byref(net), b, h, w, 100, 25.0)
+                    dtc._native.call("dtc_rn18_set_precision", net, 1)
+                    emit(f"f32_split={split} f32x_gen={gen} | rn18 fp32 {b},{h},{w} | {lib.dtc_rn18_workspace_bytes(net)}")
+                    lib.dtc_rn18_destroy(net)
 
 
 # ---------------------------------------------------------------------------------------------- launches (GPU)
@@ -256,6 +324,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--sizes", action="store_true")
     ap.add_argument("--routes", action="store_true")
+    ap.add_argument("--f32-routes", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     f = open(a.out, "w") if a.out else None
@@ -267,7 +336,7 @@ def main():
             if not a.routes:
                 f.flush()
 
-    (sizes if a.sizes else routes if a.routes else run_gpu)(emit)
+    (sizes if a.sizes else routes if a.routes else f32_routes if a.f32_routes else run_gpu)(emit)
 
 
 if __name__ == "__main__":

@@ -228,6 +228,8 @@ def configs():
     yield "soft xent_fuse=1", {"xent_fuse": 1}, T, {"soft": True}
     yield "soft xent_fuse=0", {"xent_fuse": 0}, T, {"soft": True}
     yield "fp32", {}, T, {"precision": "fp32"}
+    for lvl in (1, 2, 3, 4):
+        yield f"fp32 f32_split={lvl}", {"f32_split": lvl}, T, {"precision": "fp32"}
     yield "capture bf16", {}, T, {"capture": True}
     yield "capture fp32", {}, T, {"capture": True, "precision": "fp32"}
     for g in (1, 2, 3):
