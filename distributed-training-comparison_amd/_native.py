@@ -179,6 +179,8 @@ _SIGS = {
     "dtc_segplan_bind": (i32, [vp, vp, sz, vp]),
     "dtc_seg_norms": (i32, [vp, vp, vp, vp, vp, vp]),
     "dtc_lars_flat": (i32, [vp, vp, vp, vp, vp, f64, f64, f64, i32, f64, f64, i32, vp, vp, vp, vp]),
+    "dtc_lamb_state_words": (i32, []),
+    "dtc_lamb_flat": (i32, [vp, vp, vp, vp, vp, vp, vp, f64, f64, f64, f64, f64, i32, f64, vp, vp, vp, vp]),
     "dtc_ema_state_words": (i32, []),
     "dtc_ema_update": (i32, [PEmaRange, i32, vp, f64, i32, vp, vp]),
     "dtc_grad_accum_flat": (i32, [vp, vp, i64, i32, vp]),

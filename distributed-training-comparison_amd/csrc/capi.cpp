@@ -721,6 +721,13 @@ int dtc_lars_flat(dtc_segplan* plan, float* p, const float* g, float* mom, uint1
   return lars_flat((SegPlan*)plan, p, g, mom, pb, lr, wd, mu, nesterov, trust_coef, eps, trust_clip, inv_scale,
                    found_inf, seg_out, S(stream));
 }
+int dtc_lamb_state_words(void) { return DTC_LAMB_STATE_WORDS; }
+int dtc_lamb_flat(dtc_segplan* plan, float* p, const float* g, float* m, float* v, uint16_t* pb, void* state, double lr,
+                  double beta1, double beta2, double eps, double wd, int bias_correction, double max_trust,
+                  const float* inv_scale, const int* found_inf, float* seg_out, void* stream) {
+  return lamb_flat((SegPlan*)plan, p, g, m, v, pb, state, lr, beta1, beta2, eps, wd, bias_correction, max_trust,
+                   inv_scale, found_inf, seg_out, S(stream));
+}
 static_assert(sizeof(dtc_ema_range) == sizeof(EmaRange) && offsetof(dtc_ema_range, src) == offsetof(EmaRange, src) &&
                   offsetof(dtc_ema_range, ema_bf16) == offsetof(EmaRange, ema_bf16) &&
                   offsetof(dtc_ema_range, n) == offsetof(EmaRange, n),

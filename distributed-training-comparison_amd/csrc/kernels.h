@@ -538,6 +538,13 @@ int seg_norms(SegPlan* plan, const float* p, const float* g, const float* gmul, 
 int lars_flat(SegPlan* plan, float* p, const float* g, float* mom, u16* p_bf16, double lr, double wd, double mu,
               int nesterov, double trust_coef, double eps, int trust_clip, const float* inv_scale,
               const int* found_inf, float* seg_out, hipStream_t st);
+// LAMB over the plan's segments (lamb.hip): the tick on `state` (DTC_LAMB_STATE_WORDS zeroed 32-bit words, 16-byte
+// aligned; word 0 the step count, not advanced on a skipped step), the moment update with the norms of p and of the
+// Adam direction u, the ratios, the update with the bf16 shadow. Four launches. max_trust = 0: no clamp.
+#define DTC_LAMB_STATE_WORDS 4
+int lamb_flat(SegPlan* plan, float* p, const float* g, float* m, float* v, u16* p_bf16, void* state, double lr,
+              double beta1, double beta2, double eps, double wd, int bias_correction, double max_trust,
+              const float* inv_scale, const int* found_inf, float* seg_out, hipStream_t st);
 // Weight EMA (ema.hip) over 1..DTC_EMA_MAX_RANGES flat ranges in one update launch behind a one-thread tick:
 // ema += (src - ema) * w, ema_bf16 = bf16(ema) where given; `state` is DTC_EMA_STATE_WORDS zeroed 32-bit words
 // (16-byte aligned): word 0 the int32 count of updates, word 1 the fp32 w of the last one. Skipped when *found_inf.

@@ -20,43 +20,10 @@
 // Every result is bit-identical from run to run. Elements between the segments (the flat buffer's 64-element
 // alignment padding) are neither read nor written.
 #include <new>
-#include <vector>
-#include "flat.h"
 #include "kernels.h"
+#include "seg.h"
 
 namespace dtc {
-
-constexpr int SEG_THREADS = 256;
-constexpr int SEG_VEC = 8;  // f32x4 per thread and buffer: sixteen 16-byte loads in flight in the norm pass
-constexpr int64_t SEG_CHUNK = (int64_t)SEG_THREADS * SEG_VEC * 4;  // 8192 elements
-constexpr int SEG_MAX = 4096;
-constexpr int64_t SEG_MAX_CHUNKS = 1 << 24;
-constexpr int SEG_KNOWN_FLAGS = 1;  // bit 0: ADAPT
-
-struct SegDev {  // one segment as the kernels read it (32 bytes)
-  int64_t offset, numel;
-  int32_t flags, first_chunk, nchunks, reserved;
-};
-struct SegChunk {  // work map: workgroup -> (segment, chunk of it)
-  int32_t seg, chunk;
-};
-struct SegSums {  // one partial slot
-  double p, g;
-};
-struct SegResult {  // per segment: ||p||, |mult| * ||g||, ratio
-  float wn, gn, ratio, reserved;
-};
-
-struct SegPlan {
-  std::vector<SegDev> segs;
-  std::vector<SegChunk> map;
-  size_t off_map = 0, off_slots = 0, off_res = 0, bytes = 0;
-  void* dev = nullptr;  // caller-owned, set by bind
-  const SegDev* d_segs() const { return (const SegDev*)dev; }
-  const SegChunk* d_map() const { return (const SegChunk*)((char*)dev + off_map); }
-  SegSums* d_slots() const { return (SegSums*)((char*)dev + off_slots); }
-  SegResult* d_res() const { return (SegResult*)((char*)dev + off_res); }
-};
 
 static size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
@@ -124,19 +91,6 @@ int segplan_bind(SegPlan* plan, void* dev, size_t bytes, hipStream_t st) {
 }
 
 // ---------------------------------------------------------------- kernels
-// this workgroup's chunk: first element and length (the last chunk of a segment is the short one)
-struct ChunkSpan {
-  int64_t base;
-  int len, flags, seg;
-};
-__device__ __forceinline__ ChunkSpan chunk_span(const SegDev* __restrict__ segs, const SegChunk* __restrict__ map) {
-  const SegChunk m = map[blockIdx.x];
-  const SegDev s = segs[m.seg];
-  const int64_t start = (int64_t)m.chunk * SEG_CHUNK;
-  const int64_t left = s.numel - start;
-  return ChunkSpan{s.offset + start, (int)(left < SEG_CHUNK ? left : SEG_CHUNK), s.flags, m.seg};
-}
-
 __global__ void __launch_bounds__(SEG_THREADS) seg_sumsq_kernel(const SegDev* __restrict__ segs,
                                                                 const SegChunk* __restrict__ map,
                                                                 const float* __restrict__ p,
@@ -180,26 +134,7 @@ __global__ void __launch_bounds__(64) seg_ratio_kernel(const SegDev* __restrict_
                                                        SegResult* __restrict__ res, float* __restrict__ seg_out) {
   const SegDev s = segs[blockIdx.x];
   const double mult = inv_scale ? (double)*inv_scale : 1.0;  // loaded beside the record, not behind the fold
-  constexpr int TILE = 512;  // slots per memory latency (ResNet-18's largest tensor has 288), summed in index order
-  __shared__ SegSums sh[TILE];
-  double sp = 0.0, sg = 0.0;
-  for (int base = 0; base < s.nchunks; base += TILE) {
-#pragma unroll
-    for (int j = 0; j < TILE / 64; ++j) {
-      const int k = base + j * 64 + threadIdx.x;
-      if (k < s.nchunks) sh[j * 64 + threadIdx.x] = slots[s.first_chunk + k];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const int m = s.nchunks - base < TILE ? s.nchunks - base : TILE;
-#pragma unroll 8
-      for (int j = 0; j < m; ++j) {
-        sp += sh[j].p;
-        sg += sh[j].g;
-      }
-    }
-    __syncthreads();
-  }
+  DTC_SEG_FOLD_SLOTS(s, slots, sp, sg)
   if (threadIdx.x != 0) return;
   const double wn = sqrt(sp), gn = fabs(mult) * sqrt(sg);
   double ratio = 1.0;

@@ -63,15 +63,6 @@ struct AdamState {
 };
 static_assert(sizeof(AdamState) == 4 * DTC_ADAM_STATE_WORDS, "AdamState is DTC_ADAM_STATE_WORDS 32-bit words");
 
-// b^t by squaring, in double: at most 62 multiplications (1 - b^t within 2e-14 of pow()'s, invisible once
-// the factors are rounded to float), a fraction of the time of two library pow() calls in a one-thread kernel
-__device__ __forceinline__ double pow_int(double b, int t) {
-  double r = 1.0;
-  for (; t > 0; t >>= 1, b *= b)
-    if (t & 1) r *= b;
-  return r;
-}
-
 __global__ void adam_tick_kernel(AdamState* __restrict__ s, double lr, double b1, double b2,
                                  const int* __restrict__ found_inf) {
   if (found_inf && *found_inf) return;

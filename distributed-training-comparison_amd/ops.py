@@ -771,6 +771,25 @@ def lars_flat(plan, p, g, mom, pb, lr, weight_decay, momentum, nesterov=False, t
          ptr(found_inf), ptr(seg_out), stream_ptr())
 
 
+def lamb_state(device):
+    """The zeroed device state record of one lamb_flat optimizer (word 0: the int32 step count)."""
+    return torch.zeros(lib.dtc_lamb_state_words(), dtype=torch.int32, device=device)
+
+
+def lamb_flat(plan, p, g, m, v, pb, state, lr, beta1, beta2, eps, weight_decay, bias_correction=True, max_trust=0.0,
+              inv_scale=None, found_inf=None, seg_out=None):
+    """One LAMB step over the plan's segments of the flat fp32 buffers (include/dtc.h: dtc_lamb_flat): the Adam
+    moments `m`, `v` updated in place, the bf16 shadow `pb` refreshed; `state` from lamb_state() carries the
+    device-side step count. `seg_out` (optional fp32 [nseg, 3]) receives (||p||, ||u||, trust ratio) per segment."""
+    _seg_check(plan, p, g, m, v, pb)
+    require_cuda(state)
+    if seg_out is not None:
+        seg_out = _seg_out(plan, seg_out)
+    call("dtc_lamb_flat", plan.handle, ptr(p), ptr(g), ptr(m), ptr(v), ptr(pb), ptr(state), float(lr), float(beta1),
+         float(beta2), float(eps), float(weight_decay), int(bool(bias_correction)), float(max_trust), ptr(inv_scale),
+         ptr(found_inf), ptr(seg_out), stream_ptr())
+
+
 def eval_batch_weights(net, params, params_bf16, bufs, x, labels, n_valid, topk, rec, logits=None):
     """dtc_rn18_eval_batch_weights on the executor handle `net`: one evaluation batch read from the given flat
     parameter / bf16 shadow / running-statistics tensors (the bound buffers' layout) instead of the bound ones."""

@@ -1,4 +1,4 @@
-"""optim.SGD / Adam / AdamW mirrors, LARS and the SAM wrapper running fused flat-buffer kernels, and clip_grad_norm_.
+"""optim.SGD / Adam / AdamW mirrors, LARS, LAMB and the SAM wrapper on fused flat-buffer kernels, and clip_grad_norm_.
 
 Reference: ``optim.SGD(self.model.parameters(), lr, weight_decay, momentum=0.9, nesterov=True)``
 (src/ddp/trainer.py:92-98) stepped through ``GradScaler.step`` (trainer.py:158); the reference's README
@@ -311,6 +311,57 @@ class LARS(_FlatOptimizer):
         return self._norms, self._plan.names
 
 
+class LAMB(_FlatOptimizer):
+    """LAMB (You et al. 2020): Adam whose step is scaled per parameter tensor by the trust ratio ``||p|| / ||u||``
+    (at most ``max_trust`` when that is positive), ``u`` being the bias-corrected Adam direction plus
+    ``weight_decay * p``. The ratio and the weight decay apply to parameters with more than one dimension (conv and
+    linear weights); BatchNorm weights / biases and ``linear.bias`` take the plain Adam step. The moments and the norms
+    are formed on the device at every step (four launches, no host synchronisation, bit-reproducible); the step count
+    lives on the device and does not advance on a step GradScaler skips."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, bias_correction=True,
+                 max_trust=0.0):
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 < eps:
+            raise ValueError(f"Invalid epsilon value: {eps} (the fused kernel needs eps > 0)")
+        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError(f"Invalid beta parameters: {betas}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if not 0.0 <= max_trust:
+            raise ValueError(f"Invalid max_trust value: {max_trust} (0 means no clamp)")
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, bias_correction=bias_correction,
+                        max_trust=max_trust)
+        super().__init__(params, defaults)
+        self._exp_avg = self._exp_avg_sq = self._step_state = self._plan = self._norms = None
+
+    _STATE_BUFFERS = (("exp_avg", "_exp_avg"), ("exp_avg_sq", "_exp_avg_sq"))  # (_norms: rewritten by every step)
+
+    _get_step = Adam._get_step
+    _set_step = Adam._set_step
+
+    def _init_state(self, flat):
+        self._exp_avg = torch.zeros_like(flat.params)
+        self._exp_avg_sq = torch.zeros_like(flat.params)
+        self._step_state = ops.lamb_state(flat.params.device)
+        self._plan = ops.seg_plan(flat.layout, flat.device)  # the handle keeps its device memory (plan.mem)
+        self._norms = torch.zeros(self._plan.nseg, 3, dtype=torch.float32, device=flat.device)
+
+    def _update(self, flat, g, grad_mult, found_inf):
+        ops.lamb_flat(self._plan, flat.params, flat.grads, self._exp_avg, self._exp_avg_sq, flat.params_bf16,
+                      self._step_state, g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"],
+                      g["bias_correction"], g["max_trust"], grad_mult, found_inf, self._norms)
+
+    def layer_norms(self):
+        """(norms, names): the last non-skipped step's fp32 [n, 3] device tensor of (||p|| before the update, ||u||
+        of the Adam direction with weight decay, trust ratio applied) per parameter, and the parameter names, in
+        flat-buffer order. No synchronisation: the tensor is the one the next step overwrites (clone to keep)."""
+        if self._plan is None:
+            raise NativeError("LAMB.layer_norms: no step has run yet")
+        return self._norms, self._plan.names
+
+
 class SAM(Optimizer):
     """Sharpness-aware minimisation (Foret et al. 2021; ``adaptive=True``: ASAM, Kwon et al. 2021, typical rho 0.5
     to 2.0) around one of the fused optimizers above. One optimizer step is two passes over the same batch:
@@ -334,7 +385,7 @@ class SAM(Optimizer):
 
     def __init__(self, base_optimizer, rho=0.05, adaptive=False, eps=1e-12):
         if not isinstance(base_optimizer, _FlatOptimizer):
-            raise TypeError("SAM wraps one of this package's fused optimizers (SGD, Adam, AdamW, LARS), not "
+            raise TypeError("SAM wraps one of this package's fused optimizers (SGD, Adam, AdamW, LARS, LAMB), not "
                             f"{type(base_optimizer).__name__}")
         if not 0.0 <= rho:
             raise ValueError(f"Invalid rho value: {rho}")
@@ -431,7 +482,7 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, scaler=None) -> torch.T
     tensor, without a host synchronisation.
 
     Deviation from torch: the gradients are NOT rewritten. The multiplier is stored on the model's
-    FlatState and the next ``step()`` of SGD / Adam / AdamW / LARS applies it where it would apply ``inv_scale``
+    FlatState and the next ``step()`` of SGD / Adam / AdamW / LARS / LAMB applies it where it would apply ``inv_scale``
     (no extra read-modify-write pass over the gradients); ``p.grad`` keeps showing the unclipped values.
     """
     if float(norm_type) != 2.0:

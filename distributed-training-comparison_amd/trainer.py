@@ -26,7 +26,7 @@ from . import data as D
 from .amp import GradScaler, autocast
 from .ema import ModelEma
 from .nn import CrossEntropyLoss, ResNet18, SyncBatchNorm
-from .optim import LARS, SAM, SGD, Adam, AdamW, clip_grad_norm_
+from .optim import LAMB, LARS, SAM, SGD, Adam, AdamW, clip_grad_norm_
 from .parallel import DDP, DataParallel, PowerSGDState, barrier, bf16_compress_hook, powerSGD_hook
 
 FP32_CONV = ("exact", "split", "split-all", "split-s2", "split-full")  # --fp32-conv: the value of option f32_split is the index
@@ -81,6 +81,11 @@ def load_config(argv=None, mode: str = "ddp"):
                    help="--optimizer lars: ratio = coef * ||p|| / (||g|| + weight_decay * ||p|| + eps)")
     p.add_argument("--lars-clip", action="store_true", default=False,
                    help="--optimizer lars: LARC clipping, ratio = min(ratio / lr, 1)")
+    p.add_argument("--lamb", action="store_true", default=False,
+                   help="--optimizer adamw: LAMB, the per-tensor trust ratio ||p|| / ||u|| on the Adam direction u "
+                        "(with the same --lr / --weight-decay), for large global batches")
+    p.add_argument("--lamb-max-trust", type=float, default=0.0,
+                   help="--lamb: ratio = min(ratio, this) (0 = no clamp)")
     p.add_argument("--warmup-epochs", type=int, default=0,
                    help="linear warm-up: epoch e < N runs at lr * (e + 1) / N and StepLR's count starts at epoch N "
                         "(0 = off: the reference's plain StepLR)")
@@ -157,6 +162,10 @@ def load_config(argv=None, mode: str = "ddp"):
         p.error("--powersgd-start-iter must be at least 2")
     if h.warmup_epochs < 0 or not h.lars_trust_coef > 0:
         p.error("--warmup-epochs must be >= 0 and --lars-trust-coef > 0")
+    if h.lamb and h.optimizer != "adamw":
+        p.error("--lamb turns --optimizer adamw into LAMB: not with --optimizer " + h.optimizer)
+    if not h.lamb_max_trust >= 0.0:
+        p.error("--lamb-max-trust must be >= 0")
     if (h.mixup_alpha > 0 or h.cutmix_alpha > 0) and not h.device_data:
         p.error("--mixup-alpha / --cutmix-alpha need --device-data (the host loader does not mix)")
     if not 1 <= h.ra_num_ops <= 4 or not 0 <= h.ra_magnitude <= 30 or not 0.0 <= h.random_erasing <= 1.0:
@@ -190,7 +199,7 @@ def load_config(argv=None, mode: str = "ddp"):
 # process-group address may differ.
 RESUME_KEYS = (
     "dset", "model", "seed", "batch_size", "synthetic_train", "device_data", "amp",
-    "optimizer", "lr", "weight_decay", "lars_trust_coef", "lars_clip", "clip_grad_norm",
+    "optimizer", "lr", "weight_decay", "lars_trust_coef", "lars_clip", "lamb", "lamb_max_trust", "clip_grad_norm",
     "lr_decay_step_size", "lr_decay_gamma", "warmup_epochs",
     "label_smoothing", "mixup_alpha", "cutmix_alpha", "mix_prob",
     "auto_augment", "ra_num_ops", "ra_magnitude", "random_erasing",
@@ -465,6 +474,9 @@ class Trainer:
         elif h.optimizer == "lars":  # the sgd branch plus the trust ratio
             optimizer = LARS(self.model.parameters(), lr=h.lr, weight_decay=h.weight_decay, momentum=0.9,
                              nesterov=True, trust_coef=h.lars_trust_coef, trust_clip=h.lars_clip)
+        elif getattr(h, "lamb", False):  # the adamw branch plus the trust ratio
+            optimizer = LAMB(self.model.parameters(), lr=h.lr, weight_decay=h.weight_decay,
+                             max_trust=h.lamb_max_trust)
         else:
             cls = {"adam": Adam, "adamw": AdamW}[h.optimizer]
             optimizer = cls(self.model.parameters(), lr=h.lr, weight_decay=h.weight_decay)

@@ -448,6 +448,35 @@ int dtc_seg_norms(dtc_segplan* plan, const float* p, const float* g, const float
 int dtc_lars_flat(dtc_segplan* plan, float* p, const float* g, float* momentum_buf, uint16_t* p_bf16, double lr,
                   double weight_decay, double momentum, int nesterov, double trust_coef, double eps, int trust_clip,
                   const float* inv_scale, const int* found_inf, float* seg_out, void* stream);
+/* lamb: LAMB (You et al. 2020) = Adam whose step is scaled per tensor by the trust ratio ||p|| / ||u||, u being the
+ * Adam direction formed from the moments as this step updates them. With mult = *inv_scale (NULL: 1; GradScaler's
+ * 1/scale or dtc_grad_norm_clip's grad_mult) and t the count of non-skipped steps including this one, per element:
+ *   g' = g * mult
+ *   m  = m + (g' - m) * (1 - beta1)                        (one fused multiply-add, as dtc_adam_flat)
+ *   v  = beta2 * v + (1 - beta2) * g' * g'
+ *   r  = (m / bc1) / (sqrt(v) / sqrt(bc2) + eps)           bc1 = 1 - beta1^t, bc2 = 1 - beta2^t;
+ *                                                          bias_correction = 0: bc1 = bc2 = 1
+ *   u  = r + wd_s * p                                      wd_s = weight_decay on ADAPT segments, 0 elsewhere
+ * and per segment s, sums and sqrt in double (dtc_seg_norms' fixed order):
+ *   wn = sqrt(sum p^2), un = sqrt(sum u^2)                 (p before the update)
+ *   ADAPT:      ratio = (wn > 0 && un > 0) ? wn / un : 1, with max_trust > 0 min(ratio, max_trust); rounded once to
+ *               fp32
+ *   otherwise:  ratio = 1                                  (a bias-corrected Adam step without weight decay)
+ *   p -= lr * ratio * u ;  p_bf16 = bf16(p)
+ * `state` is dtc_lamb_state_words() (= 4) 32-bit words of device memory, 16-byte aligned, zeroed by the caller before
+ * the first step and owned by the library afterwards: word 0 is the int32 count t, advanced on the device and only by
+ * a step that is not skipped. The whole step is skipped when *found_inf != 0 (NULL: never): p, exp_avg, exp_avg_sq,
+ * p_bf16, the count and seg_out stay bit-unchanged. Elements outside the segments are neither read nor written; g is
+ * only read. seg_out (optional, device fp32 [nseg][3]) = (wn, un, ratio applied). Four launches (tick, moments +
+ * norms, ratios, update; u is formed twice by the same code rather than stored), no host synchronisation, no
+ * floating-point atomics, bit-identical from run to run. Requires eps > 0, betas in [0, 1), lr, weight_decay,
+ * max_trust >= 0 (0: no clamp); p, g, exp_avg, exp_avg_sq, state 16-byte aligned, p_bf16 8-byte aligned; a bound
+ * plan. */
+int dtc_lamb_state_words(void);
+int dtc_lamb_flat(dtc_segplan* plan, float* p, const float* g, float* exp_avg, float* exp_avg_sq, uint16_t* p_bf16,
+                  void* state, double lr, double beta1, double beta2, double eps, double weight_decay,
+                  int bias_correction, double max_trust, const float* inv_scale, const int* found_inf, float* seg_out,
+                  void* stream);
 /* ema: an exponential moving average of the weights (timm ModelEma, torchvision's --model-ema,
  * tf.train.ExponentialMovingAverage) over 1..4 flat ranges in ONE update launch -- a model's parameters and its
  * BatchNorm running statistics together. Per element of every range

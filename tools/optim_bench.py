@@ -1,5 +1,5 @@
-"""Optimizer-stage timing: adam_flat and lars_flat against sgd_nesterov, grad_norm_clip against amp_check_finite,
-and the training step with AdamW + clip and with LARS against SGD.
+"""Optimizer-stage timing: adam_flat, lars_flat and lamb_flat against sgd_nesterov, grad_norm_clip against
+amp_check_finite, and the training step with AdamW + clip and with LARS against SGD.
 
     python tools/optim_bench.py [--reps 20] [--inner 20] [--steps 40] [--batch 256] [--sam] [--out FILE]
 
@@ -8,8 +8,9 @@ each repetition times `inner` back-to-back launches of one kernel between two de
 repetitions of the kernels of a pair ALTERNATE, so both see the same machine state. Bytes per element by the
 algorithm: sgd 5 x 4 + 2 = 22 B, adam 7 x 4 + 2 = 30 B, lars sgd's 22 B + the norm pass's 8 B = 30 B, seg_norms
 (lars_flat's first two launches on their own: the norm pass over p and g and the ratios) 8 B, the two read passes
-4 B. adam_flat's time includes its one-thread tick launch, lars_flat's all three of its launches, grad_norm_clip's
-its finalize launch (what a step pays).
+4 B, lamb 24 B (moments + norms: p, g, m, v read, m, v written) + 18 B (update: p, m, v read, p and the bf16 shadow
+written) = 42 B. adam_flat's time includes its one-thread tick launch, lars_flat's all three of its launches,
+lamb_flat's all four, grad_norm_clip's its finalize launch (what a step pays).
 
 Step: bench.py's single-GPU loop body (autocast forward + CrossEntropy, scaler.scale(loss).backward(),
 scaler.step, scaler.update, loss.item()) at batch 256, bf16, with SGD, with AdamW + unscale_ + clip_grad_norm_
@@ -62,7 +63,7 @@ def main():
     n, nparam = flat.params.numel(), sum(p.numel for p in flat.layout.params)
     flat.grads.normal_(0, 1e-2)
     mom, m, v = (torch.zeros_like(flat.params) for _ in range(3))
-    state = ops.adam_state(dev)
+    state, lamb_state = ops.adam_state(dev), ops.lamb_state(dev)
     found = torch.zeros(1, dtype=torch.int32, device=dev)
     inv = torch.ones(1, device=dev)
     ws = ops.grad_norm_workspace(n, dev)
@@ -77,11 +78,13 @@ def main():
                                             1e-8, 1e-2, True, inv, found), 30),
         "lars_flat": (lambda: ops.lars_flat(plan, flat.params, flat.grads, mom, flat.params_bf16, 1e-3, 1e-4, 0.9, True,
                                             1e-3, 1e-8, False, inv, found, seg_out), 30),
+        "lamb_flat": (lambda: ops.lamb_flat(plan, flat.params, flat.grads, m, v, flat.params_bf16, lamb_state, 1e-3, 0.9,
+                                            0.999, 1e-6, 1e-2, True, 0.0, inv, found, seg_out), 42),
         "seg_norms": (lambda: ops.seg_norms(plan, flat.params, flat.grads, inv, seg_out), 8),
         "amp_check_finite": (lambda: ops.amp_check_finite(flat.grads, found), 4),
         "grad_norm_clip": (lambda: ops.grad_norm_clip(flat.grads, 1.0, inv, ws, tn, gm), 4),
     }
-    sets = (("sgd_nesterov", "adam_flat", "lars_flat", "seg_norms"), ("amp_check_finite", "grad_norm_clip"))
+    sets = (("sgd_nesterov", "adam_flat", "lars_flat", "lamb_flat", "seg_norms"), ("amp_check_finite", "grad_norm_clip"))
     if a.sam:
         saved, sam_state, sam_ws = torch.empty_like(flat.params), ops.sam_state(dev), ops.sam_workspace(n, dev)
         keep = [(flat.bufs, torch.empty_like(flat.bufs)), (flat.nbt, torch.empty_like(flat.nbt))]
@@ -131,6 +134,7 @@ def main():
         line["adam_over_sgd_bandwidth"] = ks["adam_flat"]["TBps_median"] / ks["sgd_nesterov"]["TBps_median"]
         line["lars_over_sgd_bandwidth"] = ks["lars_flat"]["TBps_median"] / ks["sgd_nesterov"]["TBps_median"]
         line["lars_over_adam_time"] = ks["lars_flat"]["median_ms"] / ks["adam_flat"]["median_ms"]
+        line["lamb_over_adam_time"] = ks["lamb_flat"]["median_ms"] / ks["adam_flat"]["median_ms"]
         line["norm_over_check_bandwidth"] = (ks["grad_norm_clip"]["TBps_median"] /
                                              ks["amp_check_finite"]["TBps_median"])
 
